@@ -67,6 +67,51 @@ def get_timings(lib, baker):
     return tm
 
 
+# --dump-outputs: per-array caps in elements (float32 arrayData bytes 32 MiB, float64 descs 12 MiB, float64 indices 8 MiB: under 64 MiB in all)
+DUMP_CAPS = {"array_data": 8 << 20, "desc_array": 512 << 10, "index_buffer": 1 << 20}
+DUMP_SEED = 20240601
+
+
+def dump_outputs(dirname, rd, fetch):
+    """Writes the arrays an ommCpuBakeResultDesc hands its caller as DIR/<name>.npy, every value exact in float32 / float64.  fetch(ptr, nbytes) -> uint8
+    array of the bulk data (host memory for ommCpuBake, a device copy for the device-resident entry; the histograms are host arrays on both).  An array
+    longer than its DUMP_CAPS entry is written as a fixed, seeded sample of its elements (sorted positions: the same for the same length);
+    result_sizes.npy holds the full lengths and the index format.  -> {name: {"shape", "of"}}"""
+    usage = np.dtype([("a", "<u4"), ("b", "<u2"), ("c", "<u2")])   # ommCpuOpacityMicromapDesc and ommCpuOpacityMicromapUsageCount share this layout
+
+    def triples(raw):
+        t = raw.view(usage)
+        return np.stack([t["a"], t["b"], t["c"]], axis=1).astype(np.float64).reshape(-1, 3)
+
+    def sample(name, a):
+        cap = DUMP_CAPS[name]
+        if a.shape[0] <= cap:
+            return a
+        return a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], cap, replace=False))]
+
+    def host(ptr, nbytes):
+        return np.frombuffer(C.string_at(ptr, nbytes), np.uint8) if nbytes else np.zeros(0, np.uint8)
+
+    def bulk(ptr, nbytes):
+        return fetch(ptr, nbytes) if nbytes else np.zeros(0, np.uint8)
+
+    isz, idt = {ot.IDX_U8: (1, np.int8), ot.IDX_U16: (2, np.int16), ot.IDX_U32: (4, np.int32)}[rd.indexFormat]
+    arrays = {
+        "array_data": sample("array_data", bulk(rd.arrayData, rd.arrayDataSize)).astype(np.float32),
+        "desc_array": sample("desc_array", triples(bulk(C.cast(rd.descArray, C.c_void_p).value, 8 * rd.descArrayCount))),
+        "index_buffer": sample("index_buffer", bulk(rd.indexBuffer, isz * rd.indexCount).view(idt)).astype(np.float64),
+        "desc_array_histogram": triples(host(C.cast(rd.descArrayHistogram, C.c_void_p).value, 8 * rd.descArrayHistogramCount)),
+        "index_histogram": triples(host(C.cast(rd.indexHistogram, C.c_void_p).value, 8 * rd.indexHistogramCount)),
+        "result_sizes": np.array([rd.arrayDataSize, rd.descArrayCount, rd.indexCount, rd.indexFormat], np.float64),
+    }
+    full = {"array_data": rd.arrayDataSize, "desc_array": rd.descArrayCount, "index_buffer": rd.indexCount}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {name: {"shape": list(a.shape), "of": int(full.get(name, a.shape[0]))} for name, a in arrays.items()}
+
+
 def source_hash():
     """sha256 (16 hex digits) over omm_amd/csrc, the same recipe as profiles/summarize_pmc.py: ties a committed PMC summary to the sources"""
     import hashlib
@@ -231,6 +276,8 @@ def main():
     ap.add_argument("--devices", type=int, default=0, help="ommxBakerKnob_Devices for the ommCpuBake measurement: the bake spread over N devices of THIS process (on a one-GPU box the ranks share the device)")
     ap.add_argument("--expand-threads", type=int, default=0, help="ommxBakerKnob_ExpandThreads (0 = library default)")
     ap.add_argument("--zero-ahead", type=int, default=0, help="ommxBakerKnob_ZeroAhead (0 = library default: on, 1 = off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the result arrays of the last timed step as DIR/<name>.npy "
+                                                                           "(float32 / float64, at most 64 MB in all: long arrays as a fixed, seeded sample)")
     ap.add_argument("--concurrent", type=int, default=0, help="also measure K host threads baking concurrently on ONE baker through ommCpuBake (bakes/s for 1, 4, .. K threads; "
                                                               "the reference documents caller-level parallelism as a first-class strategy, docs/integration_guide.md:434)")
     args = ap.parse_args()
@@ -382,6 +429,10 @@ def main():
     prod.dll.ommxGetDeviceBakeResultDesc(last, C.byref(pd))
     rd = pd.contents
     result_info = {"arrayDataBytes": int(rd.arrayDataSize), "descs": int(rd.descArrayCount), "triangles": int(rd.indexCount)}
+    dumped = None
+    if args.dump_outputs and rank == 0 and not (world == 1 and host_steps > 0):   # the device-resident bake is the timed path of this run
+        hip = ot.Hip()
+        dumped = dump_outputs(args.dump_outputs, rd, hip.download)
     prod.dll.ommxDestroyDeviceBakeResult(last)
 
     # ---- the SDK entry point proper: host arrays in, host arrays out (metric 2) ----
@@ -399,12 +450,21 @@ def main():
             assert r == ot.SUCCESS
             prod.fn("ommCpuDestroyBakeResult")(out)
         t1 = time.perf_counter()
-        for _ in range(host_steps):
+        kept = None
+        for i in range(host_steps):
             r, out = prod.bake_raw(baker, host_desc)
             assert r == ot.SUCCESS
             host_tms.append(get_timings(prod, baker))
-            prod.fn("ommCpuDestroyBakeResult")(out)
+            if args.dump_outputs and i == host_steps - 1:
+                kept = out   # (destroyed after the clock stops, once its arrays are written)
+            else:
+                prod.fn("ommCpuDestroyBakeResult")(out)
         host_ms = (time.perf_counter() - t1) / host_steps * 1e3
+        if kept is not None:
+            hpd = C.POINTER(ot.BakeResultDesc)()
+            assert prod.fn("ommCpuGetBakeResultDesc")(kept, C.byref(hpd)) == ot.SUCCESS
+            dumped = dump_outputs(args.dump_outputs, hpd.contents, lambda ptr, n: np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), (n,)))
+            prod.fn("ommCpuDestroyBakeResult")(kept)
     if args.devices:
         prod.set_knob(baker, ot.KNOB_DEVICES, 0)
 
@@ -605,6 +665,8 @@ def main():
                 prod.destroy_texture(baker, th2)
                 line["sat_off"] = {"entry": "ommCpuBake (host arrays, PCIe inclusive), texture without alphaCutoff", "gpu_micro_triangles_per_s": gmt / gpu_dt,
                                    "gpu_sample": "first %d triangles, %.1f ms" % (ks, gpu_dt * 1e3), "cpu_baseline": cb2, "speedup": (gmt / gpu_dt) / cb2["value"], "parity": "bit-exact on the CPU sample"}
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "entry": line["value_entry"], "arrays": dumped}
         print(json.dumps(line))
     if world > 1:
         torch.cuda.synchronize()

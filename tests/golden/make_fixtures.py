@@ -13,6 +13,7 @@ Outputs (data only -- inputs and expected outputs, no reference source text):
   leaflet.json    its dimensions.
   texcoord_kat.json  the GetTexCoord input/expected tables of support/tests/test_texture.cpp:40-266.
   sdk_exports.txt    the names of the 25 OMM_API functions libraries/omm-lib/include/omm.h declares (= the SDK library's export list).
+  sdk_user_symbols.txt  the omm* symbols tests/native/sdk_user.cpp and sdk_user_hpp.cpp reference when compiled against the SDK's headers.
 """
 import json, os, re, sys
 
@@ -55,6 +56,19 @@ def extract_leaflet():
     return w, h, ch, blue
 
 
+def extract_sdk_user_symbols():
+    import subprocess, tempfile
+    root = os.path.dirname(os.path.dirname(HERE))
+    names = set()
+    with tempfile.TemporaryDirectory() as td:
+        for unit in ("sdk_user", "sdk_user_hpp"):
+            obj = os.path.join(td, unit + ".o")
+            subprocess.check_call(["g++", "-std=c++17", "-Wno-deprecated-declarations", "-I" + os.path.join(REF, "libraries/omm-lib/include"), "-c",
+                                   os.path.join(root, "tests", "native", unit + ".cpp"), "-o", obj])
+            names |= {ln.split()[-1] for ln in subprocess.check_output(["nm", "-u", obj], text=True).splitlines() if ln.split()[-1].startswith("omm")}
+    return sorted(names)
+
+
 if __name__ == "__main__":
     blobs = extract_blobs()
     json.dump(blobs, open(os.path.join(HERE, "blobs.json"), "w"), indent=0, sort_keys=True)
@@ -69,6 +83,9 @@ if __name__ == "__main__":
     ex = extract_sdk_exports()
     open(os.path.join(HERE, "sdk_exports.txt"), "w").write("\n".join(ex) + "\n")
     print("sdk exports:", len(ex))
+    us = extract_sdk_user_symbols()
+    open(os.path.join(HERE, "sdk_user_symbols.txt"), "w").write("\n".join(us) + "\n")
+    print("sdk user symbols:", len(us))
 
 
 def make_abi_layout():

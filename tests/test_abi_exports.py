@@ -202,53 +202,41 @@ def test_struct_layouts_and_enum_values_equal_the_sdk_header(tmp_path):
         assert _abi_facts(sdk, "<omm.h>", tmp_path, "sdk") == golden
 
 
+def sdk_user_symbols():
+    return open(os.path.join(ROOT, "tests", "golden", "sdk_user_symbols.txt")).read().split()
+
+
 def test_sdk_header_user_links_against_the_drop_in(tmp_path):
-    """A translation unit compiled against the SDK's OWN omm.h (C++: that header is not valid C) links against libomm-lib.so:
-    every CPU-baker symbol it references resolves.  Only where the reference checkout exists."""
+    """A translation unit compiled against the SDK's OWN omm.h / omm.hpp (tests/native/sdk_user*.cpp) links against libomm-lib.so: every
+    CPU-baker symbol it references resolves.  The symbols those units reference are a committed fixture (tests/golden/sdk_user_symbols.txt):
+    a program that references exactly them links and loads.  Where the SDK headers exist the units themselves are compiled, linked and
+    run, and their references are re-checked against the fixture."""
     import subprocess
+    names = sdk_user_symbols()
+    assert len(names) == 16 and set(names) <= set(sdk_exports()), names
+    lib_dir = os.path.join(ROOT, "omm_amd", "lib")
+    src = tmp_path / "sdk_user_symbols.c"
+    src.write_text("#include <stdio.h>\n" + "".join("extern void %s(void);\n" % n for n in names) +
+                   "int main(void) { void (*f[])(void) = { %s }; unsigned k = 0, i; for (i = 0; i < sizeof f / sizeof f[0]; ++i) k += f[i] != 0; printf(\"%%u\\n\", k); return 0; }\n"
+                   % ", ".join(names))
+    exe = str(tmp_path / "sdk_user_symbols")
+    r = subprocess.run(["gcc", str(src), "-o", exe, "-L" + lib_dir, "-lomm-lib", "-Wl,-rpath," + lib_dir, "-Wl,--no-as-needed"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert subprocess.check_output([exe], text=True).strip() == str(len(names))
     sdk = "/root/reference/libraries/omm-lib/include"
     if not os.path.exists(os.path.join(sdk, "omm.h")):
-        pytest.skip("reference checkout not present")
-    src = tmp_path / "user.cpp"
-    src.write_text('''#include <omm.h>
-int main() {
-    ommBakerCreationDesc bd = ommBakerCreationDescDefault(); bd.type = ommBakerType_CPU;
-    ommBaker baker = 0; if (ommCreateBaker(&bd, &baker) != ommResult_SUCCESS) return 1;
-    ommCpuTextureDesc td = ommCpuTextureDescDefault(); ommCpuTexture tex = 0; (void)ommCpuCreateTexture(baker, &td, &tex);
-    ommCpuBakeInputDesc in = ommCpuBakeInputDescDefault(); ommCpuBakeResult res = 0; (void)ommCpuBake(baker, &in, &res);
-    const ommCpuBakeResultDesc* out = 0; (void)ommCpuGetBakeResultDesc(res, &out);
-    ommDebugStats st = ommDebugStatsDefault(); (void)ommDebugGetStats(baker, out, &st);
-    ommCpuDeserializedDesc dd = ommCpuDeserializedDescDefault(); ommCpuSerializedResult sr = 0; (void)ommCpuSerialize(baker, dd, &sr);
-    const ommCpuBlobDesc* blob = 0; (void)ommCpuGetSerializedResultDesc(sr, &blob); (void)ommCpuDestroySerializedResult(sr);
-    ommCpuBlobDesc bdsc = ommCpuBlobDescDefault(); ommCpuDeserializedResult dr = 0; (void)ommCpuDeserialize(baker, bdsc, &dr);
-    const ommCpuDeserializedDesc* ddo = 0; (void)ommCpuGetDeserializedDesc(dr, &ddo); (void)ommCpuDestroyDeserializedResult(dr);
-    ommCpuTextureDesc q = ommCpuTextureDescDefault(); (void)ommCpuGetTextureDesc(tex, &q);
-    (void)ommCpuDestroyBakeResult(res); (void)ommCpuDestroyTexture(baker, tex); (void)ommGetLibraryDesc();
-    return ommDestroyBaker(baker) == ommResult_SUCCESS ? 0 : 2;
-}
-''')
-    lib_dir = os.path.join(ROOT, "omm_amd", "lib")
-    r = subprocess.run(["g++", "-std=c++17", "-Wno-deprecated-declarations", "-I" + sdk, str(src), "-o", str(tmp_path / "user"), "-L" + lib_dir, "-lomm-lib",
-                        "-Wl,-rpath," + lib_dir], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    # the SDK's header-only C++ wrapper (omm.hpp:1003-1013 forwards to the same C symbols)
-    src2 = tmp_path / "user_hpp.cpp"
-    src2.write_text('''#include <omm.hpp>
-int main() {
-    omm::BakerCreationDesc bd; bd.type = omm::BakerType::CPU;
-    omm::Baker baker = 0; if (omm::CreateBaker(bd, &baker) != omm::Result::SUCCESS) return 1;
-    omm::Cpu::TextureDesc td; omm::Cpu::Texture tex = 0; (void)omm::Cpu::CreateTexture(baker, td, &tex);
-    omm::Cpu::BakeInputDesc in; omm::Cpu::BakeResult res = 0; (void)omm::Cpu::Bake(baker, in, &res);
-    const omm::Cpu::BakeResultDesc* out = 0; (void)omm::Cpu::GetBakeResultDesc(res, &out);
-    (void)omm::Cpu::DestroyBakeResult(res); (void)omm::Cpu::DestroyTexture(baker, tex);
-    return omm::DestroyBaker(baker) == omm::Result::SUCCESS ? 0 : 2;
-}
-''')
-    exe2 = str(tmp_path / "user_hpp")
-    r = subprocess.run(["g++", "-std=c++17", "-Wno-deprecated-declarations", "-I" + sdk, str(src2), "-o", exe2, "-L" + lib_dir, "-lomm-lib",
-                        "-Wl,-rpath," + lib_dir], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    assert subprocess.run([exe2]).returncode == 0      # baker create/destroy and the argument checks need no GPU
+        return
+    referenced = set()
+    for unit in ("sdk_user", "sdk_user_hpp"):
+        obj, exe = str(tmp_path / (unit + ".o")), str(tmp_path / unit)
+        r = subprocess.run(["g++", "-std=c++17", "-Wno-deprecated-declarations", "-I" + sdk, "-c", os.path.join(ROOT, "tests", "native", unit + ".cpp"), "-o", obj],
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        referenced |= {ln.split()[-1] for ln in subprocess.check_output(["nm", "-u", obj], text=True).splitlines() if ln.split()[-1].startswith("omm")}
+        r = subprocess.run(["g++", obj, "-o", exe, "-L" + lib_dir, "-lomm-lib", "-Wl,-rpath," + lib_dir], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+    assert sorted(referenced) == names
+    assert subprocess.run([exe]).returncode == 0      # (the omm.hpp user) baker create/destroy and the argument checks need no GPU
 
 
 def test_baker_knobs_are_per_baker_state_not_environment():
