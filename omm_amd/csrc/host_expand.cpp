@@ -234,21 +234,20 @@ void expand(uint8_t* dst, uint64_t dstBytes, const uint8_t* stream, const HostCo
             bool same = (w0 & 0xCCCCCCCCCCCCCCCCull) == 0 && ((w0 >> 4) & 0x0F0F0F0F0F0F0F0Full) == (w0 & 0x0F0F0F0F0F0F0F0Full) && w0 == (w0 & 0xFF) * 0x0101010101010101ull;
             for (int k = 1; same && k < 16; ++k) { uint64_t w; memcpy(&w, codes + 8 * k, 8); same = w == w0; }
             if (same) {
-                // (a block of zeros in a piece of the array that was zeroed while the device was baking: nothing to write)
-                if (zeroed && (w0 & 3u) == 0u) {
-                    const size_t piece = (size_t)((u0 * 16u) >> 21);
-                    if (piece < zeroed->pieces && zeroed->done[piece].load(std::memory_order_acquire)) { skippedHere += 4096u; continue; }
-                }
+                // (a block of zeros in a part of the array that was zeroed while the device was baking: nothing to write)
+                if (zeroed && (w0 & 3u) == 0u && zeroed_range(*zeroed, u0 * 16u, u0 * 16u + 4096u)) { skippedHere += 4096u; continue; }
                 if (NT && ((uintptr_t)d & 31u) == 0u) { g_fill4k(d, kPattern[w0 & 3u]); continue; }
                 const __m128i v = _mm_set1_epi32((int)kPattern[w0 & 3u]);
                 for (int k = 0; k < 256; ++k) put16<NT>(d + 16 * k, v);
                 continue;
             }
-            // (in a zeroed piece, a 64-byte line of four zero units is left alone too: states come in long runs, so most lines of a mixed block are one state)
-            const bool zeroedPiece = zeroed && (size_t)((u0 * 16u) >> 21) < zeroed->pieces && zeroed->done[(size_t)((u0 * 16u) >> 21)].load(std::memory_order_acquire)
-                                     && ((uintptr_t)d & 63u) == 0u;
+            // (in the zeroed part of the block, a 64-byte line of four zero units is left alone too: states come in long runs, so most lines of a mixed block are
+            //  one state.  zeroedEnd: the lines [32 k, 32 k + 64) with 32 k + 64 <= zeroedEnd lie in it -- the block's bytes below the extent, if its piece is complete)
+            uint64_t zeroedEnd = 0;
+            if (zeroed && ((uintptr_t)d & 63u) == 0u && zeroed->extent > u0 * 16u && piece_complete(*zeroed, (size_t)((u0 * 16u) >> kZeroPieceShift)))
+                zeroedEnd = zeroed->extent - u0 * 16u < 4096u ? zeroed->extent - u0 * 16u : 4096u;
             for (int k = 0; k < 128; ++k) {
-                if (zeroedPiece && (k & 1) == 0) { uint16_t four; memcpy(&four, codes + k, 2); if (four == 0u) { skippedHere += 64u; ++k; continue; } }
+                if ((k & 1) == 0 && 32u * (uint64_t)k + 64u <= zeroedEnd) { uint16_t four; memcpy(&four, codes + k, 2); if (four == 0u) { skippedHere += 64u; ++k; continue; } }
                 const uint32_t two = codes[k], c0 = two & 15u, c1 = two >> 4;
                 __m128i v0, v1;
                 if (c0 < 4u) v0 = _mm_set1_epi32((int)kPattern[c0]); else { v0 = _mm_loadu_si128((const __m128i*)raw); raw += 16; }
@@ -275,6 +274,27 @@ void expand(uint8_t* dst, uint64_t dstBytes, const uint8_t* stream, const HostCo
 void codec_expand_blocks(uint8_t* dst, uint64_t dstBytes, const uint8_t* stream, const HostCodecLayout& L, uint64_t b0, uint64_t b1, const ZeroedPieces* zeroed, uint64_t* skipped)
 {
     if (((uintptr_t)dst & 15u) == 0) expand<true>(dst, dstBytes, stream, L, b0, b1, zeroed, skipped); else expand<false>(dst, dstBytes, stream, L, b0, b1, zeroed, skipped);
+}
+
+ZeroPlan zero_plan(size_t cap, size_t last)
+{
+    ZeroPlan P; P.cap = cap; P.bytes = last < cap ? last : cap;
+    P.pieces = (P.bytes + ((size_t)1 << kZeroPieceShift) - 1) >> kZeroPieceShift;
+    return P;
+}
+void zero_piece_range(const ZeroPlan& P, size_t j, size_t* lo, size_t* hi)
+{
+    *lo = j << kZeroPieceShift;
+    *hi = *lo + ((size_t)1 << kZeroPieceShift) < P.bytes ? *lo + ((size_t)1 << kZeroPieceShift) : P.bytes;
+}
+uint64_t zeroed_bytes(const ZeroedPieces& z)
+{
+    uint64_t n = 0;
+    for (size_t j = 0; j < z.pieces; ++j) {
+        const uint64_t lo = (uint64_t)j << kZeroPieceShift, hi = lo + ((uint64_t)1 << kZeroPieceShift) < z.extent ? lo + ((uint64_t)1 << kZeroPieceShift) : z.extent;
+        if (hi > lo && piece_complete(z, j)) n += hi - lo;
+    }
+    return n;
 }
 
 void fill_zero_nt(uint8_t* dst, size_t lo, size_t hi)

@@ -59,12 +59,33 @@ private:
 struct HostCodecLayout { uint64_t units, blocks, offOfs, offCodes, offRaw; };
 HostCodecLayout host_codec_layout(uint64_t paddedBytes);
 
+// Zeroing ahead (omm_host.cpp: Prefill): while the device bakes, helper threads zero an idle result block of `cap` bytes in pieces of 2 MiB, up to the size of
+// the last compressed result (`last`).  The block may then hold a LARGER result (up to `cap`): the last piece ends at `bytes`, not at its 2 MiB boundary, and
+// what lies beyond `bytes` is whatever the block held before.
+constexpr unsigned kZeroPieceShift = 21;   // 2 MiB pieces
+struct ZeroPlan { size_t cap, bytes, pieces; };   // bytes: the zeroed extent, min(last, cap); pieces: ceil(bytes / 2 MiB)
+ZeroPlan zero_plan(size_t cap, size_t last);
+// bytes [*lo, *hi) of the block that piece j < P.pieces zeroes (the last one is cut at P.bytes)
+void zero_piece_range(const ZeroPlan& P, size_t j, size_t* lo, size_t* hi);
+// What the expansion may trust: piece j is complete when done[j] is set (after its range was zeroed), and a byte is known to be zero only below `extent`
+// in a complete piece.  zeroed_pieces() sets the extent to the plan's bytes; left out, it is unbounded: every complete piece was zeroed in full, or up to
+// the end of the destination it is expanded into.
+struct ZeroedPieces { const std::atomic<uint8_t>* done; size_t pieces; uint64_t extent = ~(uint64_t)0; };
+inline ZeroedPieces zeroed_pieces(const ZeroPlan& P, const std::atomic<uint8_t>* done) { return ZeroedPieces{ done, P.pieces, (uint64_t)P.bytes }; }
+inline bool piece_complete(const ZeroedPieces& z, size_t j) { return j < z.pieces && z.done[j].load(std::memory_order_acquire) != 0; }
+// bytes [lo, hi) of the block are known to be zero: all below the extent, all in one complete piece
+inline bool zeroed_range(const ZeroedPieces& z, uint64_t lo, uint64_t hi)
+{
+    return lo < hi && hi <= z.extent && (lo >> kZeroPieceShift) == ((hi - 1) >> kZeroPieceShift) && piece_complete(z, (size_t)(lo >> kZeroPieceShift));
+}
+// the bytes known to be zero (ommxBakeTimings::prefilledBytes): complete pieces, cut at the extent
+uint64_t zeroed_bytes(const ZeroedPieces& z);
+
 // Expands codec blocks [b0, b1) of `stream` (layout L) into dst[0 .. dstBytes): block b covers dst bytes [4096 b, 4096 (b + 1)); bytes beyond dstBytes are not
 // written (the device pads the array to a multiple of 256 bytes).  Write-only on dst (non-temporal stores when dst is 16-byte aligned).
-// `zeroed` (optional): the destination was filled with zeros in pieces of 2 MiB while the device was baking -- piece j (bytes [j << 21, (j + 1) << 21) of dst)
-// is complete when zeroed->done[j] is set; a codec block of 4 KiB that repeats state 0 and lies in a complete piece is not written again (a quarter of the
-// blocks of the metric configuration).  *skipped (optional) += the bytes left as they were.
-struct ZeroedPieces { const std::atomic<uint8_t>* done; size_t pieces; };
+// `zeroed` (optional): dst is the block that was zeroed ahead (ZeroedPieces); a codec block of 4 KiB that repeats state 0 (a quarter of the blocks of the
+// metric configuration), and a 64-byte line of four zero units in a mixed block, are not written again if zeroed_range() holds for all of their bytes.
+// *skipped (optional) += the bytes left as they were.
 void codec_expand_blocks(uint8_t* dst, uint64_t dstBytes, const uint8_t* stream, const HostCodecLayout& L, uint64_t b0, uint64_t b1,
                          const ZeroedPieces* zeroed = nullptr, uint64_t* skipped = nullptr);
 // zero bytes [lo, hi) of a 4 KiB-aligned block with non-temporal stores (the pre-fill itself)

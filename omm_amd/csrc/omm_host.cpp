@@ -1391,10 +1391,10 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
     // compressed result; if the block then fits this bake's result it becomes the result, and the expansion leaves zero blocks of complete pieces alone.
     // Whatever happens -- another transfer, a larger result, an error -- the block is either handed out after the threads have stopped, or goes back to the pool.
     struct Prefill {
-        std::shared_ptr<WorkerPool> pool; std::shared_ptr<HostPool> host; uint8_t* block = nullptr; size_t cap = 0, bytes = 0, pieces = 0; bool pinned = false, started = false;
+        std::shared_ptr<WorkerPool> pool; std::shared_ptr<HostPool> host; uint8_t* block = nullptr; size_t cap = 0; bool pinned = false, started = false;
+        ZeroPlan plan{ 0, 0, 0 };   // (host_expand.h: the pieces, and the extent the expansion may trust -- a larger result's bytes beyond it are stale)
         std::unique_ptr<std::atomic<uint8_t>[]> done; std::atomic<bool> cancel{ false };
         void stop() { if (started) { cancel.store(true); pool->wait(); started = false; } }   // (pieces not begun stay unmarked: the expansion writes them like any other)
-        uint64_t zeroed() const { uint64_t n = 0; for (size_t j = 0; j < pieces; ++j) if (done[j].load()) n += (j + 1 < pieces ? (size_t)2 << 20 : bytes - (j << 21)); return n; }
         ~Prefill() { stop(); if (block) host->release(block); }
     } prefill;
     struct ArrayAlloc {
@@ -1425,7 +1425,9 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
             return (uint8_t*)a.res->arrayData;
         }
     } arrayAlloc{ &baker, res, 0, false, &prefill, false };
-    StreamOut so; so.set = ses.set.get(); so.allocUser = &arrayAlloc; so.alloc = &ArrayAlloc::get;
+    StreamOut so; so.set = ses.set.get(); so.allocUser = &arrayAlloc;
+    // (a block the streamed placement writes into is no longer only zeroed: if the stream is discarded, the compressed transfer that follows must write every byte)
+    so.alloc = [](void* u, uint64_t bytes, bool* pinned) -> uint8_t* { uint8_t* p = ArrayAlloc::get(u, bytes, pinned); ((ArrayAlloc*)u)->fromPrefill = false; return p; };
     if (const uint64_t k = baker.knob(ommxBakerKnob_StreamChunks)) { so.chunksWanted = (uint32_t)k; so.forced = true; }
     // How a large arrayData reaches the caller (ommxBakerKnob_ResultTransfer).  COMPRESSED (round 5): the bake finishes on the device, the array crosses PCIe as
     // a codec stream (tail_kernels.hip: 6 % of its bytes at the metric configuration) and host threads expand it into the caller's array -- 190 - 250 GB/s with
@@ -1475,15 +1477,15 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
         const uint64_t last = baker.lastCompressedArrayBytes.load();
         if (last >= kCompressedMinBytes && (prefill.block = (uint8_t*)baker.hostPool->acquire_idle((size_t)last, &prefill.cap, &prefill.pinned)) != nullptr) {
             prefill.host = baker.hostPool; prefill.pool = baker.worker_pool(expandThreads);
-            prefill.bytes = (size_t)last < prefill.cap ? (size_t)last : prefill.cap; prefill.pieces = (prefill.bytes + ((size_t)2 << 20) - 1) >> 21;
-            prefill.done.reset(new (std::nothrow) std::atomic<uint8_t>[prefill.pieces]);
+            prefill.plan = zero_plan(prefill.cap, (size_t)last);
+            prefill.done.reset(new (std::nothrow) std::atomic<uint8_t>[prefill.plan.pieces]);
             if (prefill.done && ((uintptr_t)prefill.block & 4095u) == 0u) {
-                for (size_t j = 0; j < prefill.pieces; ++j) prefill.done[j].store(0);
+                for (size_t j = 0; j < prefill.plan.pieces; ++j) prefill.done[j].store(0);
                 if (baker.knob(ommxBakerKnob_HelperAffinity) == 0) (void)prefill.pool->bind_near(prefill.block);
                 Prefill* pf = &prefill;
-                prefill.started = prefill.pool->start((uint32_t)prefill.pieces, [pf](uint32_t j) {
+                prefill.started = prefill.pool->start((uint32_t)prefill.plan.pieces, [pf](uint32_t j) {
                     if (pf->cancel.load(std::memory_order_relaxed)) return;
-                    const size_t lo = (size_t)j << 21, hi = lo + ((size_t)2 << 20) < pf->bytes ? lo + ((size_t)2 << 20) : pf->bytes;
+                    size_t lo, hi; zero_piece_range(pf->plan, j, &lo, &hi);
                     fill_zero_nt(pf->block, lo, hi);
                     pf->done[j].store(1, std::memory_order_release);
                 });
@@ -1582,9 +1584,9 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
                 constexpr uint64_t kTaskBlocks = 512;
                 const uint64_t numTasks = (co.L.blocks + kTaskBlocks - 1) / kTaskBlocks;
                 std::atomic<uint32_t> arrived{ 0 }; std::atomic<bool> failed{ false };
-                // (the result array is the block that was zeroed ahead: blocks of zeros in its complete pieces are left alone)
+                // (the result array is the block that was zeroed ahead: blocks and lines of zeros inside its zeroed extent, in complete pieces, are left alone)
                 std::atomic<uint64_t> skippedBytes{ 0 };
-                const ZeroedPieces zeroedPieces{ prefill.done.get(), prefill.pieces };
+                const ZeroedPieces zeroedPieces = zeroed_pieces(prefill.plan, prefill.done.get());
                 const ZeroedPieces* const zeroedPtr = arrayAlloc.fromPrefill && prefill.done ? &zeroedPieces : nullptr;
                 ok = HIP_OK(hipEventSynchronize(evs[0]));
                 if (ok) arrived.store(1);
@@ -1616,7 +1618,7 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
                 });
                 ok = ok && !failed.load();
                 tm.expandThreads = pool.workers() + 1u;
-                tm.expandSkippedBytes = skippedBytes.load(); tm.prefilledBytes = zeroedPtr ? prefill.zeroed() : 0;
+                tm.expandSkippedBytes = skippedBytes.load(); tm.prefilledBytes = zeroedPtr ? zeroed_bytes(zeroedPieces) : 0;
             }
             if (!ok) (void)hipStreamSynchronize(stream);   // (nothing may still be landing in the pinned block when the session hands it back)
             for (uint32_t k = 0; k < nev; ++k) (void)hipEventDestroy(evs[k]);

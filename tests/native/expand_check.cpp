@@ -10,6 +10,23 @@
 using namespace ommx;
 static uint64_t s = 0x9E3779B97F4A7C15ull;
 static uint64_t rnd() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return s; }
+// the codec stream of src[0 .. padded) (scalar model of tail_kernels.hip: codec_code / shard_codec_write)
+static std::vector<uint8_t> encode(const std::vector<uint8_t>& src, const HostCodecLayout& L)
+{
+    std::vector<uint8_t> stream(L.offRaw + 16 * L.units + 64, 0xEE);
+    uint32_t* ofs = (uint32_t*)(stream.data() + L.offOfs); uint32_t nraw = 0;
+    for (uint64_t u = 0; u < L.units; ++u) {
+        if (u % 256 == 0) ofs[u / 256] = nraw;
+        uint32_t w[4]; memcpy(w, &src[u * 16], 16);
+        const bool same = w[0] == w[1] && w[0] == w[2] && w[0] == w[3];
+        const uint32_t code = !same ? 4u : (w[0] == 0u ? 0u : (w[0] == 0x55555555u ? 1u : (w[0] == 0xAAAAAAAAu ? 2u : (w[0] == 0xFFFFFFFFu ? 3u : 4u))));
+        uint8_t& c = stream[L.offCodes + u / 2];
+        c = (uint8_t)((u & 1) ? ((c & 0x0F) | (code << 4)) : code);
+        if (code == 4u) { memcpy(&stream[L.offRaw + 16ull * nraw], w, 16); ++nraw; }
+    }
+    ofs[L.blocks] = nraw;
+    return stream;
+}
 int main()
 {
     int cases = 0;
@@ -64,40 +81,99 @@ int main()
             o += len;
         }
         const HostCodecLayout L = host_codec_layout(padded);
-        std::vector<uint8_t> stream(L.offRaw + 16 * L.units + 64, 0xEE);
-        uint32_t* ofs = (uint32_t*)(stream.data() + L.offOfs); uint32_t nraw = 0;
-        for (uint64_t u = 0; u < L.units; ++u) {
-            if (u % 256 == 0) ofs[u / 256] = nraw;
-            uint32_t w[4]; memcpy(w, &src[u * 16], 16);
-            const bool same = w[0] == w[1] && w[0] == w[2] && w[0] == w[3];
-            const uint32_t code = !same ? 4u : (w[0] == 0u ? 0u : (w[0] == 0x55555555u ? 1u : (w[0] == 0xAAAAAAAAu ? 2u : (w[0] == 0xFFFFFFFFu ? 3u : 4u))));
-            uint8_t& c = stream[L.offCodes + u / 2];
-            c = (uint8_t)((u & 1) ? ((c & 0x0F) | (code << 4)) : code);
-            if (code == 4u) { memcpy(&stream[L.offRaw + 16ull * nraw], w, 16); ++nraw; }
-        }
-        ofs[L.blocks] = nraw;
+        const std::vector<uint8_t> stream = encode(src, L);
         std::vector<uint8_t> out(bytes + 8192, 0x77);   // stale content everywhere
         uint8_t* base = out.data(); while (((uintptr_t)base & 4095u) != 0u) ++base;
-        const size_t pieces = (bytes + (2u << 20) - 1) >> 21;
+        const ZeroPlan plan = zero_plan(bytes, bytes);
+        const size_t pieces = plan.pieces;
         std::unique_ptr<std::atomic<uint8_t>[]> done(new std::atomic<uint8_t>[pieces]);
         for (size_t j = 0; j < pieces; ++j) done[j].store(0);
         WorkerPool pool(workers);
         std::atomic<bool> cancel{ false };
         const bool started = pool.start((uint32_t)pieces, [&](uint32_t j) {
             if (cancel.load() || (int)j == cancelAt) return;   // (a cancelled / skipped piece keeps its stale bytes and stays unmarked)
-            const size_t lo = (size_t)j << 21, hi = lo + (2u << 20) < bytes ? lo + (2u << 20) : bytes;
+            size_t lo, hi; zero_piece_range(plan, j, &lo, &hi);
             fill_zero_nt(base, lo, hi);
             done[j].store(1, std::memory_order_release);
         });
         if (!started) { printf("START FAILED workers=%u\n", workers); return 1; }
         pool.wait();
-        const ZeroedPieces z{ done.get(), pieces };
+        const ZeroedPieces z = zeroed_pieces(plan, done.get());
         std::atomic<uint64_t> skipped{ 0 };
         const uint32_t tasks = (uint32_t)((L.blocks + 63) / 64);
         pool.run(tasks, [&](uint32_t t) { const uint64_t b0 = (uint64_t)t * 64, b1 = b0 + 64 < L.blocks ? b0 + 64 : L.blocks; uint64_t sk = 0; codec_expand_blocks(base, bytes, stream.data(), L, b0, b1, &z, &sk); skipped += sk; });
         if (memcmp(base, src.data(), bytes) != 0) { printf("ZERO-AHEAD MISMATCH variant=%d workers=%u cancelAt=%d\n", variant, workers, cancelAt); return 1; }
         if (skipped.load() == 0) { printf("ZERO-AHEAD skipped nothing variant=%d\n", variant); return 1; }
         ++zeroCases;
+    }
+    // ---- zeroing ahead of a block that then holds ANOTHER size of result (omm_host.cpp: Prefill, ArrayAlloc): the pool block has `cap` bytes, the helper
+    //      threads zero it up to `last` (the previous compressed result) by the plan, and the result -- smaller, equal, or larger up to cap -- is expanded over
+    //      it.  The block holds stale non-zero bytes of an earlier bake everywhere; the expansion may leave alone only what zeroed_range() vouches for ----
+    int planCases = 0; uint64_t planSkipped = 0;
+    {
+        const size_t M = (size_t)1 << 20, K = 4096;
+        struct Sweep { size_t cap, last, result; };
+        const Sweep sweep[] = {
+            { 12 * M, 9 * M + 3 * K, 9 * M + 3 * K },          // result == last (last mid-piece)
+            { 12 * M, 9 * M + 3 * K, 5 * M + 48 },             // result < last
+            { 12 * M, 9 * M + 3 * K, 9 * M + M / 2 },          // last < result < roundup_2MiB(last)
+            { 12 * M, 9 * M + 3 * K, 10 * M },                 // result == roundup_2MiB(last)
+            { 12 * M, 9 * M + 3 * K, 9 * M + 3 * K + 16 },     // one unit more than last
+            { 12 * M, 9 * M + 3 * K, 12 * M },                 // result == cap
+            { 12 * M, 8 * M, 8 * M },                          // last a multiple of 2 MiB
+            { 12 * M, 8 * M, 8 * M + K + 32 },
+            { 12 * M, 8 * M, 11 * M + 7 },
+            { 8 * M, 6 * M + 5 * K + 7, 6 * M + 5 * K + 7 },   // last not a multiple of 16
+            { 8 * M, 6 * M + 5 * K + 7, 6 * M + 5 * K + 64 },
+            { 8 * M, 6 * M + 5 * K + 7, 7 * M + 3 },
+            { 4 * M, 6 * M, 4 * M },                           // last beyond the block (clamped to cap)
+            { 2 * M, M + 48, 2 * M },                          // one partial piece
+        };
+        static const uint8_t pat[4] = { 0x00, 0x55, 0xAA, 0xFF };
+        for (const Sweep& c : sweep) for (unsigned workers : { 0u, 3u, 7u }) for (int cancelCase = 0; cancelCase < 3; ++cancelCase) {
+            const size_t bytes = c.result, padded = (bytes + 255) & ~(size_t)255;
+            std::vector<uint8_t> src(padded, 0);
+            for (size_t o = 0; o < padded; ) {   // runs of whole zero blocks, zero lines and other states, noise in between
+                size_t len = 16 * (1 + rnd() % (rnd() % 2 ? 600 : 8));
+                if (o + len > padded) len = padded - o;
+                if (rnd() % 8 == 0) for (size_t k = 0; k < len; ++k) src[o + k] = (uint8_t)rnd(); else memset(&src[o], pat[rnd() % 2 ? 0 : rnd() % 4], len);
+                o += len;
+            }
+            const HostCodecLayout L = host_codec_layout(padded);
+            const std::vector<uint8_t> stream = encode(src, L);
+            std::vector<uint8_t> out(c.cap + 8192);
+            uint8_t* base = out.data(); while (((uintptr_t)base & 4095u) != 0u) ++base;
+            for (size_t k = 0; k < c.cap; ++k) base[k] = (uint8_t)(rnd() | 1u);   // stale, never zero
+            const ZeroPlan plan = zero_plan(c.cap, c.last);
+            const int cancelAt = cancelCase == 0 ? -1 : (cancelCase == 1 ? 0 : (int)plan.pieces - 1);
+            std::unique_ptr<std::atomic<uint8_t>[]> done(new std::atomic<uint8_t>[plan.pieces]);
+            for (size_t j = 0; j < plan.pieces; ++j) done[j].store(0);
+            WorkerPool pool(workers);
+            const bool started = pool.start((uint32_t)plan.pieces, [&](uint32_t j) {
+                if ((int)j == cancelAt) return;   // (cancelled: keeps its stale bytes, stays unmarked)
+                size_t lo, hi; zero_piece_range(plan, j, &lo, &hi);
+                if (lo >= hi || hi > c.cap) { printf("PLAN piece %u [%zu, %zu) outside the block of %zu\n", j, lo, hi, c.cap); exit(1); }
+                fill_zero_nt(base, lo, hi);
+                done[j].store(1, std::memory_order_release);
+            });
+            if (started != (workers > 0)) { printf("START %d workers=%u\n", (int)started, workers); return 1; }
+            pool.wait();
+            const ZeroedPieces z = zeroed_pieces(plan, done.get());
+            const uint64_t trusted = zeroed_bytes(z);
+            std::atomic<uint64_t> skipped{ 0 };
+            const uint32_t tasks = (uint32_t)((L.blocks + 63) / 64);
+            pool.run(tasks, [&](uint32_t t) { const uint64_t b0 = (uint64_t)t * 64, b1 = b0 + 64 < L.blocks ? b0 + 64 : L.blocks; uint64_t sk = 0; codec_expand_blocks(base, bytes, stream.data(), L, b0, b1, &z, &sk); skipped += sk; });
+            if (memcmp(base, src.data(), bytes) != 0) {
+                size_t bad = 0, first = bytes; for (size_t k = 0; k < bytes; ++k) if (base[k] != src[k]) { ++bad; if (first == bytes) first = k; }
+                printf("ZERO-PLAN MISMATCH cap=%zu last=%zu result=%zu workers=%u cancel=%d: %zu wrong bytes, first at %zu\n", c.cap, c.last, bytes, workers, cancelAt, bad, first);
+                return 1;
+            }
+            if (skipped.load() > trusted) { printf("ZERO-PLAN skipped %llu > zeroed %llu cap=%zu last=%zu result=%zu\n", (unsigned long long)skipped.load(), (unsigned long long)trusted, c.cap, c.last, bytes); return 1; }
+            if (!started && (trusted != 0 || skipped.load() != 0)) { printf("ZERO-PLAN nothing was zeroed but %llu trusted\n", (unsigned long long)trusted); return 1; }
+            planSkipped += skipped.load();
+            ++planCases;
+        }
+        if (planSkipped == 0) { printf("ZERO-PLAN skipped nothing\n"); return 1; }
     }
     // ---- codec_scatter_omms: blocks of a result from the codec streams of their owners' contributions (multi-device ommCpuBake) ----
     int scatterCases = 0;
@@ -159,6 +235,6 @@ int main()
         for (int k = 0; k < 64; ++k) if (got[total + k] != 0xCD) { printf("SCATTER OVERRUN world=%u\n", world); return 1; }
         ++scatterCases;
     }
-    printf("ok %d scatter %d zero-ahead %d effective_cpus %u\n", cases, scatterCases, zeroCases, effective_cpus());
+    printf("ok %d scatter %d zero-ahead %d zero-plan %d effective_cpus %u\n", cases, scatterCases, zeroCases, planCases, effective_cpus());
     return 0;
 }
