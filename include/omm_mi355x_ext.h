@@ -204,4 +204,35 @@ typedef struct ommxCollectives
 } ommxCollectives;
 OMM_MI355X_API ommResult ommxCommFromCollectives(const ommxCollectives* collectives, uint32_t rank, uint32_t worldSize, ommxRcclComm* outComm);
 
+/* ---- using a baked micromap on the GPU (include/omm_mi355x_lookup.h is the per-hit device function behind these) ----
+ * A hit is a triangle of the baked mesh and the DXR / Vulkan barycentrics of the hit point: (1-u-v) * V0 + u * V1 + v * V2, V0..V2 in
+ * index-buffer order.  Every call below takes `count` hits and writes one byte per hit; count == 0 is SUCCESS without a launch.
+ *
+ * ommxLookupOpacity      out[i] = ommx_opacity_state(result, hit i): 0..3 (ommOpacityState) or OMMX_OPACITY_INVALID (0xFF).
+ *                        `result` is a HOST struct whose arrays (arrayData, descArray, indexBuffer) are DEVICE memory: the desc of
+ *                        ommxGetDeviceBakeResultDesc, or one the caller filled with device copies of an ommCpuBake result.  The struct is
+ *                        read during the call; the arrays, `hits` and `outStates` (device memory) are used by the kernel, which is enqueued
+ *                        on `hipStream` (a hipStream_t; null = the null stream) and runs asynchronously.  Flags: Force2State only.
+ * ommxLookupOpacityHost  the same answer from the same header code on the CPU: host pointers, synchronous.
+ * ommxResolveHits        the any-hit answer.  out[i]: bit 0 = opaque, bits 1-2 = OMM state, bit 3 = the texture was sampled; 0xFF = a hit the
+ *                        result cannot answer.  A hit whose OMM state is Transparent or Opaque is answered from the OMM alone; any other hit
+ *                        samples mip 0 of the texture at the hit's interpolated texture coordinate with the desc's runtimeSamplerDesc and
+ *                        maps alpha > alphaCutoff to alphaCutoffGreater, otherwise to alphaCutoffLessEqual (an Unknown* answer counts as its
+ *                        opaque / transparent half).  Flag IgnoreMicromap samples the texture for every hit (the plain alpha test); Force2State
+ *                        applies to the OMM state, so an unknown state then becomes known and the texture is not sampled.
+ *                        `deviceDesc` is the device-resident input desc the result was baked from (as given to ommxBakeDevice: a texture of
+ *                        this baker, sampler, cut-off, device texcoords and indices); it is refused where ommxBakeDevice would refuse it, with
+ *                        the same result code.  `result`, `hits`, `out` and the stream as for ommxLookupOpacity.
+ * None of the three allocates memory or synchronises a stream. */
+typedef struct ommxHit { uint32_t primitiveIndex; float u, v; } ommxHit;
+typedef enum ommxLookupFlags {
+    ommxLookupFlags_None           = 0,
+    ommxLookupFlags_Force2State    = 1,
+    ommxLookupFlags_IgnoreMicromap = 2
+} ommxLookupFlags;
+OMM_MI355X_API ommResult ommxLookupOpacity(const ommCpuBakeResultDesc* result, const ommxHit* hits, uint32_t count, uint8_t* outStates, uint32_t flags, void* hipStream);
+OMM_MI355X_API ommResult ommxLookupOpacityHost(const ommCpuBakeResultDesc* result, const ommxHit* hits, uint32_t count, uint8_t* outStates, uint32_t flags);
+OMM_MI355X_API ommResult ommxResolveHits(ommBaker baker, const ommCpuBakeInputDesc* deviceDesc, const ommCpuBakeResultDesc* result,
+                                         const ommxHit* hits, uint32_t count, uint8_t* out, uint32_t flags, void* hipStream);
+
 #endif

@@ -1,0 +1,121 @@
+/*
+ * omm_mi355x_lookup.h -- what a baked opacity micromap says at a ray hit (header-only).
+ *
+ * GPUs without a ray-tracing unit that reads the OMM array (the MI355X among them) consult a micromap from the any-hit or filter
+ * function of their own ray tracer.  This header is that consumer: include it in HIP device code (hipcc) or in plain C++ on the host.
+ *
+ *   ommx_micro_index(u, v, level)          hit barycentrics -> micro-triangle index on the bird curve, 0 <= index < 4^level
+ *   ommx_opacity_state(result, prim, u, v) the 4-state value (ommOpacityState, 0..3) the result stores there, or OMMX_OPACITY_INVALID
+ *   ommx_force_2state(state)               the "force OMM 2-state" ray flag: UnknownTransparent -> Transparent, UnknownOpaque -> Opaque
+ *
+ * Barycentric convention (DXR / Vulkan): the hit point is (1-u-v) * V0 + u * V1 + v * V2, where V0..V2 are the triangle's vertices in
+ * index-buffer order -- the (u, v) a DXR any-hit shader receives as attribs.barycentrics and a Vulkan one as gl_HitAttributeEXT.
+ *
+ * `result` is an ommCpuBakeResultDesc whose arrays (arrayData, descArray, indexBuffer) are readable where the function runs: host
+ * memory on the host, device memory in a kernel.  Its indexCount is one entry per triangle.  Every read stays inside the arrays the
+ * desc describes; what does not fit returns OMMX_OPACITY_INVALID instead (see ommx_opacity_state).
+ *
+ * Exact arithmetic: the mapping below decides on which side of a micro-triangle edge a point lies without rounding error.  It needs
+ * IEEE fp32 (no -ffast-math / -ffinite-math-only in the including translation unit).
+ */
+#ifndef OMM_MI355X_LOOKUP_H
+#define OMM_MI355X_LOOKUP_H
+#include "omm_mi355x.h"
+
+#ifdef __HIPCC__
+#define OMMX_LOOKUP_FN __host__ __device__ __forceinline__
+#else
+#define OMMX_LOOKUP_FN static inline
+#endif
+
+/* returned for a primitive or index entry that the result cannot answer (see ommx_opacity_state) */
+#define OMMX_OPACITY_INVALID 0xFFu
+#define OMMX_LOOKUP_MAX_LEVEL 12u
+
+/* The bird curve's forward decode (omm_amd/csrc/classify_device.h, micro_triangle) turns index digit i (bits 2i, 2i+1; most significant
+ * digit first) into bit i of the discrete barycentrics (iu, iv, iw), with two running parities X, Y of the higher digits:
+ *     b0 = digit & 1, b1 = digit >> 1,  X ^= b0,  Y ^= b0 & ~b1,  t = Y ^ b1
+ *     iu_i = (X & ~t) | (b0 & ~t) | (~b0 & ~X & t),  iv_i = Y ^ b0,  iw_i = (~X & ~t) | (b0 & ~t) | (~b0 & X & t)
+ * For fixed (X, Y) the four digits give four different (iu_i, iv_i, iw_i), so the digit is a function of (X, Y, iu_i, iv_i, iw_i): two
+ * bits per 5-bit key, key = X | Y << 1 | iu_i << 2 | iv_i << 3 | iw_i << 4, packed into one 64-bit constant (16 keys occur; the others
+ * read 0).  tests/test_lookup.py rebuilds this constant from the forward decode and checks the inverse on every index of every level. */
+#define OMMX_BIRD_DIGIT_TABLE 0x5020f008800f0205ull
+
+/* Micro-triangle index of the point (u, v) at `level` (0..12; larger levels are treated as 12).
+ *  - a point strictly inside a micro-triangle returns that micro-triangle;
+ *  - a point on a shared edge or vertex returns one of the micro-triangles whose closure contains it;
+ *  - NaN reads as 0 and u, v are clamped to [0, 1]; a point beyond the edge u + v = 1 is moved onto the row of micro-triangles along that
+ *    edge (its discrete barycentric iu is lowered first, then iv).  The result is always a valid index below 4^level. */
+OMMX_LOOKUP_FN uint32_t ommx_micro_index(float u, float v, uint32_t level)
+{
+    if (level == 0u) return 0u;
+    if (level > OMMX_LOOKUP_MAX_LEVEL) level = OMMX_LOOKUP_MAX_LEVEL;
+    const uint32_t n = 1u << level;
+    u = u > 0.f ? (u < 1.f ? u : 1.f) : 0.f;   /* (NaN fails the first comparison) */
+    v = v > 0.f ? (v < 1.f ? v : 1.f) : 0.f;
+    const float fu = u * (float)n, fv = v * (float)n;   /* exact: scaling by a power of two */
+    uint32_t iu = (uint32_t)fu, iv = (uint32_t)fv;      /* floor (both are >= 0) */
+    iu = iu < n - 1u ? iu : n - 1u;
+    iv = iv < n - 1u ? iv : n - 1u;
+    bool upright = true;
+    if (iu + iv >= n - 1u) {
+        /* on or beyond the edge u + v = 1: the upright cell of that row (a point on the edge lies in its closure) */
+        const uint32_t over = iu + iv - (n - 1u);
+        const uint32_t du = over < iu ? over : iu;
+        iu -= du; iv -= over - du;
+    } else {
+        /* cell (iu, iv) of the grid: the upright micro-triangle is its half ru + rv < 1, the inverted one the other half.  ru, rv are
+           exact; their sum is decided exactly (two-sum error term) so that a point close to the diagonal is not rounded onto it */
+        const float ru = fu - (float)iu, rv = fv - (float)iv;
+        const float s = ru + rv, bv = s - ru, err = (ru - (s - bv)) + (rv - bv);
+        upright = s < 1.f || (s == 1.f && err < 0.f);
+    }
+    /* discrete barycentrics as the forward decode produces them: iu + iv + iw = n - 1 (upright) or n - 2 (inverted, low corner (iu, iv)) */
+    const uint32_t iw = (upright ? n - 1u : n - 2u) - iu - iv;
+    uint32_t index = 0u, x = 0u, y = 0u;
+    for (uint32_t i = level; i-- > 0u;) {
+        const uint32_t key = x | (y << 1) | (((iu >> i) & 1u) << 2) | (((iv >> i) & 1u) << 3) | (((iw >> i) & 1u) << 4);
+        const uint32_t digit = (uint32_t)(OMMX_BIRD_DIGIT_TABLE >> (2u * key)) & 3u;
+        index = (index << 2) | digit;
+        x ^= digit & 1u;
+        y ^= digit == 1u ? 1u : 0u;
+    }
+    return index;
+}
+
+/* The state the result stores for triangle `prim` at the hit (u, v): 0..3 (ommOpacityState) or OMMX_OPACITY_INVALID.
+ *  - entry e = result->indexBuffer[prim], signed 8-, 16- or 32-bit after result->indexFormat;
+ *  - e in -1..-4 is a special index: state -(e + 1);
+ *  - e >= 0 selects descArray[e]: state = bit i (OC1_2_State) or bits 2i..2i+1 (OC1_4_State) of the block at arrayData + offset,
+ *    little-endian within bytes, i = ommx_micro_index(u, v, subdivisionLevel).
+ * OMMX_OPACITY_INVALID, before any read out of range: prim >= indexCount, an unknown indexFormat, e < -4, e >= descArrayCount, a level
+ * above 12, a format other than OC1_2_State / OC1_4_State, or a block that does not fit inside arrayDataSize. */
+OMMX_LOOKUP_FN uint32_t ommx_opacity_state(const ommCpuBakeResultDesc* r, uint32_t prim, float u, float v)
+{
+    if (prim >= r->indexCount) return OMMX_OPACITY_INVALID;
+    int32_t e;
+    switch (r->indexFormat) {
+    case ommIndexFormat_UINT_8:  e = ((const int8_t*)r->indexBuffer)[prim]; break;
+    case ommIndexFormat_UINT_16: e = ((const int16_t*)r->indexBuffer)[prim]; break;
+    case ommIndexFormat_UINT_32: e = ((const int32_t*)r->indexBuffer)[prim]; break;
+    default: return OMMX_OPACITY_INVALID;
+    }
+    if (e < 0) return e >= -4 ? (uint32_t)(-(e + 1)) : OMMX_OPACITY_INVALID;
+    if ((uint32_t)e >= r->descArrayCount) return OMMX_OPACITY_INVALID;
+    const ommCpuOpacityMicromapDesc d = r->descArray[e];
+    const uint32_t level = d.subdivisionLevel, bits = d.format;   /* ommFormat value == bits per micro-triangle */
+    if (level > OMMX_LOOKUP_MAX_LEVEL || (bits != 1u && bits != 2u)) return OMMX_OPACITY_INVALID;
+    const uint64_t blockBytes = (((uint64_t)bits << (2u * level)) + 7u) >> 3;
+    if ((uint64_t)d.offset + blockBytes > (uint64_t)r->arrayDataSize) return OMMX_OPACITY_INVALID;
+    const uint32_t bit = ommx_micro_index(u, v, level) * bits;
+    const uint32_t byte = ((const uint8_t*)r->arrayData)[(uint64_t)d.offset + (bit >> 3)];
+    return (byte >> (bit & 7u)) & ((1u << bits) - 1u);
+}
+
+/* ray flag "force OMM 2-state": UnknownTransparent -> Transparent, UnknownOpaque -> Opaque; other values are returned unchanged */
+OMMX_LOOKUP_FN uint32_t ommx_force_2state(uint32_t state)
+{
+    return (state == 2u || state == 3u) ? state - 2u : state;
+}
+
+#endif

@@ -1,0 +1,146 @@
+// lookup_kernels.hip -- using a baked micromap: the OMM state of a batch of ray hits (lookup_opacity) and the any-hit answer that samples the
+// alpha texture only where the OMM leaves the hit unknown (resolve_hits).  The per-hit decode is include/omm_mi355x_lookup.h, the same code the
+// host entry point ommxLookupOpacityHost runs; texel addressing and the bilinear filter are the classifier's own (classify_device.h), so a
+// resolved hit is sampled the way the bake classified its micro-triangle.
+#include <hip/hip_runtime.h>
+#include "lookup_kernels.h"
+#include "classify_device.h"
+#include "../../include/omm_mi355x_lookup.h"
+
+namespace ommx {
+
+constexpr uint32_t kLookupBlock = 256;
+constexpr uint32_t kLookupMaxBlocks = 4096;   // 256 CUs x 16 blocks of 4 waves: more than can be resident; the grid strides over the rest
+
+// The desc's fields as separate kernel arguments would be the same scalar loads; a local copy keeps the decode's pointer argument off the stack.
+__device__ __forceinline__ uint32_t hit_state(const ommCpuBakeResultDesc& r, const ommxHit& h, bool force2)
+{
+    const ommCpuBakeResultDesc rl = r;
+    const uint32_t s = ommx_opacity_state(&rl, h.primitiveIndex, h.u, h.v);
+    return force2 ? ommx_force_2state(s) : s;
+}
+
+// One hit per lane: index entry -> descriptor -> state byte, three dependent loads.  No LDS, few registers, so that many waves keep loads in flight.
+__global__ __launch_bounds__(kLookupBlock) void lookup_opacity(ommCpuBakeResultDesc r, const ommxHit* __restrict__ hits, uint32_t count,
+                                                               uint8_t* __restrict__ out, uint32_t force2)
+{
+    for (uint32_t i = blockIdx.x * kLookupBlock + threadIdx.x; i < count; i += gridDim.x * kLookupBlock) {
+        const ommxHit h = hits[i];
+        out[i] = (uint8_t)hit_state(r, h, force2 != 0);
+    }
+}
+
+// _Float16 -> float is exact (denormals included): the value glm::unpackHalf2x16 gives the bake's setup
+__device__ __forceinline__ float half_bits(uint32_t h)
+{
+    const uint16_t b = (uint16_t)h;
+    _Float16 f;
+    __builtin_memcpy(&f, &b, 2);
+    return (float)f;
+}
+
+// texture coordinate of vertex `vi`, read as the bake's setup reads it (setup_fetch)
+__device__ __forceinline__ V2 fetch_tex_coord(const ResolveParams& R, uint32_t vi)
+{
+    const uint8_t* base = (const uint8_t*)R.texCoords + (size_t)R.texCoordStride * vi;
+    if (R.texCoordFormat == ommTexCoordFormat_UV32_FLOAT) {
+        if (((uintptr_t)base & 3u) == 0) return mk2(((const float*)base)[0], ((const float*)base)[1]);
+        uint32_t a = 0, b = 0;
+        for (int q = 0; q < 4; ++q) { a |= (uint32_t)base[q] << (8 * q); b |= (uint32_t)base[4 + q] << (8 * q); }
+        return mk2(__uint_as_float(a), __uint_as_float(b));
+    }
+    uint32_t v = 0;
+    for (int q = 0; q < 4; ++q) v |= (uint32_t)base[q] << (8 * q);
+    if (R.texCoordFormat == ommTexCoordFormat_UV16_UNORM)
+        return mk2((float)(v & 0xffffu) * 1.5259021896696421759314870504694e-5f, (float)(v >> 16) * 1.5259021896696421759314870504694e-5f);
+    return mk2(half_bits(v & 0xffffu), half_bits(v >> 16));
+}
+
+// alpha of mip 0 at texture coordinate p with the runtime sampler: Linear = the classifier's bilinear(), Nearest = the texel under p
+template <bool FP32>
+__device__ __forceinline__ float sample_alpha(const ClassifyParams& P, V2 p)
+{
+    const DevMip& m = P.mips[0];
+    TexWindow W; W.tex = nullptr; W.sat = nullptr; W.base = nullptr; W.sx = 0; W.sy = 0; W.w = 0; W.h = 0;   // no LDS window: every fetch reads HBM
+    if (P.filterLinear) return bilinear<FP32, ModeDynamic>(P, m, p, W);
+    const int x = tex_coord(P.addrMode, P.pow2Dispatch, cvt_trunc_x86(__builtin_floorf(p.x * m.fw)), m.w, m.log2w);
+    const int y = tex_coord(P.addrMode, P.pow2Dispatch, cvt_trunc_x86(__builtin_floorf(p.y * m.fh)), m.h, m.log2h);
+    return load_texel_border<FP32>(m, x, y, P.borderAlpha, W);
+}
+
+// out: bit 0 = opaque, bits 1-2 = OMM state, bit 3 = texture sampled; 0xFF = invalid hit
+template <bool FP32>
+__global__ __launch_bounds__(kLookupBlock) void resolve_hits(ResolveParams R, ommCpuBakeResultDesc r, const ommxHit* __restrict__ hits, uint32_t count,
+                                                             uint8_t* __restrict__ out, uint32_t flags)
+{
+    for (uint32_t i = blockIdx.x * kLookupBlock + threadIdx.x; i < count; i += gridDim.x * kLookupBlock) {
+        const ommxHit h = hits[i];
+        const uint32_t s = hit_state(r, h, (flags & ommxLookupFlags_Force2State) != 0);
+        uint32_t o;
+        if (s == OMMX_OPACITY_INVALID) o = 0xFFu;
+        else if (s < 2u && !(flags & ommxLookupFlags_IgnoreMicromap)) o = s | (s << 1);   // known: the OMM answers, the texture is not touched
+        else if (h.primitiveIndex >= R.numTris) o = 0xFFu;
+        else {
+            const size_t base = 3ull * h.primitiveIndex;
+            uint32_t vi[3];
+            #pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (R.indexFormat == ommIndexFormat_UINT_8) vi[k] = ((const uint8_t*)R.indices)[base + k];
+                else if (R.indexFormat == ommIndexFormat_UINT_16) vi[k] = ((const uint16_t*)R.indices)[base + k];
+                else vi[k] = ((const uint32_t*)R.indices)[base + k];
+            }
+            const V2 t0 = fetch_tex_coord(R, vi[0]), t1 = fetch_tex_coord(R, vi[1]), t2 = fetch_tex_coord(R, vi[2]);
+            const float tri[6] = { t0.x, t0.y, t1.x, t1.y, t2.x, t2.y };
+            const float alpha = sample_alpha<FP32>(R.tex, bary_point(tri, h.u, h.v));   // weights (1-u-v, u, v)
+            const uint32_t st = (uint32_t)(R.tex.cutoff < alpha ? R.tex.stateGT : R.tex.stateLE);
+            o = (st & 1u) | (s << 1) | 8u;   // an Unknown* answer counts as its opaque (3) / transparent (2) half
+        }
+        out[i] = (uint8_t)o;
+    }
+}
+
+static uint32_t lookup_grid(uint32_t count)
+{
+    const uint32_t blocks = (count + kLookupBlock - 1u) / kLookupBlock;
+    return blocks < kLookupMaxBlocks ? blocks : kLookupMaxBlocks;
+}
+
+hipError_t launch_lookup_opacity(const ommCpuBakeResultDesc& result, const ommxHit* hits, uint32_t count, uint8_t* out, uint32_t flags, hipStream_t stream)
+{
+    lookup_opacity<<<lookup_grid(count), kLookupBlock, 0, stream>>>(result, hits, count, out, flags & ommxLookupFlags_Force2State);
+    return hipGetLastError();
+}
+
+hipError_t launch_resolve_hits(const ResolveParams& rp, const ommCpuBakeResultDesc& result, const ommxHit* hits, uint32_t count, uint8_t* out,
+                               uint32_t flags, hipStream_t stream)
+{
+    if (rp.tex.texIsFp32) resolve_hits<true><<<lookup_grid(count), kLookupBlock, 0, stream>>>(rp, result, hits, count, out, flags);
+    else resolve_hits<false><<<lookup_grid(count), kLookupBlock, 0, stream>>>(rp, result, hits, count, out, flags);
+    return hipGetLastError();
+}
+
+} // namespace ommx
+
+using namespace ommx;
+
+OMM_MI355X_API ommResult ommxLookupOpacity(const ommCpuBakeResultDesc* result, const ommxHit* hits, uint32_t count, uint8_t* outStates, uint32_t flags,
+                                           void* hipStream)
+{
+    if (result == nullptr || (flags & ~(uint32_t)ommxLookupFlags_Force2State) != 0) return ommResult_INVALID_ARGUMENT;
+    if (count == 0) return ommResult_SUCCESS;
+    if (hits == nullptr || outStates == nullptr) return ommResult_INVALID_ARGUMENT;
+    return launch_lookup_opacity(*result, hits, count, outStates, flags, (hipStream_t)hipStream) == hipSuccess ? ommResult_SUCCESS : ommResult_FAILURE;
+}
+
+OMM_MI355X_API ommResult ommxLookupOpacityHost(const ommCpuBakeResultDesc* result, const ommxHit* hits, uint32_t count, uint8_t* outStates, uint32_t flags)
+{
+    if (result == nullptr || (flags & ~(uint32_t)ommxLookupFlags_Force2State) != 0) return ommResult_INVALID_ARGUMENT;
+    if (count == 0) return ommResult_SUCCESS;
+    if (hits == nullptr || outStates == nullptr) return ommResult_INVALID_ARGUMENT;
+    const bool force2 = (flags & ommxLookupFlags_Force2State) != 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        const uint32_t s = ommx_opacity_state(result, hits[i].primitiveIndex, hits[i].u, hits[i].v);
+        outStates[i] = (uint8_t)(force2 ? ommx_force_2state(s) : s);
+    }
+    return ommResult_SUCCESS;
+}

@@ -9,6 +9,7 @@
 #include "bake_kernels.h"
 #include "host_tail.h"
 #include "host_expand.h"
+#include "lookup_kernels.h"
 
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
@@ -397,6 +398,7 @@ struct Texture {
     ommCpuTextureFormat format = ommCpuTextureFormat_MAX_NUM; ommCpuTextureFlags flags = ommCpuTextureFlags_None; float alphaCutoff = -1.f;
     std::vector<TexMip> mips;
     int device = -1;   // the HIP device the texels live on (the baker's)
+    const Baker* owner = nullptr;   // the baker that created it (ommxResolveHits samples only textures of its own baker)
     // multi-device ommCpuBake (ommxBakerKnob_Devices): copies of the texels and summed-area tables on the other devices, made by the first bake that needs them
     std::mutex replicaMu; std::vector<std::unique_ptr<Texture>> replicas;
     ~Texture() { for (auto& m : mips) { if (m.texels) (void)hipFree(m.texels); if (m.sat) (void)hipFree(m.sat); } }
@@ -1711,7 +1713,7 @@ ommResult create_texture_impl(Baker* b, const ommCpuTextureDesc* desc, ommCpuTex
     if (desc->mipCount > (uint32_t)kMaxMips) return L.invalid("[Invalid Arg] - more than 17 mips");
     Texture* t = b->mem.make<Texture>();
     if (!t) return ommResult_FAILURE;
-    t->mem = b->mem; t->log = &b->log; t->format = desc->format; t->flags = desc->flags; t->alphaCutoff = desc->alphaCutoff; t->device = b->bind_device();
+    t->mem = b->mem; t->log = &b->log; t->format = desc->format; t->flags = desc->flags; t->alphaCutoff = desc->alphaCutoff; t->device = b->bind_device(); t->owner = b;
     const bool linear = ((uint32_t)desc->flags & (uint32_t)ommCpuTextureFlags_DisableZOrder) != 0;
     const size_t px = desc->format == ommCpuTextureFormat_FP32 ? 4 : 1;
     const bool enableSAT = desc->alphaCutoff >= 0; // texture_impl.cpp:91
@@ -2771,6 +2773,53 @@ OMM_MI355X_API ommResult ommxDestroyDeviceBakeResult(ommxDeviceBakeResult result
     DeviceBakeResult* r = (DeviceBakeResult*)result;
     const Allocator mem = r->mem;
     mem.destroy(r);
+    return ommResult_SUCCESS;
+}
+
+// Any-hit resolution of hits against a device-resident result (include/omm_mi355x_ext.h; kernels in lookup_kernels.hip).  The desc is checked as
+// ommxBakeDevice checks it, so a desc that could not have produced the result is refused with the same code.
+OMM_MI355X_API ommResult ommxResolveHits(ommBaker baker, const ommCpuBakeInputDesc* desc, const ommCpuBakeResultDesc* result,
+                                         const ommxHit* hits, uint32_t count, uint8_t* out, uint32_t flags, void* hipStream)
+{
+    if (baker == 0) return ommResult_INVALID_ARGUMENT;
+    Baker* b = untag<Baker>(baker);
+    if (desc == 0) return b->log.invalid("input desc was not set");
+    if (tag_of(baker) != kCpuBaker) return b->log.invalid("Baker was not created as the right type");
+    if (desc->texture == 0) return b->log.invalid("[Invalid Argument] - ommCpuBakeInputDesc has no texture set");
+    if (tag_of(desc->texture) == kTexture &&
+        ((unsigned)desc->runtimeSamplerDesc.addressingMode >= (unsigned)ommTextureAddressMode_MAX_NUM ||
+         (unsigned)desc->runtimeSamplerDesc.filter >= (unsigned)ommTextureFilterMode_MAX_NUM))
+        return ommResult_FAILURE;
+    ommResult r = validate_desc(*b, *desc);
+    if (r != ommResult_SUCCESS) return r;
+    r = scope_fences(*b, *desc, false);
+    if (r != ommResult_SUCCESS) return r;
+    const Texture& tex = *untag<Texture>(desc->texture);
+    if (tex.owner != b) return b->log.invalid("[Invalid Argument] - ommxResolveHits: the texture was created by another baker");
+    if (result == nullptr) return b->log.invalid("[Invalid Argument] - ommxResolveHits: result is not set");
+    if ((flags & ~(uint32_t)(ommxLookupFlags_Force2State | ommxLookupFlags_IgnoreMicromap)) != 0) return b->log.invalid("[Invalid Argument] - ommxResolveHits: unknown flags");
+    if (count == 0) return ommResult_SUCCESS;
+    if (hits == nullptr || out == nullptr) return b->log.invalid("[Invalid Argument] - ommxResolveHits: hits / out are not set");
+    ResolveParams rp; memset(&rp, 0, sizeof rp);
+    ClassifyParams& P = rp.tex;
+    const TexMip& tm = tex.mips[0];
+    DevMip& dm = P.mips[0];
+    dm.texels = tm.texels; dm.sat = tm.sat; dm.w = tm.w; dm.h = tm.h;
+    dm.log2w = (int)ctz32((uint32_t)tm.w); dm.log2h = (int)ctz32((uint32_t)tm.h);
+    dm.pow2 = is_pow2(tm.w) && is_pow2(tm.h);
+    dm.fw = (float)tm.w; dm.fh = (float)tm.h; dm.rw = 1.f / (float)tm.w; dm.rh = 1.f / (float)tm.h;
+    P.mipCount = 1; P.pow2Dispatch = dm.pow2;
+    P.texIsFp32 = tex.format == ommCpuTextureFormat_FP32;
+    P.addrMode = desc->runtimeSamplerDesc.addressingMode;
+    P.filterLinear = desc->runtimeSamplerDesc.filter == ommTextureFilterMode_Linear;
+    P.cutoff = desc->alphaCutoff; P.borderAlpha = desc->runtimeSamplerDesc.borderAlpha;
+    P.stateGT = desc->alphaCutoffGreater; P.stateLE = desc->alphaCutoffLessEqual;
+    rp.texCoords = desc->texCoords; rp.texCoordFormat = desc->texCoordFormat;
+    rp.texCoordStride = desc->texCoordStrideInBytes ? desc->texCoordStrideInBytes : (desc->texCoordFormat == ommTexCoordFormat_UV32_FLOAT ? 8u : 4u);
+    rp.indices = desc->indexBuffer; rp.indexFormat = desc->indexFormat; rp.numTris = desc->indexCount / 3u;
+    const DeviceScope onBakersDevice(b->bind_device());
+    if (launch_resolve_hits(rp, *result, hits, count, out, flags, (hipStream_t)hipStream) != hipSuccess)
+        return b->log.failure("[Failure] - ommxResolveHits: kernel launch failed");
     return ommResult_SUCCESS;
 }
 
