@@ -10,12 +10,18 @@ micro-triangles span several texels); the driver's line is the default, c2.
 Prints ONE JSON line (rank 0):
   value / ms_per_step   micro-triangles of all unique work items / wall time of a step through ommCpuBake, the SDK entry point: host arrays in, host
   = bake_wall_time_ms   arrays out, PCIe inclusive (SURVEY.md section 8d defines both metrics on it); K timed steps after W warm-up steps; details: host_api
-  device_resident       the SAME bake through ommxBakeDevice (UV / index inputs and result arrays resident in HBM), same steps and warm-up.
-                        (N > 1 GPUs: the sharded device-resident entry is the headline; value_same_entry_as_n_gt_1 = the same entry at every N.)
   host_api              details of the ommCpuBake steps: how arrayData reached the host (result_transfer: plain / streamed / compressed, --result-transfer;
                         bytes over PCIe, codec and expansion times, helper threads), --devices N = the same call spread over N devices of this process
+(N > 1 GPUs, or --host-api-steps 0: the device-resident entry below is the headline, with its phases and roofline.)
+
+A plain run does only what that line needs: set-up, W warm-up and K timed steps of the headline entry, --dump-outputs, the line.
+--full adds every other measurement and check, in the same run:
+  device_resident       the SAME bake through ommxBakeDevice (UV / index inputs and result arrays resident in HBM), same steps and warm-up, with
+                        phases_ms and rates; value_same_entry_as_n_gt_1 = the same entry at every N (N > 1: the ommCpuBake steps as host_api)
   roofline              what limits the dominant kernel (classify_tiles): VALU issue slots; roofline_hbm = the HBM view on the units the
-                        launch really processes; cpu_baseline = the oracle (port of the reference CPU baker) on the host cores, same run
+                        launch really processes
+  cpu_baseline          the oracle (port of the reference CPU baker) on the host cores, with the bit-exact parity gate on its sample, fine_pass_only,
+                        the SAT-off pair (c2), ommCpuCreateTexture at 4K and 8K (c2), concurrent_bakes (--concurrent K)
 """
 import argparse
 import ctypes as C
@@ -267,9 +273,11 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2")
     ap.add_argument("--tris", type=int, default=0, help="override the configuration's triangle count")
     ap.add_argument("--host-api-steps", type=int, default=-1, help="timed bakes through ommCpuBake (host arrays in / out); -1 = --steps, 0 = skip")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="triangles baked by the CPU baseline (-1 = the configuration's default, 0 = skip)")
-    ap.add_argument("--create-texture", type=int, default=1, help="time ommCpuCreateTexture at 4K and 8K (0 = skip)")
-    ap.add_argument("--sat-off-sample", type=int, default=50000, help="c2 only: triangles of the SAT-off (no coarse pass) GPU measurement; CPU uses 1/20 of it (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beyond the headline steps: the other entry point, roofline, "
+                                                        "CPU baseline with its parity gate, SAT-off pair, ommCpuCreateTexture timings, --concurrent")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="--full: triangles baked by the CPU baseline (-1 = the configuration's default, 0 = skip)")
+    ap.add_argument("--create-texture", type=int, default=1, help="--full: time ommCpuCreateTexture at 4K and 8K (0 = skip)")
+    ap.add_argument("--sat-off-sample", type=int, default=50000, help="--full, c2 only: triangles of the SAT-off (no coarse pass) GPU measurement; CPU uses 1/20 of it (0 = skip)")
     ap.add_argument("--generic-pass", type=int, default=0, help="ommxBakerKnob_GenericPass (0 = library default, 1 = inside the persistent launch, 2 = deferred pass)")
     ap.add_argument("--stream-chunks", type=int, default=0, help="ommxBakerKnob_StreamChunks for the ommCpuBake measurement (0 = library default)")
     ap.add_argument("--result-transfer", type=int, default=0, help="ommxBakerKnob_ResultTransfer for the ommCpuBake measurement (0 = library default, 1 = plain copy, 2 = streamed placement, 3 = compressed)")
@@ -278,9 +286,11 @@ def main():
     ap.add_argument("--zero-ahead", type=int, default=0, help="ommxBakerKnob_ZeroAhead (0 = library default: on, 1 = off)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the result arrays of the last timed step as DIR/<name>.npy "
                                                                            "(float32 / float64, at most 64 MB in all: long arrays as a fixed, seeded sample)")
-    ap.add_argument("--concurrent", type=int, default=0, help="also measure K host threads baking concurrently on ONE baker through ommCpuBake (bakes/s for 1, 4, .. K threads; "
+    ap.add_argument("--concurrent", type=int, default=0, help="--full: also measure K host threads baking concurrently on ONE baker through ommCpuBake (bakes/s for 1, 4, .. K threads; "
                                                               "the reference documents caller-level parallelism as a first-class strategy, docs/integration_guide.md:434)")
     args = ap.parse_args()
+    if not args.full and (args.concurrent > 0 or args.cpu_sample > 0):
+        ap.error("--concurrent and --cpu-sample size measurements that only a --full run makes: add --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as typed: this process becomes the launcher -- one rank per GPU under torch.distributed.run, same arguments,
         # rank 0's JSON line on this process's stdout.  (The driver's own torch.distributed.run command line lands in the branch below.)
@@ -289,6 +299,9 @@ def main():
     tris = args.tris or cfg["tris"]
     host_steps = args.steps if args.host_api_steps < 0 else args.host_api_steps
     cpu_sample = cfg["cpu_sample"] if args.cpu_sample < 0 else args.cpu_sample
+    # the headline entry: ommCpuBake at N = 1, the device-resident entry at N > 1 or with --host-api-steps 0; --full times the other one as well
+    host_headline = args.gpus == 1 and host_steps > 0
+    run_device = args.full or not host_headline
 
     import torch
     import torch.distributed as dist
@@ -323,13 +336,14 @@ def main():
         prod.set_knob(baker, ot.KNOB_ZERO_AHEAD, args.zero_ahead)
     th = prod.create_texture(baker, [tex], alpha_cutoff=0.5)
     host_desc = desc_for(th, uv, ix, lv, kw)
-    # inputs resident in HBM before the timed region: torch owns the device buffers, the library gets raw pointers
-    d_uv = torch.from_numpy(np.ascontiguousarray(uv)).cuda()
-    d_ix = torch.from_numpy(ix.astype(np.int32)).cuda()
-    d_lv = torch.from_numpy(np.ascontiguousarray(lv)).cuda() if lv is not None else None
-    desc = ot.BakeInputDesc.from_buffer_copy(host_desc)
-    desc.texCoords, desc.indexBuffer = d_uv.data_ptr(), d_ix.data_ptr()
-    desc.subdivisionLevels = d_lv.data_ptr() if d_lv is not None else None
+    if run_device:
+        # inputs resident in HBM before the timed region: torch owns the device buffers, the library gets raw pointers
+        d_uv = torch.from_numpy(np.ascontiguousarray(uv)).cuda()
+        d_ix = torch.from_numpy(ix.astype(np.int32)).cuda()
+        d_lv = torch.from_numpy(np.ascontiguousarray(lv)).cuda() if lv is not None else None
+        desc = ot.BakeInputDesc.from_buffer_copy(host_desc)
+        desc.texCoords, desc.indexBuffer = d_uv.data_ptr(), d_ix.data_ptr()
+        desc.subdivisionLevels = d_lv.data_ptr() if d_lv is not None else None
 
     import omm_amd.sharded as shard
 
@@ -404,45 +418,48 @@ def main():
         g0 = torch.empty(4 * world, dtype=torch.int32, device="cuda")
         dist.all_gather_into_tensor(g0, w0)
         torch.cuda.synchronize()
-    last = None
-    for _ in range(args.warmup):
-        if last is not None:
-            prod.dll.ommxDestroyDeviceBakeResult(last)
-        last = step()
-    sync()
-    t0 = time.perf_counter()
-    tms = []
-    for _ in range(args.steps):
-        if last is not None:
-            prod.dll.ommxDestroyDeviceBakeResult(last)
-        last = step()
-        tms.append(get_timings(prod, baker))
-    sync()
-    elapsed = time.perf_counter() - t0
-    if world > 1:
-        tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed = float(tt.item())
-    micro_tris = float(tms[-1].microTriangles)  # whole job: every rank reports the full work-item list
+    tms, result_info, dumped = [], None, None
+    if run_device:
+        last = None
+        for _ in range(args.warmup):
+            if last is not None:
+                prod.dll.ommxDestroyDeviceBakeResult(last)
+            last = step()
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            if last is not None:
+                prod.dll.ommxDestroyDeviceBakeResult(last)
+            last = step()
+            tms.append(get_timings(prod, baker))
+        sync()
+        elapsed = time.perf_counter() - t0
+        if world > 1:
+            tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            elapsed = float(tt.item())
 
-    pd = C.POINTER(ot.BakeResultDesc)()
-    prod.dll.ommxGetDeviceBakeResultDesc(last, C.byref(pd))
-    rd = pd.contents
-    result_info = {"arrayDataBytes": int(rd.arrayDataSize), "descs": int(rd.descArrayCount), "triangles": int(rd.indexCount)}
-    dumped = None
-    if args.dump_outputs and rank == 0 and not (world == 1 and host_steps > 0):   # the device-resident bake is the timed path of this run
-        hip = ot.Hip()
-        dumped = dump_outputs(args.dump_outputs, rd, hip.download)
-    prod.dll.ommxDestroyDeviceBakeResult(last)
+        pd = C.POINTER(ot.BakeResultDesc)()
+        prod.dll.ommxGetDeviceBakeResultDesc(last, C.byref(pd))
+        rd = pd.contents
+        result_info = {"arrayDataBytes": int(rd.arrayDataSize), "descs": int(rd.descArrayCount), "triangles": int(rd.indexCount)}
+        if args.dump_outputs and rank == 0 and not (world == 1 and host_steps > 0):   # the device-resident bake is the timed path of this run
+            hip = ot.Hip()
+            dumped = dump_outputs(args.dump_outputs, rd, hip.download)
+        prod.dll.ommxDestroyDeviceBakeResult(last)
 
     # ---- the SDK entry point proper: host arrays in, host arrays out (metric 2) ----
     host_ms, host_first_ms, host_tms = None, None, []
     if args.devices:
         prod.set_knob(baker, ot.KNOB_DEVICES, args.devices)
-    if rank == 0 and host_steps > 0:
+    if rank == 0 and host_steps > 0 and (host_headline or args.full):
         t1 = time.perf_counter()
         r, out = prod.bake_raw(baker, host_desc)
         assert r == ot.SUCCESS
+        if result_info is None:   # no device-resident bake in this run: the sizes of the same result, read from this untimed first call
+            hpd = C.POINTER(ot.BakeResultDesc)()
+            assert prod.fn("ommCpuGetBakeResultDesc")(out, C.byref(hpd)) == ot.SUCCESS
+            result_info = {"arrayDataBytes": int(hpd.contents.arrayDataSize), "descs": int(hpd.contents.descArrayCount), "triangles": int(hpd.contents.indexCount)}
         prod.fn("ommCpuDestroyBakeResult")(out)
         host_first_ms = (time.perf_counter() - t1) * 1e3   # cold: the pinned staging buffer and the result pages are set up
         for _ in range(max(0, args.warmup - 1)):
@@ -476,21 +493,16 @@ def main():
             comm_info = {"kind": "RCCL communicator made by the library (ncclCommCount / ncclCommUserRank)" if native else "caller collectives over torch.distributed (%s)" % dist.get_backend(),
                          "ranks": int(cw.value), "this_rank": int(cr.value)}
     if rank == 0:
-        dev_ms = elapsed / args.steps * 1e3
         # headline: the SDK entry point itself (SURVEY.md section 8d defines both metrics on ommCpuBake); the device-resident entry is the named secondary.
         # N > 1 (and runs that skip the host bakes) have only the device-resident entry.
         headline_host = host_ms is not None and world == 1
+        dev_ms = elapsed / args.steps * 1e3 if tms else None
         ms_per_step = host_ms if headline_host else dev_ms
+        if tms and host_tms:
+            assert host_tms[-1].microTriangles == tms[-1].microTriangles, "ommCpuBake and the device-resident entry count different work items"
+        t_last = tms[-1] if tms else host_tms[-1]   # (a plain ommCpuBake run times no device-resident bake: the same work items from its own timings)
+        micro_tris = float(t_last.microTriangles)  # whole job: every rank reports the full work-item list
         avg = lambda f, ts=tms: float(np.mean([getattr(t, f) for t in ts]))
-        classify_ms = avg("classifyMs")
-        persistent_ms = avg("persistentMs") or classify_ms
-        generic_ms = avg("genericMs")
-        # the dominant kernel: the persistent classify_tiles launch, or -- bakes of asset-sized triangles -- the deferred generic pass behind it
-        dom_kernel = "classify_generic" if generic_ms > persistent_ms else "classify_tiles"
-        tiles_ms = persistent_ms
-        if dom_kernel == "classify_generic":
-            persistent_ms = generic_ms   # (every roofline figure below is about the dominant kernel)
-        t_last = tms[-1]
         bits = 2
         line = {
             "communicator": comm_info,
@@ -509,21 +521,32 @@ def main():
             # `value` / `ms_per_step` / `bake_wall_time_ms`: the SDK call a drop-in user makes, ommCpuBake, host arrays in and out, PCIe inclusive (SURVEY.md
             # section 8d defines both metrics on it).  `device_resident`: the same bake through ommxBakeDevice (inputs and result arrays in HBM), same steps.
             "value_entry": "ommCpuBake" if headline_host else ("ommxBakeDevice" if world == 1 else ("ommxShardedBakeRccl" if one_call else "ommxSharded* + torch.distributed")),
-            # A scaling curve over N must compare ONE entry: at N > 1 `value` is the device-resident sharded bake, so the N = 1 line carries the
-            # device-resident single-GPU bake under this key as well (at N > 1 it repeats `value`)
-            "value_same_entry_as_n_gt_1": {"entry": "ommxBakeDevice" if world == 1 else entry_n, "value": micro_tris / (dev_ms * 1e-3), "ms_per_step": dev_ms,
-                                           "note": "the device-resident bake (UV / index inputs and result arrays in HBM): the entry whose sharded form is `value` for n_gpus > 1"},
             "bake_wall_time_ms": ms_per_step,
             "bake_wall_time_entry": "ommCpuBake (host arrays in/out, PCIe inclusive)" if headline_host else "device-resident entry (ommCpuBake was not timed in this run)",
-            "device_resident": {"entry": "ommxBakeDevice" if world == 1 else entry_n, "ms_per_bake": dev_ms, "micro_triangles_per_s": micro_tris / (dev_ms * 1e-3), "bakes": args.steps,
-                                "note": "the ommCpuBake contract with the UV / index inputs and the result arrays resident in HBM (no PCIe in the timed region)"},
-            "rates": {"all_work_items": micro_tris / (ms_per_step * 1e-3),
-                      "open_tiles_only": float(t_last.openTileMicroTriangles) / ((tiles_ms + generic_ms) * 1e-3) if tiles_ms + generic_ms > 0 else None,
-                      "note": "`value` counts 4^level micro-triangles for every unique work item like the reference's loop does; most of them are settled by hierarchical queries "
-                              "(summed-area table, curve-free regions) without per-micro-triangle work, so the rate over the micro-triangles of the tiles that reach classify_tiles "
-                              "(device-resident bake, kernel time) is given too; the fine pass alone: fine_pass_only, measured on the CPU baseline's sample on both sides"},
-            "phases_ms": {k: avg(k) for k in ("uploadMs", "setupMs", "triageMs", "classifyMs", "persistentMs", "genericMs", "digestMs", "tailMs", "gatherMs", "downloadMs", "totalMs")},
         }
+        if tms:
+            classify_ms = avg("classifyMs")
+            persistent_ms = avg("persistentMs") or classify_ms
+            generic_ms = avg("genericMs")
+            # the dominant kernel: the persistent classify_tiles launch, or -- bakes of asset-sized triangles -- the deferred generic pass behind it
+            dom_kernel = "classify_generic" if generic_ms > persistent_ms else "classify_tiles"
+            tiles_ms = persistent_ms
+            if dom_kernel == "classify_generic":
+                persistent_ms = generic_ms   # (every roofline figure below is about the dominant kernel)
+            line.update({
+                # A scaling curve over N must compare ONE entry: at N > 1 `value` is the device-resident sharded bake, so the N = 1 line carries the
+                # device-resident single-GPU bake under this key as well (at N > 1 it repeats `value`)
+                "value_same_entry_as_n_gt_1": {"entry": "ommxBakeDevice" if world == 1 else entry_n, "value": micro_tris / (dev_ms * 1e-3), "ms_per_step": dev_ms,
+                                               "note": "the device-resident bake (UV / index inputs and result arrays in HBM): the entry whose sharded form is `value` for n_gpus > 1"},
+                "device_resident": {"entry": "ommxBakeDevice" if world == 1 else entry_n, "ms_per_bake": dev_ms, "micro_triangles_per_s": micro_tris / (dev_ms * 1e-3), "bakes": args.steps,
+                                    "note": "the ommCpuBake contract with the UV / index inputs and the result arrays resident in HBM (no PCIe in the timed region)"},
+                "rates": {"all_work_items": micro_tris / (ms_per_step * 1e-3),
+                          "open_tiles_only": float(t_last.openTileMicroTriangles) / ((tiles_ms + generic_ms) * 1e-3) if tiles_ms + generic_ms > 0 else None,
+                          "note": "`value` counts 4^level micro-triangles for every unique work item like the reference's loop does; most of them are settled by hierarchical queries "
+                                  "(summed-area table, curve-free regions) without per-micro-triangle work, so the rate over the micro-triangles of the tiles that reach classify_tiles "
+                                  "(device-resident bake, kernel time) is given too; the fine pass alone: fine_pass_only, measured on the CPU baseline's sample on both sides"},
+                "phases_ms": {k: avg(k) for k in ("uploadMs", "setupMs", "triageMs", "classifyMs", "persistentMs", "genericMs", "digestMs", "tailMs", "gatherMs", "downloadMs", "totalMs")},
+            })
         if host_ms is not None:
             havg = lambda f: avg(f, host_tms)
             line["host_api"] = {"entry": "ommCpuBake (host arrays in/out, PCIe inclusive)", "ms_per_bake": host_ms, "bakes": host_steps, "first_call_ms": host_first_ms,
@@ -549,58 +572,59 @@ def main():
                                                    "(small results, or a classification so long that the copy is not worth a quarter of its speed)"},
                                 "phases_ms": {k: havg(k) for k in ("uploadMs", "setupMs", "triageMs", "classifyMs", "digestMs", "tailMs", "gatherMs", "downloadMs", "totalMs")}}
 
-        # ---- roofline of the dominant kernel, classify_tiles (the persistent launch of the levels >= 6) ----
-        # The kernel is bound by VALU issue slots, not by HBM and not by MFMA.  Instruction counts per launch come from the separate
-        # rocprofv3 --pmc passes of profiles/collect.sh (they cannot be read from inside this process) and apply only to the workload AND the library
-        # sources they were collected on: the summary carries a hash of omm_amd/csrc, and a summary of other sources is not used.
-        launches = 1
-        # HBM view on the units the launch really processes: packed states of the OPEN tiles (0.25 B per 4-state micro-triangle), their 48-byte records,
-        # one pass over the texture and its summed-area table (5 B per texel)
-        tw, thh = tex.shape[1], tex.shape[0]
-        alg_bytes = bits / 8.0 * float(t_last.openTileMicroTriangles) + 48.0 * t_last.openTiles + tw * thh * 5.0
-        formula = "(0.25 B x micro-triangles of the open tiles + 48 B x open tiles + 5 B x texels) / HIP-event duration of the launch"
-        if dom_kernel == "classify_generic":   # queue entry read (8 B) + state ORed in (4 B word) per queued micro-triangle, one pass over the texture
-            alg_bytes = 12.0 * float(t_last.genericMicroTriangles) + tw * thh * (4.0 if tex.dtype == np.float32 else 1.0)
-            formula = "(12 B x queued micro-triangles + one pass over the texels) / HIP-event duration of the launch"
-        hbm_achieved = alg_bytes / (persistent_ms * 1e-3) / 1e9 if persistent_ms > 0 else 0.0
-        roof_hbm = {"bound": "hbm", "kernel": dom_kernel, "achieved": hbm_achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_achieved / HBM_PEAK_GBS, "traffic": None,
-                    "avg_launch_ms": persistent_ms, "algorithmic_bytes_per_launch": alg_bytes,
-                    "formula": formula,
-                    "all_work_items_view": {"note": "SURVEY.md section 8d per-unit figure (0.25 B per micro-triangle of EVERY unique work item + 24 B per item + 5 B per texel) over the same duration; "
-                                                    "95 % of those micro-triangles are settled by hierarchical SAT queries and never reach this launch",
-                                            "achieved": (bits / 8.0 * micro_tris + 24.0 * t_last.uniqueItems + tw * thh * 5.0) / (persistent_ms * 1e-3) / 1e9 if persistent_ms > 0 else None}}
-        roof_hbm["all_work_items_view"]["frac"] = (roof_hbm["all_work_items_view"]["achieved"] or 0.0) / HBM_PEAK_GBS
-        line["roofline"] = roof_hbm
-        tpath = os.path.join(ROOT, "profiles", "pmc_latest_%s.json" % args.config)
-        default_workload = tris == cfg["tris"]
-        if world == 1 and default_workload and os.path.exists(tpath):
-            tj = json.load(open(tpath))
-            if tj.get("source_sha256_16") == source_hash() and tj.get("kernel", "classify_tiles") == dom_kernel:
-                src = ("profiles/%s_pmc.md -- NOT counters of this run: separate rocprofv3 --pmc passes of `%s`, collected %s on %s; %s; per-launch counts are deterministic for the "
-                       "workload and are used only when the hash of omm_amd/csrc matches (%s)") % (tj.get("tag"), tj.get("command"), tj.get("collected_utc", "in an earlier round"),
-                                                                                                 tj.get("collected_on", "a gpurun lease"), tj.get("corrections"), tj.get("source_sha256_16"))
-                roof_hbm["traffic"] = tj.get("traffic_bytes_per_launch")
-                roof_hbm["traffic_source"] = src
-                valu = tj.get("valu_wave_instructions_per_launch"); hz = tj.get("shader_clock_hz")
-                if valu and hz and persistent_ms > 0:
-                    ipc = valu / (persistent_ms * 1e-3 * hz * NUM_SIMDS)
-                    line["roofline"] = {"bound": "valu_issue", "kernel": dom_kernel, "achieved": ipc, "peak": VALU_ISSUE_PEAK, "unit": "VALU wave-instructions / cycle / SIMD",
-                                        "frac": ipc / VALU_ISSUE_PEAK, "traffic": tj.get("traffic_bytes_per_launch"), "avg_launch_ms": persistent_ms,
-                                        "formula": "SQ_INSTS_VALU per launch (%.4g, PMC pass) / (HIP-event duration of the launch x %.4g Hz shader clock (GRBM_GUI_ACTIVE / 8 / duration of the counter pass) x 1024 SIMDs) / 0.5" % (valu, hz),
-                                        "calibrated_issue_utilisation": tj.get("valu_issue_utilisation"), "scalar_issue_utilisation": tj.get("scalar_issue_utilisation"),
-                                        "valu_lane_utilisation": tj.get("valu_lane_util"), "scalar_per_valu": tj.get("scalar_per_valu"),
-                                        "note": "calibrated = every instruction class priced with its measured issue cost (profiles/valu_rates_mi355x.json) instead of 2 cycles",
-                                        "source": src}
-                    line["roofline_hbm"] = roof_hbm
-            else:
-                roof_hbm["traffic_source"] = "none: %s was collected on other sources (%s, tree is %s)" % (os.path.basename(tpath), tj.get("source_sha256_16"), source_hash())
-        # the streaming part of the path for comparison: final gather of the surviving OMM blocks into arrayData order
-        gather_ms = avg("gatherMs")
-        if gather_ms > 0 and world == 1:
-            gb = 2.0 * result_info["arrayDataBytes"] + 8.0 * result_info["descs"] + 8.0 * result_info["triangles"]
-            line["roofline_streaming"] = {"bound": "hbm", "kernel": "tail_gather_omms (+ narrow_indices)", "achieved": gb / (gather_ms * 1e-3) / 1e9,
-                                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gb / (gather_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
-        if world == 1 and args.concurrent > 0:
+        if tms:
+            # ---- roofline of the dominant kernel, classify_tiles (the persistent launch of the levels >= 6) ----
+            # The kernel is bound by VALU issue slots, not by HBM and not by MFMA.  Instruction counts per launch come from the separate
+            # counter-collection passes of profiles/collect.sh (they cannot be read from inside this process) and apply only to the workload AND the library
+            # sources they were collected on: the summary carries a hash of omm_amd/csrc, and a summary of other sources is not used.
+            launches = 1
+            # HBM view on the units the launch really processes: packed states of the OPEN tiles (0.25 B per 4-state micro-triangle), their 48-byte records,
+            # one pass over the texture and its summed-area table (5 B per texel)
+            tw, thh = tex.shape[1], tex.shape[0]
+            alg_bytes = bits / 8.0 * float(t_last.openTileMicroTriangles) + 48.0 * t_last.openTiles + tw * thh * 5.0
+            formula = "(0.25 B x micro-triangles of the open tiles + 48 B x open tiles + 5 B x texels) / HIP-event duration of the launch"
+            if dom_kernel == "classify_generic":   # queue entry read (8 B) + state ORed in (4 B word) per queued micro-triangle, one pass over the texture
+                alg_bytes = 12.0 * float(t_last.genericMicroTriangles) + tw * thh * (4.0 if tex.dtype == np.float32 else 1.0)
+                formula = "(12 B x queued micro-triangles + one pass over the texels) / HIP-event duration of the launch"
+            hbm_achieved = alg_bytes / (persistent_ms * 1e-3) / 1e9 if persistent_ms > 0 else 0.0
+            roof_hbm = {"bound": "hbm", "kernel": dom_kernel, "achieved": hbm_achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_achieved / HBM_PEAK_GBS, "traffic": None,
+                        "avg_launch_ms": persistent_ms, "algorithmic_bytes_per_launch": alg_bytes,
+                        "formula": formula,
+                        "all_work_items_view": {"note": "SURVEY.md section 8d per-unit figure (0.25 B per micro-triangle of EVERY unique work item + 24 B per item + 5 B per texel) over the same duration; "
+                                                        "95 % of those micro-triangles are settled by hierarchical SAT queries and never reach this launch",
+                                                "achieved": (bits / 8.0 * micro_tris + 24.0 * t_last.uniqueItems + tw * thh * 5.0) / (persistent_ms * 1e-3) / 1e9 if persistent_ms > 0 else None}}
+            roof_hbm["all_work_items_view"]["frac"] = (roof_hbm["all_work_items_view"]["achieved"] or 0.0) / HBM_PEAK_GBS
+            line["roofline"] = roof_hbm
+            tpath = os.path.join(ROOT, "profiles", "pmc_latest_%s.json" % args.config)
+            default_workload = tris == cfg["tris"]
+            if world == 1 and default_workload and os.path.exists(tpath):
+                tj = json.load(open(tpath))
+                if tj.get("source_sha256_16") == source_hash() and tj.get("kernel", "classify_tiles") == dom_kernel:
+                    src = ("profiles/%s_pmc.md -- NOT counters of this run: separate counter-collection passes of `%s`, collected %s on %s; %s; per-launch counts are deterministic for the "
+                           "workload and are used only when the hash of omm_amd/csrc matches (%s)") % (tj.get("tag"), tj.get("command"), tj.get("collected_utc", "in an earlier round"),
+                                                                                                     tj.get("collected_on", "an unrecorded machine"), tj.get("corrections"), tj.get("source_sha256_16"))
+                    roof_hbm["traffic"] = tj.get("traffic_bytes_per_launch")
+                    roof_hbm["traffic_source"] = src
+                    valu = tj.get("valu_wave_instructions_per_launch"); hz = tj.get("shader_clock_hz")
+                    if valu and hz and persistent_ms > 0:
+                        ipc = valu / (persistent_ms * 1e-3 * hz * NUM_SIMDS)
+                        line["roofline"] = {"bound": "valu_issue", "kernel": dom_kernel, "achieved": ipc, "peak": VALU_ISSUE_PEAK, "unit": "VALU wave-instructions / cycle / SIMD",
+                                            "frac": ipc / VALU_ISSUE_PEAK, "traffic": tj.get("traffic_bytes_per_launch"), "avg_launch_ms": persistent_ms,
+                                            "formula": "SQ_INSTS_VALU per launch (%.4g, PMC pass) / (HIP-event duration of the launch x %.4g Hz shader clock (GRBM_GUI_ACTIVE / 8 / duration of the counter pass) x 1024 SIMDs) / 0.5" % (valu, hz),
+                                            "calibrated_issue_utilisation": tj.get("valu_issue_utilisation"), "scalar_issue_utilisation": tj.get("scalar_issue_utilisation"),
+                                            "valu_lane_utilisation": tj.get("valu_lane_util"), "scalar_per_valu": tj.get("scalar_per_valu"),
+                                            "note": "calibrated = every instruction class priced with its measured issue cost (profiles/valu_rates_mi355x.json) instead of 2 cycles",
+                                            "source": src}
+                        line["roofline_hbm"] = roof_hbm
+                else:
+                    roof_hbm["traffic_source"] = "none: %s was collected on other sources (%s, tree is %s)" % (os.path.basename(tpath), tj.get("source_sha256_16"), source_hash())
+            # the streaming part of the path for comparison: final gather of the surviving OMM blocks into arrayData order
+            gather_ms = avg("gatherMs")
+            if gather_ms > 0 and world == 1:
+                gb = 2.0 * result_info["arrayDataBytes"] + 8.0 * result_info["descs"] + 8.0 * result_info["triangles"]
+                line["roofline_streaming"] = {"bound": "hbm", "kernel": "tail_gather_omms (+ narrow_indices)", "achieved": gb / (gather_ms * 1e-3) / 1e9,
+                                              "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gb / (gather_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
+        if args.full and world == 1 and args.concurrent > 0:
             # K caller threads share one baker and one texture (the SDK allows concurrent ommCpuBake calls on a baker: docs/integration_guide.md:434); every
             # thread bakes the same desc through ommCpuBake + ommCpuDestroyBakeResult; ctypes releases the GIL for the duration of a call
             import threading
@@ -621,10 +645,10 @@ def main():
                 cc[str(K)] = {"bakes_per_s": K * per_thread / dtc, "ms_per_bake_per_thread": dtc / per_thread * 1e3, "bakes": K * per_thread}
             line["concurrent_bakes"] = {"entry": "ommCpuBake from K threads on one baker", "threads": cc,
                                         "scaling_vs_one_thread": {k: v["bakes_per_s"] / cc[str(ks[0])]["bakes_per_s"] for k, v in cc.items()}}
-        if world == 1 and args.create_texture and args.config == "c2":
+        if args.full and world == 1 and args.create_texture and args.config == "c2":
             line["create_texture_ms"] = {"entry": "ommCpuCreateTexture, UNORM8 + alphaCutoff (H2D + device summed-area table)", "4096": create_texture_ms(prod, baker, 4096, 1234),
                                          "8192": create_texture_ms(prod, baker, 8192, 1234)}
-        if cpu_sample > 0 and world == 1:
+        if args.full and cpu_sample > 0 and world == 1:
             cb, cpu_res, (suv, six, slv), dt, ph = cpu_baseline(tex, uv, ix, lv, kw, cpu_sample)
             # correctness gate of the same run: the HIP library bakes the CPU sample, byte-for-byte comparison
             sdesc = desc_for(th, suv, six, slv, kw)

@@ -26,7 +26,7 @@ python profiles/summarize_pmc.py $tag $O "python bench.py --config $cfg $PM" > $
 # valu_issue roofline and its traffic figure; bench.py accepts the summary only when its source hash equals the tree's)
 [ -s $O/${tag}_hbm_traffic.json ] && cp $O/${tag}_hbm_traffic.json $R/profiles/pmc_latest_$cfg.json
 cd /tmp
-timeout 1200 $BENCH > $O/bench.json 2> $O/bench.err
+timeout 1200 $BENCH --full > $O/bench.json 2> $O/bench.err
 cd $R
 tail -c 900 $O/bench.json; echo; cat $O/pmc_summary.json; head -14 $O/kernel_stats.md
 # only the summaries travel back (gpurun merges at most 64 MiB; the raw trace database and counter CSVs of one configuration are larger than that)

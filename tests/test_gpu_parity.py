@@ -982,7 +982,7 @@ def test_bench_contract_small():
     import json, subprocess, sys, os
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "c2", "--tris", "3000", "--steps", "2", "--warmup", "1",
-                          "--cpu-sample", "300", "--sat-off-sample", "400", "--host-api-steps", "2", "--stream-chunks", "3", "--create-texture", "0"], capture_output=True, text=True, timeout=600)
+                          "--cpu-sample", "300", "--sat-off-sample", "400", "--host-api-steps", "2", "--stream-chunks", "3", "--create-texture", "0", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -998,7 +998,7 @@ def test_bench_contract_small():
     assert d["roofline"]["bound"] == "hbm"          # (the issue-slot roofline needs the PMC summary of the full-size workload)
     for cfgname in ("c1", "c4", "cards"):
         o2 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", cfgname, "--tris", "1500", "--steps", "1", "--warmup", "1", "--cpu-sample", "200",
-                             "--host-api-steps", "1"], capture_output=True, text=True, timeout=600)
+                             "--host-api-steps", "1", "--full"], capture_output=True, text=True, timeout=600)
         assert o2.returncode == 0, (cfgname, o2.stderr[-2000:])
         d2 = json.loads([l for l in o2.stdout.splitlines() if l.startswith("{")][0])
         assert d2["config"]["name"] == cfgname and d2["parity_vs_cpu_baseline"].startswith("bit-exact") and d2["value"] > 0
@@ -1009,6 +1009,35 @@ def test_bench_contract_small():
     assert set(("value", "unit", "cores", "kind", "sample")) <= set(d["cpu_baseline"]) and d["cpu_baseline"]["kind"] == "port"
     assert "workload" in d["config"] and "model" not in d["config"]
     assert d["parity_vs_cpu_baseline"].startswith("bit-exact") and d["sat_off"]["parity"].startswith("bit-exact")
+
+
+def test_bench_plain_run_small(tmp_path):
+    """bench.py without --full times the headline entry alone (ommCpuBake at N = 1) and prints its line: the same work, result and dumped arrays
+    as the --full run of the same command, none of the secondary measurements"""
+    import json, subprocess, sys, os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = {}
+    for mode in ("plain", "full"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--config", "c2", "--tris", "3000", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / mode)]
+        if mode == "full":
+            cmd += ["--full", "--cpu-sample", "0", "--sat-off-sample", "0", "--create-texture", "0"]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, (mode, out.stderr[-2000:])
+        got = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(got) == 1, (mode, out.stdout[-2000:])
+        lines[mode] = json.loads(got[0])
+    d, f = lines["plain"], lines["full"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config", "host_api"):
+        assert k in d, k
+    for k in ("device_resident", "value_same_entry_as_n_gt_1", "phases_ms", "roofline", "cpu_baseline", "sat_off", "create_texture_ms"):
+        assert k not in d, k
+    assert "device_resident" in f and "roofline" in f
+    assert d["value_entry"] == f["value_entry"] == "ommCpuBake" and d["ms_per_step"] == d["host_api"]["ms_per_bake"] > 0 and d["steps"] == 2 and d["warmup"] == 1
+    assert d["config"]["result"] == f["config"]["result"] and d["config"]["unique_items"] == f["config"]["unique_items"]
+    assert abs(d["value"] * d["ms_per_step"] / (f["value"] * f["ms_per_step"]) - 1.0) < 1e-9   # the same micro-triangle count
+    assert d["dump_outputs"]["arrays"] == f["dump_outputs"]["arrays"]
+    for name in d["dump_outputs"]["arrays"]:
+        assert np.array_equal(np.load(str(tmp_path / "plain" / (name + ".npy"))), np.load(str(tmp_path / "full" / (name + ".npy")))), name
 
 
 # ---------------------------------------------------------------------------------------------

@@ -144,3 +144,16 @@ def test_bench_gpus_n_relaunches_itself_under_the_launcher(monkeypatch):
     assert a[a.index("--nproc-per-node") + 1] == "8" and a[a.index("--master-addr") + 1] == "127.0.0.1" and int(a[a.index("--master-port") + 1]) > 0
     assert os.path.samefile(a[a.index("--master-port") + 2], os.path.join(root, "bench.py"))
     assert a[-6:] == ["--gpus", "8", "--steps", "3", "--warmup", "1"]
+
+
+def test_bench_full_only_options_need_full(monkeypatch, capsys):
+    """--concurrent and --cpu-sample size measurements that only `bench.py --full` makes: a run without --full refuses them instead of ignoring them"""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    for extra in (["--concurrent", "4"], ["--cpu-sample", "300"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "1"] + extra)
+        with pytest.raises(SystemExit) as e:
+            bench.main()
+        assert e.value.code == 2 and "--full" in capsys.readouterr().err, extra
