@@ -36,19 +36,6 @@ namespace ommx {
 //        3. states are packed LSB-first into 32-bit words (coalesced stores) and the tile's state mask is OR-reduced
 //           for the uniform-OMM ("special index") detection.
 // ------------------------------------------------------------------------------------------------
-// curve-free-region test (region_curve.h) of the 64-groups inside the persistent kernel: inlined, or as a call with a register allocation of its own
-// (measured on the metric configuration: 15.55 vs 15.60 ms -- the same; inlined it needs 40 bytes per lane less scratch)
-#ifndef OMMX_RC_CALL
-#define OMMX_RC_CALL 0
-#endif
-#if OMMX_RC_CALL
-#define OMMX_RC_GROUP_TEST region_curve_state_call
-#else
-#define OMMX_RC_GROUP_TEST region_curve_state_impl
-#endif
-#ifndef OMMX_RC_LEVELS   // bit 0: items, bit 1: tiles, bit 2: 64-groups (A/B builds; the product ships all three)
-#define OMMX_RC_LEVELS 7
-#endif
 constexpr int BLOCK = 256;
 constexpr int GROUP = 64;
 
@@ -84,7 +71,7 @@ __global__ __launch_bounds__(256) void triage_items(ClassifyParams P, const floa
     const float maxAbs = item_max_abs(t);
     if (P.useCoarse) st = region_state<ModeDynamic>(P, whole, maxAbs, no_window());
     // small triangles in a mixed neighbourhood that the level curve does not reach (region_curve.h): uniform as well
-    if ((OMMX_RC_LEVELS & 1) && st < 0 && region_curve_applies(P) && !degenerate[i]) {
+    if (st < 0 && region_curve_applies(P) && !degenerate[i]) {
         const DevMip& m = P.mips[0];
         st = region_curve_state<ModeDynamic>(P, P.texIsFp32 != 0, rc_shape(t, m.fw, m.fh, m.w, m.h, level[i]), whole, maxAbs);
     }
@@ -190,15 +177,14 @@ __global__ __launch_bounds__(256) void triage_tiles(ClassifyParams P, ItemArrays
         r = region_rect<ModeDynamic>(P, sub, maxAbs);
         // (a tile that IS its work item -- level 6 here, level 5 in the 1024-tile queue -- was asked both questions by triage_items, with the same arguments,
         //  and is on the active list because the answer was no: configs[1], 10 192 such tiles, 22 -> 9 us)
-        constexpr bool kSameTests = ((OMMX_RC_LEVELS & 1) != 0) == ((OMMX_RC_LEVELS & 2) != 0);
-        const bool asked = kSameTests && level == TILE_LOG4;
+        const bool asked = level == TILE_LOG4;
         if (P.useCoarse && !asked) st = region_state<ModeDynamic>(P, sub, maxAbs, no_window());
         // a tile in a mixed neighbourhood that the level curve does not reach (region_curve.h): settled like a uniform one
         if (st < 0 && region_curve_applies(P) && !A.degenerate[item]) {
             const DevMip& m = P.mips[0];
             const RcShape shape = rc_shape(uv, m.fw, m.fh, m.w, m.h, level);
             fatItem = shape.ok != 0 && shape.fat != 0;   // (into the record of an open tile: the persistent launch's single-texel pass asks per micro-triangle)
-            if ((OMMX_RC_LEVELS & 2) && !asked) st = region_curve_state<ModeDynamic>(P, P.texIsFp32 != 0, shape, sub, maxAbs);
+            if (!asked) st = region_curve_state<ModeDynamic>(P, P.texIsFp32 != 0, shape, sub, maxAbs);
         }
     }
     // ---- open tiles: wave-compacted append, section by section (a wave sees one section, two at a range boundary, early items apart) ----
@@ -271,7 +257,7 @@ __global__ __launch_bounds__(256, OMMX_TRIAGE_WAVES) void triage_groups(Classify
     const uint32_t g = threadIdx.x % GROUPS, slot = threadIdx.x / GROUPS;
     const bool coarse = P.useCoarse != 0;
     const bool fastFine = P.filterLinear != 0 && P.mipCount == 1 && !P.noFine && P.altKernel == 0;
-    const bool curveOn = (OMMX_RC_LEVELS & 4) && region_curve_applies(P);
+    const bool curveOn = region_curve_applies(P);
     const uint32_t bits = (uint32_t)P.format, groupBytes = 8u * bits;   // 64 micro-triangles x bits
     for (uint32_t sec = 0; sec < numSections; ++sec) {
         const uint32_t base = queueCtl[kSecBases + sec], tail = queueCtl[kSecTails + sec];
@@ -363,9 +349,6 @@ constexpr uint32_t kDeferredState = 0xFEu;   // s_state code of a micro-triangle
 // The kernel's first argument read again from the kernarg segment (scalar loads through the scalar cache) behind an empty asm the optimizer cannot look through:
 // a phase that starts with it re-loads the few fields it uses instead of the kernel holding every field any phase uses in SGPRs from its first line to its
 // last -- which do not exist: the allocator parks them in VGPR lanes (74 in the instantiation that defers the texel walks) and every use is a v_readlane.
-#ifndef OMMX_FRESH_PARAMS
-#define OMMX_FRESH_PARAMS 1
-#endif
 __device__ __forceinline__ const ClassifyParams* fresh_kernarg_params()
 {
     auto p = __builtin_amdgcn_kernarg_segment_ptr();   // (a pointer into the constant address space; ClassifyParams is the first argument of the kernels that call this)
@@ -394,22 +377,13 @@ __global__ __launch_bounds__(BLOCK, OMMX_CLASSIFY_WAVES) void classify_tiles(Cla
     // from it -- LDS addresses, lane masks, wave indices, a dozen of them -- out of the persistent tile loop and keeps them alive across all phases, i.e. in
     // scratch (round 4: 18 scratch stores in front of the loop, reloads in every phase).  Recomputing them costs one or two instructions each.
     uint32_t tid = threadIdx.x;
-#if OMMX_FRESH_PARAMS
     // (only the instantiation that defers the texel walks: there it takes the last 20 bytes of scratch away, 4.65 -> 4.34 ms on the asset-shaped bake; the
     //  hot instantiation of the metric configuration has no scratch to lose and runs 7.41 -> 7.50 ms with the reloads)
-    constexpr bool kFresh = DEFER || OMMX_FRESH_PARAMS == 2;   // (2: A/B builds, every instantiation)
+    constexpr bool kFresh = DEFER;
     const ClassifyParams* Pp = kFresh ? fresh_kernarg_params() : &Pk;
 #define P (*Pp)
 #define OMMX_FRESH_P() do { if (kFresh) Pp = fresh_kernarg_params(); } while (0)
-#else
-#define P Pk
-#define OMMX_FRESH_P() ((void)0)
-#endif
-#ifndef OMMX_NO_TID_LAUNDER
 #define OMMX_FRESH_TID() do { asm volatile("" : "+v"(tid)); OMMX_FRESH_P(); } while (0)
-#else
-#define OMMX_FRESH_TID() OMMX_FRESH_P()
-#endif
     // DEFER: hand `n` queued micro-triangles (s_queue[0 .. n)) to the generic queue; false = no room, the caller walks them itself.  Block-uniform.
     auto defer_generic = [&](uint32_t n, uint32_t itemWord, uint32_t level) -> bool {
         if (!DEFER || !SLICED || n == 0u) return false;
@@ -521,11 +495,7 @@ __global__ __launch_bounds__(BLOCK, OMMX_CLASSIFY_WAVES) void classify_tiles(Cla
             TexRect r; r.sx = (int)(rec.z & 0xFFFFu); r.sy = (int)(rec.z >> 16); r.ex = (int)(rec.w & 0xFFFFu); r.ey = (int)(rec.w >> 16); r.ok = (rec.x >> 31) != 0u;
             const int ww = r.ex - r.sx + 1, wh = r.ey - r.sy + 1;
             bool windowOk = false;
-#ifdef OMMX_EXP_NO_WINDOW
-            if (false) {
-#else
             if (r.ok && ww <= WIN && wh <= WIN) {
-#endif
                 const DevMip& m0 = P.mips[0];
                 // 64 x 4 thread grid over the window (no integer division by the run-time width): column = lane, one row per wave and pass
                 const int cx = (int)(tid & 63u);
@@ -849,16 +819,12 @@ __global__ __launch_bounds__(BLOCK, OMMX_CLASSIFY_WAVES) void classify_tiles(Cla
 // raster + level-line kernel / nearest vote per texel: fine_state).  Inside classify_tiles one lane walks one box in lockstep with 63 others:
 // neighbouring boxes differ in size by orders of magnitude, two thirds of the walks end at their first mixed texel after a handful of visits
 // and the rest visit every texel under the triangle, so a fifth of the lanes does useful work (profiles/r03_v3_cards_pmc.md).  Here the walks
-// are queue entries and a lane that finishes one takes the next (generic_walks below); every texel of a box is visited at most
-// once, in row-major order, with the serial loop's early exit: same state.  Mip chains, the alternative kernel and degenerate items take the
+// are queue entries that the waves of classify_generic take a chunk at a time (generic_dense below); every texel of a box is visited at most
+// once, with the serial loop's early exit: same state.  Mip chains, the alternative kernel and degenerate items take the
 // serial fine_state().  The state is ORed into the packed word the persistent launch left 0; item mask / known count are folded per wave.
-// (Round 3's form -- 12 visits one lane per walk, then eight lanes per unfinished walk -- took 36.9 ms where this one takes 28.8.)
 // ------------------------------------------------------------------------------------------------
-struct RasterBox { EdgeEq e0, e1, e2; int minx, miny, xend, yend; uint32_t w, cnt; };   // texels [minx, xend) x [miny, yend), row-major index k < cnt
-struct TexelCursor { int x, y; };
-__device__ __forceinline__ TexelCursor cursor_at(const RasterBox& B, uint32_t k) { TexelCursor c; c.x = B.minx + (int)(k % B.w); c.y = B.miny + (int)(k / B.w); return c; }
-__device__ __forceinline__ bool cursor_live(const RasterBox& B, const TexelCursor& c) { return c.y < B.yend; }
-__device__ __forceinline__ void cursor_step(const RasterBox& B, TexelCursor& c) { if (++c.x == B.xend) { c.x = B.minx; ++c.y; } }
+// texels [minx, xend) x [miny, yend), row-major index k < cnt.  (Nothing reads w and cnt any more; without them clang lays out classify_generic differently.)
+struct RasterBox { EdgeEq e0, e1, e2; int minx, miny, xend, yend; uint32_t w, cnt; };
 __device__ __forceinline__ RasterBox raster_box(const DevMip& m, const MicroTri& t, float off)
 {
     // same set-up as raster_micro_triangle (classify_device.h): winding, raster-space vertices, box
@@ -880,13 +846,6 @@ __device__ __forceinline__ RasterBox raster_box(const DevMip& m, const MicroTri&
     const bool ok = cnt64 != 0ull && cnt64 <= 0xFFFFFFF0ull;
     B.w = ok ? (uint32_t)w : 1u; B.cnt = ok ? (uint32_t)cnt64 : 0u; B.xend = ok ? maxx : minx + 1; B.yend = ok ? maxy : miny;
     return B;
-}
-// does texel k of the box (row-major) lie under the (conservative) triangle?  (the cheap half of a visit: a lane skips to its next covered texel in a loop
-// of these, so that the expensive half below runs with every lane that still has one -- half the texels of a box are not under its triangle)
-__device__ __forceinline__ bool texel_under(const RasterBox& B, const TexelCursor& c)
-{
-    const float sx = (float)c.x, sy = (float)c.y;
-    return eval_cons(B.e0, sx, sy) < 0.f && eval_cons(B.e1, sx, sy) < 0.f && eval_cons(B.e2, sx, sy) < 0.f;
 }
 // a wave's classified entries: state ORed into the packed word the persistent launch left 0; item mask / known count with one atomic per item and wave
 // (the entries of a wave mostly share their item)
@@ -914,171 +873,21 @@ __device__ __forceinline__ uint32_t generic_commit(const ClassifyParams& P, cons
     return committed;
 }
 
-// ---- the walks ----
-// A wave that runs 64 walks in lockstep has two thirds of its lanes finished after two visits, waiting for its longest walk.  Here a lane that finishes
-// gets the next queued micro-triangle: a wave pulls chunks of OMMX_GENERIC_CHUNK entries from a cursor next to the queue's count word, and whenever
-// OMMX_GENERIC_REFILL lanes are idle they commit their states together (generic_commit folds the item masks per wave), take the next entries and set them
-// up (micro-triangle, centre vote, raster box) in one round.  Same visits in the same order per walk as the serial loop, with its early exit: same state.
-// Rows are left at the first texel that is not under the triangle after one that was: the texels under the conservative triangle form an interval in
-// every row (each edge function is monotone in x, in fp32 too).
-// KIND 0, the level-line kernel (Linear filter): most cells of a long walk are cheap -- flat (no edge can cross a constant patch: the reference votes by the
-// first texel) and with all four texels on a side the walk has already seen; when only (any vote above, any vote below) counts, such a cell changes nothing.
-// Every lane advances to its next cell that needs work (corner votes: its texels are not all on a seen side; edge tests: it is not flat), a few rounds of
-// fetch + compare, and then the wave does the corner votes and the three edge tests for those cells together.  KIND 1, Nearest: every covered texel votes
-// with its sample.
-#ifndef OMMX_GENERIC_REFILL
-#define OMMX_GENERIC_REFILL 16   // measured on the cards workload: 8 / 16 / 32 = 30.2 / 29.0 / 31.1 ms
-#endif
-#ifndef OMMX_GENERIC_CHUNK
-#define OMMX_GENERIC_CHUNK 1024u
-#endif
-#ifndef OMMX_GENERIC_ADVANCE
-#define OMMX_GENERIC_ADVANCE 4   // rounds of advancing per round of cell work (1 / 4 / 8: 28.6 / 28.8 / 31.2 ms)
-#endif
-template <bool FP32, int KIND, class MD>
-__device__ __forceinline__ void generic_walks(const ClassifyParams& P, const ItemArrays& A, const GenericQueue& G, uint32_t n)
-{
-    const DevMip& m = P.mips[0];
-    const uint32_t lane = threadIdx.x & 63u;
-    const bool countsMatter = P.promotion == 0;
-    const float off = KIND == 0 ? -0.5f : 0.f;
-    unsigned long long* const cursorWord = G.count + 1;
-    uint32_t chunkNext = 0, chunkEnd = 0;   // (wave-uniform) the chunk of the queue this wave works on
-    bool drained = false;                   // (wave-uniform) no entries left in the queue
-    uint32_t classified = 0;                // (wave-uniform) entries this wave has committed: one atomic per wave at the end (count[2], a statistic)
-    bool have = false, result = false;      // this lane: holds an unfinished walk / a finished one that is not committed yet
-    bool rowSeen = false;                   // a texel of the cursor's row was under the triangle
-    uint32_t item = 0, levelWord = 0, above = 0, below = 0;
-    int direct = -1;                        // state of a degenerate item's micro-triangle (serial fine_state), or -1
-    MicroTri t; t.p0 = t.p1 = t.p2 = mk2(0.f, 0.f);
-    RasterBox B = raster_box(m, t, off);
-    TexelCursor c = cursor_at(B, 0u);
-    // to the next texel under the triangle; false: the box is exhausted
-    auto next_covered = [&]() -> bool {
-        while (cursor_live(B, c) && !texel_under(B, c)) { if (rowSeen) { c.x = B.minx; ++c.y; rowSeen = false; } else cursor_step(B, c); }
-        return cursor_live(B, c);
-    };
-    auto step = [&]() { rowSeen = true; cursor_step(B, c); if (c.x == B.minx) rowSeen = false; };   // (c.x == minx: the step wrapped into the next row)
-    for (;;) {
-        const unsigned long long busy = __ballot(have);
-        const uint32_t idle = 64u - (uint32_t)__popcll(busy);
-        if ((!drained && idle >= (uint32_t)OMMX_GENERIC_REFILL) || busy == 0ull) {
-            // ---- commit what is finished, hand out the next entries ----
-            classified += generic_commit(P, A, result, item, levelWord & 0xFFFFFFu, direct >= 0 ? direct : state_from_coverage(P, above, below));
-            result = false;
-            if (drained) break;   // (busy == 0)
-            if (chunkNext == chunkEnd) {
-                unsigned long long start = 0;
-                if (lane == 0u) start = atomicAdd(cursorWord, (unsigned long long)OMMX_GENERIC_CHUNK);
-                start = (unsigned long long)__shfl((long long)start, 0);
-                if (start >= (unsigned long long)n) drained = true;
-                else { chunkNext = (uint32_t)start; chunkEnd = start + OMMX_GENERIC_CHUNK < (unsigned long long)n ? (uint32_t)start + OMMX_GENERIC_CHUNK : n; }
-            }
-            if (!drained) {
-                const uint32_t avail = chunkEnd - chunkNext, take = idle < avail ? idle : avail;
-                const uint32_t rank = (uint32_t)__popcll(~busy & ((1ull << lane) - 1ull));
-                bool get = !have && rank < take;
-                uint2 ent = get ? G.entries[chunkNext + rank] : make_uint2(0u, 0u);
-                chunkNext += take;
-                if (ent.x == 0xFFFFFFFFu) get = false;   // (null entry: the inside part of a reservation that did not fit)
-                const bool degenerate = get && ((ent.x >> 30) & 1u) != 0u;
-                if (get) { item = ent.x & 0x3FFFFFFFu; levelWord = ent.y; above = 0; below = 0; direct = -1; }
-                if (__ballot(degenerate) != 0ull) {   // (rare: degenerate items take the serial form)
-                    if (degenerate) { direct = fine_state<FP32, MD>(P, micro_triangle(A.uv + 6ull * item, levelWord & 0xFFFFFFu, levelWord >> 24), true, no_window()); result = true; get = false; }
-                }
-                if (get) {
-                    t = micro_triangle(A.uv + 6ull * item, levelWord & 0xFFFFFFu, levelWord >> 24);
-                    if (KIND == 0) vote(P.cutoff < bilinear<FP32, MD, true>(P, m, t.p0, no_window()), above, below);
-                    B = raster_box(m, t, off);
-                    c = cursor_at(B, 0u); rowSeen = false;
-                    have = true;
-                }
-            }
-            continue;
-        }
-        if (KIND == 1) {   // ---- Nearest: one visit ----
-            if (have) {
-                if (!next_covered()) { have = false; result = true; }
-                else {
-                    nearest_texel<FP32, MD>(P, m, c.x, c.y, above, below, no_window());
-                    step();
-                    if (!countsMatter && above != 0 && below != 0) { have = false; result = true; }
-                }
-            }
-            continue;
-        }
-        // ---- level line: every walking lane advances to its next cell that needs work ----
-        bool cell = false, corners = false;
-        float ha = 0.f, hb = 0.f, hc = 0.f, hd = 0.f, pfx = 0.f, pfy = 0.f;
-        uint32_t obits = 0;
-        for (int round = 0; round < OMMX_GENERIC_ADVANCE; ++round) {
-            if (have && !cell) {
-                if (!next_covered()) { have = false; result = true; }
-                else {
-                    pfx = (float)c.x + 0.5f; pfy = (float)c.y + 0.5f;
-                    float gx, gy, gz, gw;   // 00, 01, 11, 10
-                    fetch_cell<FP32, MD, true>(P, m, MD::pow2(P), c.x, c.y, no_window(), gx, gy, gz, gw);
-                    const bool o0 = P.cutoff < gx, o1 = P.cutoff < gy, o2 = P.cutoff < gz, o3 = P.cutoff < gw;
-                    hb = gw - gx; hc = gy - gx; hd = gx + gz - gy - gw; ha = gx - P.cutoff;
-                    const bool flat = near_zero(hb, 1e-6f) & near_zero(hc, 1e-6f) & near_zero(hd, 1e-6f);
-                    const bool seen = !countsMatter & (o0 == o1) & (o1 == o2) & (o2 == o3) & (o0 ? above != 0 : below != 0);
-                    // a cell that is not flat needs its three edge tests -- unless the level curve provably stays out of it (cell_excluded, classify_device.h: audited
-                    // by the oracle next to every edge test): most cells of a long walk are such cells, all four texels on a side the walk has seen, in the smooth
-                    // flank of an alpha edge.  They are passed like the flat ones, so the edge tests below run for the cells that need them.
-                    bool edgesNeeded = !flat;
-#ifndef OMMX_NO_CELL_EXCLUSION
-                    if (edgesNeeded) {
-                        const V2 q0 = mk2(m.fw * t.p0.x - pfx, m.fh * t.p0.y - pfy), q1 = mk2(m.fw * t.p1.x - pfx, m.fh * t.p1.y - pfy), q2 = mk2(m.fw * t.p2.x - pfx, m.fh * t.p2.y - pfy);
-                        edgesNeeded = !cell_excluded(q0, q1, q2, ha, hb, hc, hd);
-                    }
-#endif
-                    corners = !seen;
-                    cell = !seen | edgesNeeded;
-                    obits = (o0 ? 1u : 0u) | (o1 ? 2u : 0u) | (o2 ? 4u : 0u) | (o3 ? 8u : 0u) | (flat ? 16u : 0u) | (edgesNeeded ? 32u : 0u);
-                    step();
-                }
-            }
-            if (__ballot(have && !cell) == 0ull || __popcll(__ballot(cell)) >= 48) break;
-        }
-        // ---- the cells that need work: bake_kernels_cpu.h:241-399 ----
-        if (cell) {
-            const bool o0 = (obits & 1u) != 0u, o1 = (obits & 2u) != 0u, o2 = (obits & 4u) != 0u, o3 = (obits & 8u) != 0u, flat = (obits & 16u) != 0u, edgesNeeded = (obits & 32u) != 0u;
-            bool both = false;
-            if (corners) {
-                const float ipx = pfx * m.rw, ipy = pfy * m.rh;
-                const bool in0 = point_in_triangle_flat(t, ipx, ipy), in1 = point_in_triangle_flat(t, ipx, ipy + m.rh);
-                const bool in2 = point_in_triangle_flat(t, ipx + m.rw, ipy + m.rh), in3 = point_in_triangle_flat(t, ipx + m.rw, ipy);
-                const bool isO = (in0 & o0) | (in1 & o1) | (in2 & o2) | (in3 & o3), isT = (in0 & !o0) | (in1 & !o1) | (in2 & !o2) | (in3 & !o3);
-                above += isO ? 1u : 0u; below += isT ? 1u : 0u;
-                both = isO & isT;
-                if (flat & !both) vote(o0, above, below);
-            }
-            if (edgesNeeded & !both & (countsMatter | !(above != 0 && below != 0))) {
-                const V2 q0 = mk2(m.fw * t.p0.x - pfx, m.fh * t.p0.y - pfy), q1 = mk2(m.fw * t.p1.x - pfx, m.fh * t.p1.y - pfy), q2 = mk2(m.fw * t.p2.x - pfx, m.fh * t.p2.y - pfy);
-                const bool x0 = edge_crosses_level_curve(q0, q1, ha, hb, hc, hd), x1 = edge_crosses_level_curve(q1, q2, ha, hb, hc, hd), x2 = edge_crosses_level_curve(q2, q0, ha, hb, hc, hd);
-                if (x0 | x1 | x2) { above += 1; below += 1; }
-            }
-            if (!countsMatter && above != 0 && below != 0) { have = false; result = true; }
-        }
-    }
-    if (lane == 0u && classified) atomicAdd(G.count + 2, (unsigned long long)classified);
-}
-
-
-// ---- the dense form of the walks (round 5) ----
-// The walks above keep one lane per micro-triangle for everything, so a wave's instructions are issued for a third of its lanes: the skip to the next covered
-// texel runs for the one lane at the start of a wide row, the corner votes for the dozen lanes whose cell is not on a seen side, the edge tests for the cells
-// that need them.  Here a lane OWNS a micro-triangle (its record lies in the wave's LDS: edge functions, box, vertices, cursor, vote counters) and WORKS on
-// whatever visit is next: every round the active owners offer OMMX_GENERIC_QUOTA texels of their boxes each, the wave tests them 64 at a time (texel_under's
-// three edge functions), the covered ones go into a ring of visits; whenever the ring holds 64, the wave fetches 64 cells and does their votes; cells that need
-// their edge tests go into a second ring and are done 64 at a time as well.  The votes of a micro-triangle are sums (bake_kernels_cpu.h:241-399 adds to two
-// counters per texel; GetStateFromCoverage reads the sums), so the order in which its texels are visited does not matter, and when only (any above, any below)
-// counts -- every promotion but Nearest -- the visits of a micro-triangle that is already mixed are dropped wherever they are: the serial loop's early exit.
+// ---- the walks, in dense form (round 5) ----
+// Walks that keep one lane per micro-triangle for everything (rounds 3-4, profiles/EXPERIMENTS.md) have a wave's instructions issued for a third of its lanes:
+// the skip to the next covered texel runs for the one lane at the start of a wide row, the corner votes for the dozen lanes whose cell is not on a seen side,
+// the edge tests for the cells that need them.  Here a lane OWNS a micro-triangle (its record lies in the wave's LDS: edge functions, box, vertices, cursor,
+// vote counters) and WORKS on whatever visit is next: every round the active owners offer OMMX_GENERIC_QUOTA texels of their boxes each, the wave tests them
+// 64 at a time (the three conservative edge functions), the covered ones go into a ring of visits; whenever the ring holds 64, the wave fetches 64 cells and
+// does their votes; cells that need their edge tests go into a second ring and are done 64 at a time as well.  The votes of a micro-triangle are sums
+// (bake_kernels_cpu.h:241-399 adds to two counters per texel; GetStateFromCoverage reads the sums), so the order in which its texels are visited does not
+// matter, and when only (any above, any below) counts -- every promotion but Nearest -- the visits of a micro-triangle that is already mixed are dropped
+// wherever they are: the serial loop's early exit.
 // An owner finishes when its box is exhausted (or it is mixed) AND none of its visits is in a ring (a counter per owner), so a record is never reused under a
 // visit.  No workgroup barrier: the structures are per wave, a wave's LDS operations execute in order.
-#ifndef OMMX_GENERIC_DENSE
-#define OMMX_GENERIC_DENSE 1
-#endif
+// Linear filter (KIND 0), the level-line kernel: most cells of a long walk are cheap -- flat (no edge can cross a constant patch: the reference votes by the
+// first texel) and with all four texels on a side the walk has already seen; when only (any vote above, any vote below) counts, such a cell changes nothing.
+// Nearest (KIND 1): every covered texel votes with its sample.
 #ifndef OMMX_GENERIC_QUOTA_LOG2
 #define OMMX_GENERIC_QUOTA_LOG2 2   // texels an owner offers per round: 2 / 4 / 8 = 19.3 / 18.2 / 19.5 ms on the cards workload
 #endif
@@ -1111,12 +920,6 @@ __device__ __forceinline__ void generic_dense(const ClassifyParams& P, const Ite
     bool drained = false;
     uint32_t classified = 0;
     uint32_t cHead = 0, cCount = 0, eHead = 0, eCount = 0;   // (wave-uniform) the two rings
-#ifdef OMMX_GD_STATS
-    uint32_t st[12] = { 0 };
-#define GD_STAT(i, v) st[i] += (v)
-#else
-#define GD_STAT(i, v) do { } while (0)
-#endif
     // the owner's side of this lane
     bool have = false, result = false;
     uint32_t item = 0, levelWord = 0, fAbove = 0, fBelow = 0;
@@ -1136,7 +939,6 @@ __device__ __forceinline__ void generic_dense(const ClassifyParams& P, const Ite
         const uint2 ab = on ? make_uint2(r[9], r[10]) : make_uint2(0u, 0u);
         const uint32_t above = ab.x, below = ab.y;
         const bool live = on && (countsMatter || !(above != 0 && below != 0));
-        GD_STAT(4, 1u); GD_STAT(5, (uint32_t)__popcll(__ballot(live)));
         uint32_t da = 0, db = 0;
         bool toEdge = false;
         float ha = 0.f, hb = 0.f, hc = 0.f, hd = 0.f;
@@ -1153,13 +955,14 @@ __device__ __forceinline__ void generic_dense(const ClassifyParams& P, const Ite
                 hb = gw - gx; hc = gy - gx; hd = gx + gz - gy - gw; ha = gx - P.cutoff;
                 const bool flat = near_zero(hb, 1e-6f) & near_zero(hc, 1e-6f) & near_zero(hd, 1e-6f);
                 const bool seen = !countsMatter & (o0 == o1) & (o1 == o2) & (o2 == o3) & (o0 ? above != 0 : below != 0);
+                // a cell that is not flat needs its three edge tests -- unless the level curve provably stays out of it (cell_excluded, classify_device.h: audited
+                // by the oracle next to every edge test): most cells of a long walk are such cells, all four texels on a side the walk has seen, in the smooth
+                // flank of an alpha edge.  They are passed like the flat ones, so the edge ring holds the cells that need their tests.
                 bool edgesNeeded = !flat;
-#ifndef OMMX_NO_CELL_EXCLUSION
                 if (edgesNeeded) {
                     const V2 q0 = mk2(m.fw * t.p0.x - pfx, m.fh * t.p0.y - pfy), q1 = mk2(m.fw * t.p1.x - pfx, m.fh * t.p1.y - pfy), q2 = mk2(m.fw * t.p2.x - pfx, m.fh * t.p2.y - pfy);
                     edgesNeeded = !cell_excluded(q0, q1, q2, ha, hb, hc, hd);
                 }
-#endif
                 bool both = false;
                 if (!seen) {
                     const float ipx = pfx * m.rw, ipy = pfy * m.rh;
@@ -1180,7 +983,7 @@ __device__ __forceinline__ void generic_dense(const ClassifyParams& P, const Ite
             const uint32_t e = (eHead + eCount + (uint32_t)__popcll(em & below_me)) & MASK;
             eRing[e] = word;   // (the cell is fetched again there: 16 bytes of ring per entry cost a wave per SIMD)
         }
-        eCount += (uint32_t)__popcll(em); GD_STAT(6, (uint32_t)__popcll(em));
+        eCount += (uint32_t)__popcll(em);
         if (on && !toEdge) atomicSub(r + 11, 1u);
         OMMX_WAVE_SYNC();
     };
@@ -1192,7 +995,6 @@ __device__ __forceinline__ void generic_dense(const ClassifyParams& P, const Ite
         eHead = (eHead + cnt) & MASK; eCount -= cnt;
         uint32_t* const r = rec + slot * GD_REC;
         const uint2 ab = on ? make_uint2(r[9], r[10]) : make_uint2(0u, 0u);
-        GD_STAT(7, 1u); GD_STAT(8, (uint32_t)__popcll(__ballot(on && (countsMatter || !(ab.x != 0 && ab.y != 0)))));
         if (on && (countsMatter || !(ab.x != 0 && ab.y != 0))) {
             const uint4 v0 = *(const uint4*)(r + 12), v1 = *(const uint4*)(r + 16);
             const int x = (int)v1.z + (int)((word >> 6) & 8191u), y = (int)v1.w + (int)(word >> 19);
@@ -1247,7 +1049,6 @@ __device__ __forceinline__ void generic_dense(const ClassifyParams& P, const Ite
                 if (__ballot(degenerate) != 0ull) {   // (rare: degenerate items take the serial form)
                     if (degenerate) { direct = fine_state<FP32, MD>(P, micro_triangle(A.uv + 6ull * item, levelWord & 0xFFFFFFu, levelWord >> 24), true, no_window()); result = true; get = false; }
                 }
-                GD_STAT(9, 1u); GD_STAT(10, (uint32_t)__popcll(__ballot(get)));
                 if (get) {
                     const MicroTri t = micro_triangle(A.uv + 6ull * item, levelWord & 0xFFFFFFu, levelWord >> 24);
                     uint32_t a0 = 0, b0 = 0;
@@ -1273,7 +1074,6 @@ __device__ __forceinline__ void generic_dense(const ClassifyParams& P, const Ite
         const unsigned long long emask = __ballot(active);
         const uint32_t nAct = (uint32_t)__popcll(emask);
         if (nAct == 0u) {   // nothing to enumerate: what the waiting owners wait for is in the rings
-            GD_STAT(11, 1u);
             while (cCount) { cell_stage(cCount < 64u ? cCount : 64u); if (eCount >= 64u) edge_stage(64u); }
             while (eCount) edge_stage(eCount < 64u ? eCount : 64u);
             continue;
@@ -1285,7 +1085,6 @@ __device__ __forceinline__ void generic_dense(const ClassifyParams& P, const Ite
         }
         OMMX_WAVE_SYNC();
         const uint32_t passes = (nAct * Q + 63u) >> 6;
-        GD_STAT(0, 1u); GD_STAT(1, passes);
         for (uint32_t p = 0; p < passes; ++p) {
             const uint32_t rk = p * (64u >> OMMX_GENERIC_QUOTA_LOG2) + (lane >> OMMX_GENERIC_QUOTA_LOG2);
             const bool valid = rk < nAct;
@@ -1311,7 +1110,6 @@ __device__ __forceinline__ void generic_dense(const ClassifyParams& P, const Ite
                 }
             }
             const unsigned long long cm = __ballot(covered);
-            GD_STAT(2, (uint32_t)__popcll(__ballot(valid && y < byend))); GD_STAT(3, (uint32_t)__popcll(cm));
             if (covered) {
                 const uint32_t c = (cHead + cCount + (uint32_t)__popcll(cm & below_me)) & MASK;
                 cRing[c] = slot | ((uint32_t)(x - bminx) << 6) | ((uint32_t)(y - bminy) << 19);
@@ -1329,9 +1127,6 @@ __device__ __forceinline__ void generic_dense(const ClassifyParams& P, const Ite
         OMMX_WAVE_SYNC();
     }
     if (lane == 0u && classified) atomicAdd(G.count + 2, (unsigned long long)classified);
-#ifdef OMMX_GD_STATS
-    if (lane == 0u) for (int i = 0; i < 12; ++i) atomicAdd(G.count + 8 + i, (unsigned long long)st[i]);
-#endif
 }
 
 #ifndef OMMX_GENERIC_WAVES
@@ -1343,12 +1138,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OMMX_GENERI
     const uint32_t n = *G.count < (unsigned long long)G.capacity ? (uint32_t)*G.count : G.capacity;
     const uint32_t lane = threadIdx.x & 63u, wave = (blockIdx.x * 256u + threadIdx.x) >> 6, waves = (gridDim.x * 256u) >> 6;
     if (P.mipCount == 1 && !(P.filterLinear && P.altKernel)) {
-#if OMMX_GENERIC_DENSE
         __shared__ __attribute__((aligned(16))) uint32_t s_dense[4][GD_WAVE_DWORDS];
         if (P.filterLinear) generic_dense<FP32, 0, MD>(P, A, G, n, s_dense[threadIdx.x >> 6]); else generic_dense<FP32, 1, MD>(P, A, G, n, s_dense[threadIdx.x >> 6]);
-#else
-        if (P.filterLinear) generic_walks<FP32, 0, MD>(P, A, G, n); else generic_walks<FP32, 1, MD>(P, A, G, n);
-#endif
         return;
     }
     uint32_t classified = 0;
@@ -1403,11 +1194,8 @@ void classify_plan(const uint32_t first[kNumLevels], const uint32_t count[kNumLe
     TileSections& S = plan->ranges; S.n = K;
     // (round 4: the classification of the metric workload is now faster than the PCIe copy of its result, so the copy engine is the critical pipe and what
     //  counts is how early its FIRST piece is ready: the first ranges are small -- a quarter, a half, three quarters of the others --, the rest equal)
-#ifndef OMMX_STREAM_RAMP
-#define OMMX_STREAM_RAMP 1
-#endif
     double wsum = 0.0, wacc = 0.0;
-    auto weight = [&](uint32_t k) { return (OMMX_STREAM_RAMP && K >= 8u && k < 3u) ? 0.25 * (double)(k + 1u) : 1.0; };
+    auto weight = [&](uint32_t k) { return (K >= 8u && k < 3u) ? 0.25 * (double)(k + 1u) : 1.0; };
     for (uint32_t k = 0; k < K; ++k) wsum += weight(k);
     for (uint32_t k = 1; k <= K; ++k) {
         wacc += weight(k - 1u);
@@ -1527,7 +1315,7 @@ static void launch_classify_md(const ClassifyParams& P, const ItemArrays& A, con
     // ---- deferred generic pass: the micro-triangles of several texels that the persistent launches queued instead of walking ----
     if (deferred) {
         if (chunks.markGeneric) chunks.markGeneric(chunks.user);
-        hipLaunchKernelGGL((classify_generic<FP32, MD>), dim3(numCUs * (OMMX_GENERIC_DENSE ? (uint32_t)OMMX_GENERIC_WAVES : 8u)), dim3(256), 0, stream, P, A, chunks.generic);
+        hipLaunchKernelGGL((classify_generic<FP32, MD>), dim3(numCUs * (uint32_t)OMMX_GENERIC_WAVES), dim3(256), 0, stream, P, A, chunks.generic);
     }
     for (uint32_t k = 0; k < K; ++k) {
         if (chunks.after) {   // the work items of this range, as segments of the per-level active lists, in the order of the final result

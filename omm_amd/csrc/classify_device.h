@@ -220,7 +220,6 @@ __device__ __forceinline__ void fetch_cell(const ClassifyParams& P, const DevMip
 {
     const int x0 = tex_coord(MD::addr(P), pow2, px, m.w, m.log2w), y0 = tex_coord(MD::addr(P), pow2, py, m.h, m.log2h);
     const int x1 = tex_coord(MD::addr(P), pow2, px + 1, m.w, m.log2w), y1 = tex_coord(MD::addr(P), pow2, py + 1, m.h, m.log2h);
-#ifndef OMMX_NO_CELL_FETCH
     {
         const uint32_t wx = (uint32_t)(x0 - W.sx), wy = (uint32_t)(y0 - W.sy);
         if (wx + 1u < (uint32_t)W.w && wy + 1u < (uint32_t)W.h && x1 == x0 + 1 && y1 == y0 + 1 && m.texels == W.base) {
@@ -229,7 +228,6 @@ __device__ __forceinline__ void fetch_cell(const ClassifyParams& P, const DevMip
             return;
         }
     }
-#endif
     // outside the window: the two texels of a row are neighbours in memory unless the address mode folds the cell at a seam -- one load per row
     // (the deferred generic pass does nothing but such fetches: classify_generic 28.6 -> 27.8 ms)
     // (PAIRS: only where the caller asks for it -- in the persistent kernel the extra path costs more registers than the rare fetch outside the window saves)
@@ -267,7 +265,6 @@ __device__ __forceinline__ uint32_t load_sat(const DevMip& m, int x, int y, cons
 // texture_impl.h:110-125
 __device__ __forceinline__ uint32_t sat_sum(const DevMip& m, int sx, int sy, int ex, int ey, const TexWindow& W)
 {
-#ifndef OMMX_NO_CELL_FETCH
     {   // all four corners in the LDS window: its entry (i, j) is SAT(W.sx - 1 + i, W.sy - 1 + j) with the zero row / column for -1
         // already stored, so the "sx > 0 / sy > 0" selections below are table look-ups
         const uint32_t i0 = (uint32_t)(sx - W.sx), j0 = (uint32_t)(sy - W.sy), i1 = (uint32_t)(ex - W.sx + 1), j1 = (uint32_t)(ey - W.sy + 1);
@@ -275,7 +272,6 @@ __device__ __forceinline__ uint32_t sat_sum(const DevMip& m, int sx, int sy, int
         if (W.w != 0 && i0 <= (uint32_t)W.w && i1 <= (uint32_t)W.w && j0 <= (uint32_t)W.h && j1 <= (uint32_t)W.h)
             return W.sat[i1 + j1 * pitch] + W.sat[i0 + j0 * pitch] - W.sat[i1 + j0 * pitch] - W.sat[i0 + j1 * pitch];
     }
-#endif
     const uint32_t A = (sx > 0 && sy > 0) ? load_sat(m, sx - 1, sy - 1, W) : 0u;
     const uint32_t B = sy > 0 ? load_sat(m, ex, sy - 1, W) : 0u;
     const uint32_t C = sx > 0 ? load_sat(m, sx - 1, ey, W) : 0u;
@@ -362,12 +358,10 @@ __device__ __forceinline__ bool point_on_edge(V2 a0, V2 a1, float x, float y)
 {
     const float ux = x - a0.x, uy = y - a0.y;
     const float dx = a1.x - a0.x, dy = a1.y - a0.y;
-#ifndef OMMX_NO_EDGE_PREFILTER
     const float w = ux * dx + uy * dy, l2 = dx * dx + dy * dy;
     const float M = __builtin_fabsf(dx) + __builtin_fabsf(dy), U = __builtin_fabsf(ux) + __builtin_fabsf(uy);
     const float T = M * (1e-4f + 1e-5f * (U + M));
     if (w - l2 > T || -w > T) return false;
-#endif
     return near_zero(vlen(ux, uy) + vlen(x - a1.x, y - a1.y) - vlen(dx, dy), 1e-5f);
 }
 
@@ -387,15 +381,11 @@ struct RootFilter { float lo, hi; bool on; };
 __device__ __forceinline__ RootFilter root_filter(V2 a0, V2 a1) // a0.x <= a1.x
 {
     RootFilter f;
-#ifndef OMMX_NO_ROOT_FILTER
     const float M = __builtin_fabsf(a1.x - a0.x) + __builtin_fabsf(a1.y - a0.y);
     f.on = M <= 2.f;
     float lo = a0.x - 5e-3f; lo = lo > 0.f ? lo : 0.f;
     float hi = a1.x + 5e-3f; hi = hi < 1.f ? hi : 1.f;
     f.lo = lo - 1e-3f; f.hi = hi + 1e-3f;
-#else
-    f.on = false; f.lo = f.hi = 0.f;
-#endif
     return f;
 }
 // true when RN(n / c) is provably outside the acceptance interval
@@ -551,13 +541,9 @@ __device__ __forceinline__ void level_line_texel(const ClassifyParams& P, const 
         // edge vectors out of the raster loops (LICM keeps ~27 more loop-invariant VGPRs live otherwise: 121 VGPRs = 4 waves/SIMD,
         // or 100+ bytes/lane of HBM-backed scratch when bounded).  With it the kernel needs 75 VGPRs, no scratch, 6 waves/SIMD
         // (68.7 -> 59.8 ms on the bench workload).  Values are unchanged -- the same fp32 expressions are evaluated per texel.
-#ifndef OMMX_NO_LAUNDER
         MicroTri t = tIn;
         asm volatile("" : "+v"(t.p0.x), "+v"(t.p0.y), "+v"(t.p1.x), "+v"(t.p1.y), "+v"(t.p2.x), "+v"(t.p2.y));
         t.p0p2 = mk2(t.p0.x - t.p2.x, t.p0.y - t.p2.y); t.p1p0 = mk2(t.p1.x - t.p0.x, t.p1.y - t.p0.y); t.p2p1 = mk2(t.p2.x - t.p1.x, t.p2.y - t.p1.y);
-#else
-        const MicroTri& t = tIn;
-#endif
         // (ipx is never a zero, so the reference's "+ 0.f" on the unchanged coordinate of each corner is the identity)
         const bool in0 = point_in_triangle_flat(t, ipx, ipy);
         const bool in1 = point_in_triangle_flat(t, ipx, ipy + m.rh);
@@ -585,12 +571,8 @@ __device__ __forceinline__ void level_line_texel(const ClassifyParams& P, const 
         if (edge_crosses_level_curve(q0, q1, ha, b, c, d)) { above += 1; below += 1; }
         return;
     }
-#ifndef OMMX_NO_LAUNDER
     MicroTri t = tIn;
     asm volatile("" : "+v"(t.p0.x), "+v"(t.p0.y), "+v"(t.p1.x), "+v"(t.p1.y), "+v"(t.p2.x), "+v"(t.p2.y));
-#else
-    const MicroTri& t = tIn;
-#endif
     const V2 q0 = mk2(m.fw * t.p0.x - pfx, m.fh * t.p0.y - pfy);
     const V2 q1 = mk2(m.fw * t.p1.x - pfx, m.fh * t.p1.y - pfy);
     const V2 q2 = mk2(m.fw * t.p2.x - pfx, m.fh * t.p2.y - pfy);
@@ -666,9 +648,6 @@ __device__ __forceinline__ void raster_micro_triangle(const ClassifyParams& P, c
     const float hix = std_max(std_max(a.x, b.x), c.x), hiy = std_max(std_max(a.y, b.y), c.y);
     const int minx = cvt_trunc_x86(__builtin_floorf(lox)), miny = cvt_trunc_x86(__builtin_floorf(loy));
     const int maxx = cvt_trunc_x86(__builtin_ceilf(hix)), maxy = cvt_trunc_x86(__builtin_ceilf(hiy));
-#ifdef OMMX_NO_LAUNDER
-    const EdgeEq e0 = edge_eq(a, b), e1 = edge_eq(b, c), e2 = edge_eq(c, a);
-#endif
     // Only the Nearest promotion looks at the counts (bake_kernels_cpu.h:38,49); for the forced promotions the state is
     // final as soon as both counters are non-zero, so the remaining texels cannot change the result.
     const bool countsMatter = P.promotion == 0;
@@ -676,7 +655,6 @@ __device__ __forceinline__ void raster_micro_triangle(const ClassifyParams& P, c
         bool wasInside = false;
         for (int x = minx; x < maxx; ++x) {
             const float sx = (float)x, sy = (float)y;
-#ifndef OMMX_NO_LAUNDER
             // edge equations are re-derived per texel from the (opaque) vertices instead of living in 15 VGPRs across both loops
             // -- same expressions, same values; see the register-pressure note in level_line_texel()
             V2 t0 = t.p0, t1 = t.p1, t2 = t.p2;
@@ -686,8 +664,7 @@ __device__ __forceinline__ void raster_micro_triangle(const ClassifyParams& P, c
             V2 lc = mk2(t2.x * m.fw + off, t2.y * m.fh + off);
             if (!ccw) { V2 sw = la; la = lc; lc = sw; }
             const EdgeEq e0 = edge_eq(la, lb), e1 = edge_eq(lb, lc), e2 = edge_eq(lc, la);
-#endif
-        const bool inside = eval_cons(e0, sx, sy) < 0.f && eval_cons(e1, sx, sy) < 0.f && eval_cons(e2, sx, sy) < 0.f;
+            const bool inside = eval_cons(e0, sx, sy) < 0.f && eval_cons(e1, sx, sy) < 0.f && eval_cons(e2, sx, sy) < 0.f;
             if (inside) {
                 if (KIND == 0) level_line_texel<FP32, false, MD>(P, m, t, x, y, above, below, W);
                 else if (KIND == 1) nearest_texel<FP32, MD>(P, m, x, y, above, below, W);
@@ -901,12 +878,6 @@ __device__ __forceinline__ int region_curve_state(const ClassifyParams& P, bool 
 {
     return region_curve_state_impl(rc_tex<MD>(P, fp32), sh, sub.lo.x, sub.lo.y, sub.hi.x, sub.hi.y, maxAbs);
 }
-// the same as a real call: inside the persistent classify_tiles kernel the test runs once per 64-group in ONE wave of the tile's set-up phase, and inlined it
-// costs the whole kernel registers (25 -> 49 spilled VGPRs); as a callee it has an allocation of its own
-__device__ __attribute__((noinline)) int region_curve_state_call(RcTex T, RcShape sh, float lox, float loy, float hix, float hiy, float maxAbs)
-{
-    return region_curve_state_impl(T, sh, lox, loy, hix, hiy, maxAbs);
-}
 
 // ---- fine pass of a micro-triangle whose conservative raster covers ONE texel of mip 0 (Linear filter, non-degenerate item) ----
 // At the bench configuration 95 % of the micro-triangles that reach the level-line pass are far smaller than a texel (level 8 on an
@@ -980,9 +951,6 @@ __device__ __forceinline__ int fine_single_texel(const ClassifyParams& P, const 
         // one inside (rc_corners_far, region_curve.h: audited on every cell visit of the oracle's level-line kernel) -- the four tests, 100 of this pass's 460
         // vector instructions, run only in waves where a lane is near a corner.
         bool isO = false, isT = false;
-#ifdef OMMX_EXP_SKIP_ALL_CORNERS   // (timing experiment: wrong results)
-        const bool nearCorner = false;
-#elif !defined(OMMX_NO_CORNER_SKIP)
         bool nearCorner = true;
         if (shape[2] != 0u) {   // (wave-uniform: the chunk's work item has the corner bound)
             // the vertices in the cell's coordinates, as the level-line kernel forms them (bake_kernels_cpu.h:378-379): their box is rc_corners_far()'s frame
@@ -991,9 +959,6 @@ __device__ __forceinline__ int fine_single_texel(const ClassifyParams& P, const 
             nearCorner = !rc_corners_far(&sh, __builtin_fminf(__builtin_fminf(r0x, r1x), r2x), __builtin_fmaxf(__builtin_fmaxf(r0x, r1x), r2x),
                                          __builtin_fminf(__builtin_fminf(r0y, r1y), r2y), __builtin_fmaxf(__builtin_fmaxf(r0y, r1y), r2y));
         }
-#else
-        const bool nearCorner = true;   // (A/B builds: the four tests for every micro-triangle, as in rounds 1 - 5)
-#endif
         if (__any(nearCorner)) {   // (wave-uniform branch; the tests themselves stay straight-line code)
             // (ipx is never a zero, so the reference's "+ 0.f" on the unchanged coordinate of each corner is the identity)
             const bool in0 = point_in_triangle_flat(t, ipx, ipy);

@@ -458,49 +458,6 @@ inline uint32_t f2u(float f) { return (uint32_t)_mm_cvttss_si64(_mm_set_ss(f)); 
 
 struct HostTri { float p[6]; };
 
-float half_to_float(uint16_t h) // glm::unpackHalf2x16 element
-{
-    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16;
-    uint32_t e = (h >> 10) & 0x1f, m = h & 0x3ffu;
-    uint32_t bits;
-    if (e == 0) {
-        if (m == 0) bits = sign;
-        else { e = 1; while (!(m & 0x400u)) { m <<= 1; e--; } m &= 0x3ffu; bits = sign | ((e + 112u) << 23) | (m << 13); }
-    } else if (e == 31) bits = sign | 0x7f800000u | (m << 13);
-    else bits = sign | ((e + 112u) << 23) | (m << 13);
-    float f; memcpy(&f, &bits, 4); return f;
-}
-
-// util/geometry.h:191-239 + bake_cpu_impl.cpp:579-587
-HostTri fetch_triangle(const ommCpuBakeInputDesc& d, uint32_t prim)
-{
-    uint32_t stride = d.texCoordStrideInBytes;
-    if (stride == 0) stride = d.texCoordFormat == ommTexCoordFormat_UV32_FLOAT ? 8u : 4u;
-    uint32_t idx[3];
-    const size_t o = 3ull * prim;
-    for (int k = 0; k < 3; ++k) {
-        if (d.indexFormat == ommIndexFormat_UINT_8) idx[k] = ((const uint8_t*)d.indexBuffer)[o + k];
-        else if (d.indexFormat == ommIndexFormat_UINT_16) idx[k] = ((const uint16_t*)d.indexBuffer)[o + k];
-        else idx[k] = ((const uint32_t*)d.indexBuffer)[o + k];
-    }
-    HostTri t;
-    for (int k = 0; k < 3; ++k) {
-        const uint8_t* base = (const uint8_t*)d.texCoords + (size_t)stride * idx[k];
-        if (d.texCoordFormat == ommTexCoordFormat_UV32_FLOAT) { memcpy(&t.p[2 * k], base, 8); }
-        else {
-            uint32_t v; memcpy(&v, base, 4);
-            if (d.texCoordFormat == ommTexCoordFormat_UV16_UNORM) {
-                t.p[2 * k] = (float)(v & 0xffffu) * 1.5259021896696421759314870504694e-5f;
-                t.p[2 * k + 1] = (float)(v >> 16) * 1.5259021896696421759314870504694e-5f;
-            } else if (d.texCoordFormat == ommTexCoordFormat_UV16_FLOAT) {
-                t.p[2 * k] = half_to_float((uint16_t)(v & 0xffffu)); t.p[2 * k + 1] = half_to_float((uint16_t)(v >> 16));
-            } else { t.p[2 * k] = 0; t.p[2 * k + 1] = 0; }
-        }
-    }
-    return t;
-}
-
-bool tri_invalid(const HostTri& t) { for (float v : t.p) if (std::isnan(v) || std::isinf(v)) return true; return false; }
 bool tri_degenerate(const HostTri& t) // util/geometry.h:44-47
 {
     const float* p = t.p;
@@ -1166,11 +1123,7 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
     const size_t spanBytes = (size_t)((const uint8_t*)(dFine + fineSlots.size()) - (const uint8_t*)dArrayHist);
     // (into the arena's pinned block when there is one: three copies queued, ONE wait -- into pageable memory each copy is a wait of its own)
     uint32_t hostCtlLocal[kClassifyCtlWords];
-#ifdef OMMX_GD_STATS
-    unsigned long long genericLocal[20] = { 0 };
-#else
-    unsigned long long genericLocal[3] = { 0, 0, 0 };
-#endif   // reservations (incl. null padding), the pass's cursor, micro-triangles it classified
+    unsigned long long genericLocal[3] = { 0, 0, 0 };   // reservations (incl. null padding), the pass's cursor, micro-triangles it classified
     const size_t spanAt = 1024, ctlAt = spanAt + pad256(spanBytes), genAt = ctlAt + sizeof hostCtlLocal;
     const bool pinnedBack = hostBlock && genAt + sizeof genericLocal <= kHostBlockBytes;
     std::vector<uint8_t> spanLocal(pinnedBack ? 0 : spanBytes);
@@ -1194,9 +1147,6 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
     tm.streamPreviewMs = pv0 >= 0 ? et.ms(pv0, pv1) : 0.f;
     tm.tailMs = et.ms(e3, e4); tm.gatherMs = et.ms(e4, e5); tm.persistentMs = mk.mark >= 0 ? et.ms(mk.mark, mk.markGeneric >= 0 ? mk.markGeneric : e2) : 0.f;
     tm.genericMs = mk.markGeneric >= 0 ? et.ms(mk.markGeneric, e2) : 0.f; tm.genericMicroTriangles = genericWords[2];
-#ifdef OMMX_GD_STATS
-    if (dGeneric) { fprintf(stderr, "GDSTATS entries %llu:", genericWords[2]); for (int i = 0; i < 12; ++i) fprintf(stderr, " %llu", genericWords[8 + i]); fprintf(stderr, "\n"); }
-#endif
     for (int k = 0; k < kFineSlots; ++k) fineCount += fineSlots[(size_t)k * kFineStride];
     queueTails[1] = hostCtl[kCtl1024 + kSecTails]; for (uint32_t k = 0; k < kMaxClassifyChunks; ++k) queueTails[0] += hostCtl[kSecTails + k];   // (1024-tile queue; sections of the 4096-tile queue)
     tm.openTiles = queueTails[0] + queueTails[1]; tm.openTileMicroTriangles = (uint64_t)queueTails[0] * 4096u + (uint64_t)queueTails[1] * 1024u;
@@ -1536,10 +1486,7 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
         return k;
     };
     hipEvent_t evResult = nullptr;   // the device result is complete (everything in front of it on the bake's stream)
-#ifndef OMMX_DEFER_SMALL
-#define OMMX_DEFER_SMALL 1
-#endif
-    bool deferSmall = OMMX_DEFER_SMALL && ok && co.on && ses.open_comm() && HIP_OK(hipEventCreateWithFlags(&evResult, hipEventDisableTiming));
+    bool deferSmall = ok && co.on && ses.open_comm() && HIP_OK(hipEventCreateWithFlags(&evResult, hipEventDisableTiming));
     if (deferSmall) deferSmall = HIP_OK(hipEventRecord(evResult, stream)) && HIP_OK(hipStreamWaitEvent(ses.commStream, evResult, 0));
     struct EvGuard { hipEvent_t& e; ~EvGuard() { if (e) (void)hipEventDestroy(e); } } evGuard{ evResult };
     if (ok && !deferSmall) ok = small_copies(stream);
