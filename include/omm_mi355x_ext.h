@@ -223,6 +223,10 @@ OMM_MI355X_API ommResult ommxCommFromCollectives(const ommxCollectives* collecti
  *                        `deviceDesc` is the device-resident input desc the result was baked from (as given to ommxBakeDevice: a texture of
  *                        this baker, sampler, cut-off, device texcoords and indices); it is refused where ommxBakeDevice would refuse it, with
  *                        the same result code.  `result`, `hits`, `out` and the stream as for ommxLookupOpacity.
+ *                        The result may have more index entries than deviceDesc has triangles (indexCount / 3).  A hit on a primitive at or
+ *                        beyond the desc's triangle count is answered from the OMM where its state there is Transparent or Opaque (after
+ *                        Force2State, if set); where the texture would have to be sampled -- an unknown state, or any state under
+ *                        IgnoreMicromap -- it reads 0xFF, and the desc's index buffer and texture coordinates are not read for it.
  * None of the three allocates memory or synchronises a stream. */
 typedef struct ommxHit { uint32_t primitiveIndex; float u, v; } ommxHit;
 typedef enum ommxLookupFlags {

@@ -20,11 +20,18 @@ __device__ __forceinline__ uint32_t hit_state(const ommCpuBakeResultDesc& r, con
     return force2 ? ommx_force_2state(s) : s;
 }
 
+// The grid stride without 32-bit wrap-around: a count within one stride of 2^32 would otherwise bring a lane back to hits it has answered, forever.
+__device__ __forceinline__ uint32_t next_hit(uint32_t i, uint32_t count)
+{
+    const uint32_t stride = gridDim.x * kLookupBlock;
+    return count - i > stride ? i + stride : count;   // (i < count here)
+}
+
 // One hit per lane: index entry -> descriptor -> state byte, three dependent loads.  No LDS, few registers, so that many waves keep loads in flight.
 __global__ __launch_bounds__(kLookupBlock) void lookup_opacity(ommCpuBakeResultDesc r, const ommxHit* __restrict__ hits, uint32_t count,
                                                                uint8_t* __restrict__ out, uint32_t force2)
 {
-    for (uint32_t i = blockIdx.x * kLookupBlock + threadIdx.x; i < count; i += gridDim.x * kLookupBlock) {
+    for (uint32_t i = blockIdx.x * kLookupBlock + threadIdx.x; i < count; i = next_hit(i, count)) {
         const ommxHit h = hits[i];
         out[i] = (uint8_t)hit_state(r, h, force2 != 0);
     }
@@ -73,7 +80,7 @@ template <bool FP32>
 __global__ __launch_bounds__(kLookupBlock) void resolve_hits(ResolveParams R, ommCpuBakeResultDesc r, const ommxHit* __restrict__ hits, uint32_t count,
                                                              uint8_t* __restrict__ out, uint32_t flags)
 {
-    for (uint32_t i = blockIdx.x * kLookupBlock + threadIdx.x; i < count; i += gridDim.x * kLookupBlock) {
+    for (uint32_t i = blockIdx.x * kLookupBlock + threadIdx.x; i < count; i = next_hit(i, count)) {
         const ommxHit h = hits[i];
         const uint32_t s = hit_state(r, h, (flags & ommxLookupFlags_Force2State) != 0);
         uint32_t o;

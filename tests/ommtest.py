@@ -384,6 +384,20 @@ class Hip:
     def free(self, p):
         self.rt.hipFree(p)
 
+    def stream_create(self, non_blocking=False):
+        self.rt.hipStreamCreateWithFlags.argtypes = [C.POINTER(C.c_void_p), C.c_uint]
+        s = C.c_void_p()
+        assert self.rt.hipStreamCreateWithFlags(C.byref(s), 1 if non_blocking else 0) == 0   # 1 = hipStreamNonBlocking
+        return s
+
+    def stream_sync(self, stream):
+        self.rt.hipStreamSynchronize.argtypes = [C.c_void_p]
+        assert self.rt.hipStreamSynchronize(stream) == 0
+
+    def stream_destroy(self, stream):
+        self.rt.hipStreamDestroy.argtypes = [C.c_void_p]
+        assert self.rt.hipStreamDestroy(stream) == 0
+
 
 def device_result_to_host(lib, hip, out):
     """host copy (BakeResult) of an ommxDeviceBakeResult; destroys the device result"""

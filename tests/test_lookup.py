@@ -1,5 +1,7 @@
 """Host checks of the micromap consumer (include/omm_mi355x_lookup.h): the barycentrics -> micro-triangle map, the decoding of hand-built results
-through ommxLookupOpacityHost (the same header code the lookup_opacity kernel runs), and the bounds rule.  No GPU needed."""
+through ommxLookupOpacityHost (the same header code the lookup_opacity kernel runs), and the bounds rule; and checks of the reference code the
+GPU tests (tests/test_lookup_gpu.py) compare the kernels with: the numpy texel addressing against the oracle's, the closure-holder sets against
+the host lookup, and the share of each sampler case's hits that lies in the exclusion band.  No GPU needed."""
 import ctypes as C
 import os
 import re
@@ -7,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 import ommtest as ot
+import lookup_util as lu
+from lookup_util import Result, pack, unpack, digit_result
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID = 0xFF
@@ -32,39 +36,12 @@ def orc():
     return dll
 
 
-class Result:
-    """an ommCpuBakeResultDesc over numpy arrays (kept alive by the object)"""
-
-    def __init__(self, array_data, descs, index, index_format):
-        self.array = np.ascontiguousarray(array_data, np.uint8)
-        self.descs = np.ascontiguousarray(np.array(descs, dtype=[("o", "<u4"), ("l", "<u2"), ("f", "<u2")]).reshape(-1))
-        idt = {ot.IDX_U8: np.int8, ot.IDX_U16: np.int16, ot.IDX_U32: np.int32}.get(index_format, np.int32)
-        self.index = np.ascontiguousarray(np.array(index, dtype=np.int64).astype(idt))
-        d = ot.BakeResultDesc()
-        d.arrayData, d.arrayDataSize = self.array.ctypes.data, self.array.size
-        d.descArray, d.descArrayCount = C.cast(self.descs.ctypes.data, C.POINTER(ot.MicromapDesc)), self.descs.size
-        d.indexBuffer, d.indexCount, d.indexFormat = self.index.ctypes.data, self.index.size, index_format
-        self.desc = d
-
-
 def lookup(lib, res, prims, u, v, flags=0):
     hits = np.empty(len(prims), HIT)
     hits["prim"], hits["u"], hits["v"] = prims, u, v
     out = np.full(len(prims), 0xAB, np.uint8)
     assert lib.ommxLookupOpacityHost(C.byref(res.desc), hits.ctypes.data, len(hits), out.ctypes.data, flags) == ot.SUCCESS
     return out
-
-
-def pack(states, bits):
-    """micro-triangle states -> block bytes: state i at bit i (2-state) / bits 2i..2i+1 (4-state), little-endian within bytes"""
-    s = np.asarray(states, np.uint8)
-    per = 8 // bits
-    s = np.concatenate([s, np.zeros((-len(s)) % per, np.uint8)]).reshape(-1, per)
-    return (s.astype(np.uint32) << (bits * np.arange(per, dtype=np.uint32))).sum(axis=1).astype(np.uint8)
-
-
-def unpack(block, i, bits):
-    return (block[(i * bits) >> 3] >> ((i * bits) & 7)) & ((1 << bits) - 1)
 
 
 def centroids(orc, level):
@@ -116,16 +93,6 @@ def test_digit_table_is_the_inverse_of_the_forward_decode():
                 y ^= 1 if d == 1 else 0
     assert len(seen) == 16
     assert sum(d << (2 * k) for k, d in seen.items()) == table
-
-
-def digit_result(level):
-    """one 4-state block per base-4 digit of the index: in block p micro-triangle i stores (i >> 2p) & 3, so the states a point reads in
-    primitives 0..level-1 spell the index the lookup chose"""
-    n = 4 ** level
-    i = np.arange(n, dtype=np.uint32)
-    blocks = [pack((i >> (2 * p)) & 3, 2) for p in range(max(level, 1))]
-    size = len(blocks[0])
-    return Result(np.concatenate(blocks), [(p * size, level, 2) for p in range(len(blocks))], list(range(len(blocks))), ot.IDX_U32)
 
 
 def lookup_index(lib, res, level, u, v):
@@ -197,33 +164,29 @@ def test_decoding_of_hand_built_results(lib, orc, index_format, bits):
         assert np.array_equal(f, np.where(expect >= 2, expect - 2, expect))
 
 
-# ---- the bounds rule (host only) ----
+# ---- the bounds rule on the host (the same table goes through both kernels in tests/test_lookup_gpu.py) ----
 def test_bounds_rule(lib):
-    """every input the result cannot answer reads OMMX_OPACITY_INVALID, with no read outside the arrays given"""
-    lvl3 = pack(np.arange(64) % 4, 2)                       # 16 bytes
-    descs = [(0, 3, 2), (0, 13, 2), (0, 2, 0), (0, 2, 3), (1, 3, 2), (8, 3, 1), (9, 3, 1), (16, 0, 1)]
-    res = Result(lvl3, descs, [0, 1, 2, 3, 4, 5, 6, 7, 8, -5, -128, -1, 0], ot.IDX_U8)
-    hit = dict(u=[0.3], v=[0.3])
+    """every input the result cannot answer reads OMMX_OPACITY_INVALID, with no read outside the arrays given: the table of
+    lookup_util.bounds_table -- level 13, formats 0 and 3, blocks that end at / one byte past / start at arrayDataSize, entries >= descArrayCount
+    and below -4, special indices, primitives >= indexCount, unknown index formats, empty arrays -- in all three index formats"""
+    for index_format in (ot.IDX_U8, ot.IDX_U16, ot.IDX_U32):
+        table = lu.bounds_table(index_format)
+        res = Result(table["array"], table["descs"], [r[0] for r in table["rows"]], index_format)
+        assert res.array.size == 16 and res.desc.descArrayCount == 8
+        for name, fields, prims, expect, near in lu.bounds_variants(table):
+            for flags in (0, FORCE_2STATE):
+                hits = lu.bounds_hits(prims)
+                got = lu.lookup_host(lib, lu.with_fields(res.desc, **fields), hits, flags)
+                want = np.where((expect == 2) | (expect == 3), expect - 2, expect).astype(np.uint8) if flags else expect
+                assert np.array_equal(got, want), (index_format, name, flags, got, want)
+        # what the table must contain, whatever its layout: valid blocks that end exactly at arrayDataSize, every special index, every refusal
+        name, fields, prims, expect, near = lu.bounds_variants(table)[0]
+        assert {0, 1, 2, 3} <= set(expect.tolist()) and (expect == INVALID).sum() >= 14 and not near.all()
+    res = Result(pack(np.arange(64) % 4, 2), [(0, 3, 2)], [0], ot.IDX_U8)
     def one(prim, r=res, **kw):
-        return lookup(lib, r, [prim], kw.get("u", hit["u"]), kw.get("v", hit["v"]))[0]
-    assert one(0) < 4 and one(11) == 0 and one(12) < 4       # valid: a block that fits, a special index
-    assert one(1) == INVALID                                 # level 13
-    assert one(2) == INVALID and one(3) == INVALID           # format INVALID (0) / MAX_NUM (3)
-    assert one(4) == INVALID                                 # 16-byte block at offset 1 of a 16-byte array
-    assert one(5) < 2                                        # 8-byte 2-state block at 8: the last byte of the array
-    assert one(6) == INVALID                                 # ... at 9
-    assert one(7) == INVALID                                 # level-0 block at offset 16 == arrayDataSize
-    assert one(8) == INVALID                                 # entry 8 >= descArrayCount (8)
-    assert one(9) == INVALID and one(10) == INVALID          # entries below -4
-    assert one(13) == INVALID and one(0xFFFFFFFF) == INVALID  # prim >= indexCount
-    for fmt in (3, 7, 0x7FFFFFFF):                      # unknown index formats
-        bad = Result(lvl3, descs[:1], [0], ot.IDX_U32)
-        bad.desc.indexFormat = fmt
-        assert one(0, bad) == INVALID
-    empty = Result(np.zeros(0, np.uint8), [], [], ot.IDX_U32)
-    assert one(0, empty) == INVALID
+        return lookup(lib, r, [prim], kw["u"], kw["v"])[0]
     nodata = Result(np.zeros(0, np.uint8), [(0, 0, 1)], [0], ot.IDX_U16)
-    assert one(0, nodata) == INVALID                         # arrayDataSize 0
+    assert one(0, nodata, u=[0.3], v=[0.3]) == INVALID           # arrayDataSize 0 with a null array
     # NaN, infinities and points outside the triangle still read a valid micro-triangle of a valid block
     for u, v in [(np.nan, 0.2), (0.2, np.nan), (np.inf, -np.inf), (-1.0, 5.0), (0.9, 0.9), (1e30, 1e30), (-0.0, 1.0)]:
         assert one(0, u=[u], v=[v]) < 4
@@ -238,6 +201,111 @@ def test_micro_index_stays_in_range_for_any_float(lib):
         u, v = bits[0].view(np.float32), bits[1].view(np.float32)
         idx = lookup_index(lib, res, level, u, v)
         assert (idx < 4 ** level).all()
+
+
+# ---- the reference code of the GPU tests ----
+@pytest.mark.parametrize("level", [0, 1, 2, 3, 5, 8, 10])
+def test_edge_and_vertex_points_read_a_micro_triangle_that_holds_them(lib, level):
+    """lookup_util.closure_holders (candidates from the forward decode, containment on the decoded vertices in float64) against the host lookup
+    at every vertex, every edge midpoint and one ulp to either side of the cell diagonal -- the check the GPU test makes of the kernel"""
+    rng = np.random.default_rng(40 + level)
+    micro = lu.edge_level_sample(rng, level)
+    u, v = lu.edge_and_vertex_points(micro, level)
+    assert len(u) == 8 * len(micro)
+    res = digit_result(level)
+    idx = lu.digits_to_index(level, lu.lookup_host(lib, res.desc, lu.digit_hits(level, u, v)), len(u))
+    assert (idx < 4 ** level).all()
+    beyond = lu.check_index_is_a_holder(level, u, v, idx)
+    assert beyond <= len(micro)   # only diagonal midpoints moved outwards across the edge u + v = 1 leave the triangle
+    # the holders are what they claim: a centroid is held by its own micro-triangle alone, a shared vertex by up to six
+    cu, cv = lu.centroid_points(lu.micro_vertices(micro, np.full(len(micro), level)))
+    cand, holds = lu.closure_holders(level, cu, cv)
+    assert (holds.sum(axis=1) == 1).all() and np.array_equal(cand[holds], micro)
+    cand, holds = lu.closure_holders(level, u[:3 * len(micro)], v[:3 * len(micro)])
+    assert holds.sum(axis=1).max() == (6 if level >= 2 else (3 if level == 1 else 1)) and holds.sum(axis=1).min() >= 1
+    # and the check fails for a neighbour: the index of another micro-triangle is not accepted at a centroid
+    if level >= 1:
+        with pytest.raises(AssertionError):
+            lu.check_index_is_a_holder(level, cu, cv, (micro + 1) % 4 ** level)
+
+
+def test_numpy_addressing_equals_the_oracle():
+    """lookup_util._addr == orc_get_tex_coord (pinned to the reference's tables in test_oracle_units.py) for x in -3w..3w, every address mode,
+    sizes that are powers of two and sizes that are not, and the texture-wide flag both ways where the size allows it"""
+    dll = C.CDLL(ot.oracle_path())
+    dll.orc_get_tex_coord.argtypes = [C.c_int] * 6 + [C.POINTER(C.c_int)]
+    out = (C.c_int * 2)()
+    for size in (1, 2, 7, 64, 256, 333, 517, 600, 1000, 1024):
+        x = np.arange(-3 * size, 3 * size + 1, dtype=np.int64)
+        pow2_axis = (size & (size - 1)) == 0
+        for flag in ((0, 1) if pow2_axis else (0,)):   # flag 0 with a power-of-two side: the other side of the texture is not one
+            for mode in (ot.WRAP, ot.MIRROR, ot.CLAMP, ot.BORDER, ot.MIRROR_ONCE):
+                got = lu._addr(mode, x, size, bool(flag))
+                want = np.empty(len(x), np.int64)
+                for k, xi in enumerate(x):
+                    dll.orc_get_tex_coord(mode, flag, int(xi), int(xi), size, size, out)
+                    assert out[0] == out[1]
+                    want[k] = out[0]
+                border = want == 0x7FFFFFFE if mode == ot.BORDER else np.zeros(len(x), bool)
+                assert border.any() == (mode == ot.BORDER)
+                assert np.array_equal(got, np.where(border, -1, want)), (size, flag, mode, x[got != np.where(border, -1, want)][:5])
+                assert ((got >= 0) & (got < size) | border).all()
+
+
+def test_numpy_sampler_against_a_scalar_restatement():
+    """sample_alpha on a non-square texture that is not a power of two, every mode and filter, against a per-point Python restatement with
+    Python floats (float64) of the same definition: fp32 texel coordinate and weights, float64 blend"""
+    rng = np.random.default_rng(3)
+    tex = rng.integers(0, 256, (5, 7), dtype=np.uint8)
+    h, w = tex.shape
+    tu, tv = rng.uniform(-2.5, 3.5, 300).astype(np.float32), rng.uniform(-2.5, 3.5, 300).astype(np.float32)
+    f32 = np.float32
+    for mode in (ot.WRAP, ot.MIRROR, ot.CLAMP, ot.BORDER, ot.MIRROR_ONCE):
+        def texel(x, y):
+            ax, ay = int(lu._addr(mode, np.array([x]), w, False)[0]), int(lu._addr(mode, np.array([y]), h, False)[0])
+            return 0.625 if ax < 0 or ay < 0 else float(f32(tex[ay, ax]) * f32(1.0 / 255.0))
+        near = lu.sample_alpha(tex, tu, tv, mode, ot.NEAREST, 0.625)
+        lin = lu.sample_alpha(tex, tu, tv, mode, ot.LINEAR, 0.625)
+        for k in range(len(tu)):
+            assert near[k] == texel(int(np.floor(tu[k] * f32(w))), int(np.floor(tv[k] * f32(h))))
+            px, py = tu[k] * f32(w) - f32(0.5), tv[k] * f32(h) - f32(0.5)
+            x, y = int(np.floor(px)), int(np.floor(py))
+            wx, wy = float(f32(px - np.floor(px))), float(f32(py - np.floor(py)))
+            want = (texel(x, y) * (1 - wx) + texel(x + 1, y) * wx) * (1 - wy) + (texel(x, y + 1) * (1 - wx) + texel(x + 1, y + 1) * wx) * wy
+            assert abs(lin[k] - want) < 1e-15
+
+
+def test_sampler_cases_are_well_posed(oracle):
+    """the conditions tests/test_lookup_gpu.py::test_resolve_sampler_paths rests on, decided here without the product's kernels: by the numpy
+    reference alone, at most 0.1 % of any case's hits have an alpha within 1e-6 of the cut-off (the GPU test asserts it again) and every case
+    samples both sides of its cut-off; and in the ORACLE's bake of the case every known state agrees with the numpy sampler"""
+    for name in lu.sampler_case_names():
+        c = lu.sampler_case(name)
+        alpha, near = lu.reference_alpha(c)
+        above = alpha > np.float64(np.float32(c["cutoff"]))
+        assert near.sum() <= lu.BAND_CAP * len(near), (name, int(near.sum()))
+        assert 0.02 < above.mean() < 0.98, (name, above.mean())
+        b = oracle.create_baker()
+        t = oracle.create_texture(b, c["mips"], alpha_cutoff=c["cutoff"])
+        d = ot.make_desc(t, c["raw"].reshape(-1)[c["uv_offset"]:], c["ix"], 6, levels=c["levels"], addr=c["addr"], filt=c["filt"],
+                         promo=ot.PROMO_NEAREST, flags=ot.FLAG_THREADS, uv_format=c["uv_format"], border_alpha=c["border"],
+                         alpha_cutoff=c["cutoff"], le=c["le"], gt=c["gt"])
+        d.texCoordStrideInBytes = c["stride"]
+        res = oracle.bake(b, d, want_stats=False)
+        oracle.destroy_texture(b, t)
+        oracle.destroy_baker(b)
+        lv, has = lu.prim_levels(res)
+        assert np.array_equal(lv[has], c["levels"][has]), name
+        state = lu.numpy_states(res, c["prims"], c["micro"])
+        q = c["uv_read"][c["ix"].reshape(-1, 3)].reshape(-1, 6)
+        area = np.float32(0.5) * np.abs(q[:, 0] * (q[:, 3] - q[:, 5]) + q[:, 2] * (q[:, 5] - q[:, 1]) + q[:, 4] * (q[:, 1] - q[:, 3]))
+        degenerate = (area.astype(np.float64) < 1e-9)[c["prims"]] if c["filt"] == ot.NEAREST else np.zeros(c["m"], bool)
+        known = (state < 2) & ~near & ~degenerate
+        bad = known & ((np.where(above, c["gt"], c["le"]) & 1) != state)
+        print("%s: %d of %d hits in the band, %.1f %% above the cut-off, %d known hits, %d of %d triangles re-drawn as slivers" % (
+            name, int(near.sum()), len(near), 100.0 * above.mean(), int(known.sum()), c["slivers"], c["ntris"]))
+        assert c["slivers"] <= c["ntris"] // 10, name
+        assert not bad.any(), (name, int(bad.sum()))
 
 
 # ---- argument checks that need no device ----
