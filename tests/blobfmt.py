@@ -32,8 +32,11 @@ def lz4_block_decompress(src, out_size):
                     break
         ml += 4
         start = len(out) - off
-        for k in range(ml):
-            out.append(out[start + k])
+        assert 0 < off <= len(out), "LZ4 match offset outside the output"
+        if off >= ml:
+            out += out[start:start + ml]
+        else:   # overlapping match: the last `off` bytes repeat
+            out += (bytes(out[start:]) * (ml // off + 1))[:ml]
     assert len(out) == out_size, (len(out), out_size)
     return bytes(out)
 
@@ -75,8 +78,31 @@ def xy_to_morton(x, y):
     return spread(x) | (spread(y) << 1)
 
 
+def morton_index(w, h):
+    """(h, w) array of the Morton-Z index of every texel (xy_to_morton for whole arrays)"""
+    def spread(v):
+        v = v.astype(np.uint64)
+        for s, m in ((8, 0x00FF00FF), (4, 0x0F0F0F0F), (2, 0x33333333), (1, 0x55555555)):
+            v = (v | (v << np.uint64(s))) & np.uint64(m)
+        return v
+    return (spread(np.arange(w))[None, :] | (spread(np.arange(h))[:, None] << np.uint64(1))).astype(np.int64)
+
+
+def next_pow2(v):
+    return 1 << max(0, int(v) - 1).bit_length()
+
+
+def mip_num_elements(w, h, tiling):
+    """texels of a mip's storage slot (texture_impl.cpp:107-117): Morton-Z pads to a power-of-two square"""
+    return next_pow2(max(w, h)) ** 2 if tiling == 1 else w * h
+
+
 def parse_blob(blob, xxh64=None):
-    """Returns dict(version=..., inputs=[...], results=[...]).  xxh64(data, seed)->int optionally verifies the digest."""
+    """Returns dict(version=..., inputs=[...], results=[...]).  xxh64(data, seed)->int optionally verifies the digest.
+    texture: `mips` are the texels; when the blob carries a summed-area-table section (`has_sat`), `sat[m]` is mip m's table as an
+    (h, w) uint32 array -- row-major with stride w in BOTH tilings (texture_impl.cpp:191-220), read at the mip's dataOffsetSAT --
+    and `sat_rest[m]` the raw bytes of the remainder of that mip's slot (up to the next mip's offset, or the end of the section);
+    `mip_descs[m]` = (w, h, dataOffset, numElements, dataOffsetSAT) and `sat_size` the section's size as stored."""
     r = Reader(blob)
     digest = r.fmt("Q")
     if xxh64 is not None:
@@ -107,13 +133,19 @@ def parse_blob(blob, xxh64=None):
             raw = np.frombuffer(data, np.float32 if texfmt == 1 else np.uint8, count=ne, offset=off)
             a = np.empty((h, w), raw.dtype)
             if tiling == 1:  # Morton-Z internal order
-                for j in range(h):
-                    for i in range(w):
-                        a[j, i] = raw[xy_to_morton(i, j)]
+                a[:] = raw[morton_index(w, h)]
             else:
                 a[:] = raw.reshape(h, w)
             arrays.append(a)
-        d["texture"] = dict(mips=arrays, tiling=tiling, flags=texflags, alphaCutoff=tex_cutoff, format=texfmt, has_sat=len(sat) != 0)
+        sats, rests = [], []
+        if len(sat):
+            for m, (w, h, rw, rh, off, ne, offsat) in enumerate(mips):
+                end = mips[m + 1][6] if m + 1 < nm else len(sat)
+                assert offsat + 4 * w * h <= end <= len(sat), "SAT slot of mip %d does not fit its section" % m
+                sats.append(np.frombuffer(sat, "<u4", count=w * h, offset=offsat).reshape(h, w))
+                rests.append(sat[offsat + 4 * w * h:end])
+        d["texture"] = dict(mips=arrays, tiling=tiling, flags=texflags, alphaCutoff=tex_cutoff, format=texfmt, has_sat=len(sat) != 0,
+                            sat=sats, sat_rest=rests, sat_size=len(sat), mip_descs=[(m[0], m[1], m[4], m[5], m[6]) for m in mips])
         d["addressingMode"], d["filter"], d["borderAlpha"], d["alphaMode"] = r.fmt("iifi")
         d["texCoordFormat"] = r.fmt("i")
         d["texCoords"] = r.take(r.fmt("Q"))

@@ -719,24 +719,7 @@ def test_near_duplicate_merge_and_size_budget(product, oracle):
 # ---------------------------------------------------------------------------------------------
 # blob (de)serialisation -- SURVEY.md section 8(f) #1
 # ---------------------------------------------------------------------------------------------
-class BlobDesc(__import__("ctypes").Structure):
-    _fields_ = [("data", __import__("ctypes").c_void_p), ("size", __import__("ctypes").c_uint64)]
-
-
-class DeserializedDesc(__import__("ctypes").Structure):
-    import ctypes as _C
-    _fields_ = [("flags", _C.c_int), ("numInputDescs", _C.c_int), ("inputDescs", _C.POINTER(ot.BakeInputDesc)),
-                ("numResultDescs", _C.c_int), ("resultDescs", _C.POINTER(ot.BakeResultDesc))]
-
-
-def _bind_serialize(dll):
-    import ctypes as C
-    dll.ommCpuSerialize.argtypes = [C.c_void_p, C.POINTER(DeserializedDesc), C.POINTER(C.c_void_p)]
-    dll.ommCpuGetSerializedResultDesc.argtypes = [C.c_void_p, C.POINTER(C.POINTER(BlobDesc))]
-    dll.ommCpuDestroySerializedResult.argtypes = [C.c_void_p]
-    dll.ommCpuDeserialize.argtypes = [C.c_void_p, C.POINTER(BlobDesc), C.POINTER(C.c_void_p)]
-    dll.ommCpuGetDeserializedDesc.argtypes = [C.c_void_p, C.POINTER(C.POINTER(DeserializedDesc))]
-    dll.ommCpuDestroyDeserializedResult.argtypes = [C.c_void_p]
+from sat_util import BlobDesc, DeserializedDesc, bind as _bind_serialize   # the ctypes view of the (de)serialisation entry points
 
 
 def _deserialize(product, baker, blob_bytes, expect=ot.SUCCESS):
