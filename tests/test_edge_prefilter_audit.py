@@ -181,3 +181,45 @@ def test_corner_votes_skipped_only_where_no_corner_can_be_inside(audit):
     # (the long form of this sweep -- ~4x the triangles, every address mode at every offset, five minutes -- ran when the predicate went in: 0 disagreements)
     assert visits > 1000000 and far > visits // 4, (visits, far)
     assert bad == 0, (visits, far, bad)
+
+
+VALUE_DOMAIN_FAMILIES = ["sdf", "hdr", "huge", "denormal", "plateau", "nonfinite", "unorm8", "uv"]
+
+
+def value_domain_bakes(audit, family):
+    """every bake of one family of tests/value_domain_cases.py (the inputs of test_value_domain_gpu.py) through the audit build; "uv" = its UV cases"""
+    import value_domain_cases as vd
+    if family == "uv":
+        tex = vd.uv_texture()
+        for c in vd.uv_cases():
+            vd.oracle_bake(audit, [tex], c["uv"], c["ix"], c["level"], c["sat"], vd.UV_CUTOFF, levels=c["levels"], **c["kw"])
+        return
+    for inp in vd.inputs():
+        if inp["family"] == family:
+            for b in vd.bakes_of(inp):
+                vd.oracle_bake(audit, inp["mips"], b["uv"], b["ix"], b["level"], b["sat"], inp["cutoff"], **b["kw"])
+
+
+def test_exclusion_predicates_on_value_domain_inputs(audit):
+    """The four predicates over texel values, cut-offs and UVs outside [0, 1]: signed-distance and HDR values, +-3e38 (the predicates' own products overflow),
+    denormals, plateaus of the cut-off and its neighbours, NaN / +-inf texels, UNORM8 texels equal to the cut-off, +-0 / denormal / beyond-int-range UVs.  First
+    check of "NaN / Inf operands compare false and take the exact path" and of the bounds scaled by S = |ha| + |hb| + |hc| + |hd|: per family, no predicate
+    excludes what the reference accepts, and no family is vacuous (both exclusion predicates are asked).  An exclusion rate of 0 % is fine (tests/README.md has
+    the figures)."""
+    for family in VALUE_DOMAIN_FAMILIES:
+        audit.dll.orc_audit_reset(); audit.dll.orc_audit_curve_reset(); audit.dll.orc_audit_cell_reset(); audit.dll.orc_audit_corner_reset()
+        value_domain_bakes(audit, family)
+        calls, discarded, bad = (audit.dll.orc_audit_counter(i) for i in range(3))
+        roots, rejected, bad_roots = (audit.dll.orc_audit_counter(i) for i in (4, 5, 6))
+        calls3, excluded3, bad3, crossings3 = (audit.dll.orc_audit_curve_counter(i) for i in range(4))
+        cell = _cell_counts(audit)
+        visits, far, bad_corner = _corner_counts(audit)
+        print("value-domain audit %-10s point_on_edge %9d calls %5.1f %% discarded | roots %9d %5.1f %% rejected | curve_excluded %8d calls %5.1f %% excluded | "
+              "cell_excluded %8d calls %5.1f %% excluded | corners %9d visits %5.1f %% far" %
+              (family, calls, 100.0 * discarded / max(calls, 1), roots, 100.0 * rejected / max(roots, 1), calls3, 100.0 * excluded3 / max(calls3, 1),
+               cell[0], 100.0 * cell[1] / max(cell[0], 1), visits, 100.0 * far / max(visits, 1)))
+        assert calls3 > 0 and cell[0] > 0 and visits > 0, (family, calls3, cell[0], visits)      # a family with no predicate call would be a vacuous case
+        assert bad == 0 and bad_roots == 0, (family, bad, bad_roots)
+        assert bad3 == 0, (family, calls3, excluded3, bad3)
+        assert cell[2] == 0 and cell[5] == 0, (family, cell)          # the shipped predicate (8x) and the bounds as derived (1x)
+        assert bad_corner == 0, (family, visits, far, bad_corner)

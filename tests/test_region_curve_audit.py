@@ -78,3 +78,16 @@ def test_region_verdicts_seed_sweep_on_every_lease(audit, seed):
     c = counters(audit)
     assert c[0] > 300_000 and c[1] > 200_000, tuple(c)
     assert c[3] == 0 and c[11] == 0, c
+
+
+def test_region_verdicts_on_value_domain_inputs(audit):
+    """the inputs of test_value_domain_gpu.py (tests/value_domain_cases.py): texel values, cut-offs and UVs outside [0, 1] -- signed-distance / HDR values, +-3e38,
+    denormals, plateaus at the cut-off, NaN / +-inf texels, UNORM8 texels equal to the cut-off.  Per family: sub-triangles are tested, no settled descendant differs."""
+    from test_edge_prefilter_audit import VALUE_DOMAIN_FAMILIES, value_domain_bakes
+    for family in VALUE_DOMAIN_FAMILIES:
+        audit.dll.orc_audit_region_reset()
+        value_domain_bakes(audit, family)
+        c = counters(audit)
+        print("value-domain region audit %-10s sub-triangles %9d settled %5.1f %% (mixed cells: %d) | weaker verdict %8d" % (family, c[0], 100.0 * c[1] / max(c[0], 1), c[6], c[8]))
+        assert c[0] > 0, (family, c)
+        assert c[3] == 0 and c[11] == 0, (family, c)
