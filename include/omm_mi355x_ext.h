@@ -239,4 +239,47 @@ OMM_MI355X_API ommResult ommxLookupOpacityHost(const ommCpuBakeResultDesc* resul
 OMM_MI355X_API ommResult ommxResolveHits(ommBaker baker, const ommCpuBakeInputDesc* deviceDesc, const ommCpuBakeResultDesc* result,
                                          const ommxHit* hits, uint32_t count, uint8_t* out, uint32_t flags, void* hipStream);
 
+/* ---- ommDebugStats of a device-resident result, computed where the result lives ----
+ * ommxDebugGetStatsDevice   ommDebugGetStats / ommDebugGetStats2 for a result whose arrays are DEVICE memory.  `deviceResult` is a HOST struct as for
+ *                        ommxLookupOpacity: the desc of ommxGetDeviceBakeResultDesc, or one the caller filled with device copies of an ommCpuBake
+ *                        result (on the baker's device).  One streaming pass over arrayData and one over the index buffer; nothing is downloaded.
+ *   integer fields       exactly what ommDebugGetStats answers for a host copy of the same arrays, its 32-bit arithmetic included: per referenced
+ *                        block, (uint32_t)(references * count[state]) is added to the 64-bit totals.  Blocks no primitive selects add nothing.
+ *   bounds               the host call trusts the descriptors; this one applies the rule of include/omm_mi355x_lookup.h before any read: a
+ *                        descriptor with a level above 12, a format other than OC1_2_State / OC1_4_State or a block that does not fit inside
+ *                        arrayDataSize has zero counts and adds nothing, and a primitive that selects it is ignored like one whose entry is below -4
+ *                        or at or beyond descArrayCount (which the host ignores too).  *outSkippedPrimitives (optional) <- the number of primitives
+ *                        ignored for any of these reasons.
+ *   outputs (optional)   per-block and per-primitive answers in DEVICE memory, every member optional; complete when the call returns:
+ *                        stateCounts[d][s]   micro-triangles of block d in ommOpacityState s (all blocks, referenced or not),
+ *                        referenceCounts[d]  primitives whose index entry selects block d,
+ *                        knownFraction[i]    1 for FullyTransparent / FullyOpaque, 0 for the two FullyUnknown specials and for ignored primitives,
+ *                                            otherwise (float)(T + O) / (float)(T + O + UT + UO) of the selected block, one IEEE fp32 division.
+ *   knownAreaMetric      with `deviceTriangleAreas` (indexCount floats in device memory):
+ *                            (float)( sum_i (double)area[i] * (double)knownFraction[i]  /  sum_i (double)area[i] )
+ *                        both sums in fp64 over a fixed partition and a fixed tree, without floating-point atomics: two calls on the same inputs
+ *                        return the same bits.  This is the QUANTITY ommDebugGetStats2 reports, not its rounding: the host sums in fp32 in triangle
+ *                        order (per block first), which no parallel reduction reproduces; the two agree to about (indexCount + 4) * 2^-22.
+ *                        A zero area sum gives the host's NaN.  Without areas (NULL) the metric is 0, as in ommDebugGetStats.
+ *   stream, memory       the kernels run on `hipStream` (a hipStream_t; null = the null stream), which the call synchronises before it returns -- the
+ *                        answer is a host struct.  Scratch comes from the baker's device pool and is back there when the call returns.
+ *   result codes         null baker, deviceResult or out, a baker of unknown type, an unknown indexFormat -> INVALID_ARGUMENT; indexCount == 0 ->
+ *                        SUCCESS without a launch (all fields zero, `outputs` untouched).
+ * ommxGetDeviceBakeResultTriangleAreas   the UV-space area of every input triangle (the side channel ommDebugGetStats2 reads from an
+ *                        ommCpuBakeResult): every result of ommxBakeDevice owns a device copy, indexCount floats, valid until
+ *                        ommxDestroyDeviceBakeResult.  Results of ommxShardedFinish / ommxShardedBakeRccl do not carry areas: *deviceAreas <- NULL.
+ * ommxDebugGetStatsDevice2  the ommDebugGetStats2 of device results: ommxDebugGetStatsDevice on the result's desc with its own areas, on the null
+ *                        stream.  For a sharded result (no areas) knownAreaMetric is 0. */
+typedef struct ommxDeviceStatsOutputs {   /* every member optional (NULL = not wanted); DEVICE memory */
+    uint32_t* stateCounts;      /* [descArrayCount][4]: Transparent, Opaque, UnknownTransparent, UnknownOpaque micro-triangles of each OMM block */
+    uint32_t* referenceCounts;  /* [descArrayCount]: primitives whose index entry selects the block */
+    float*    knownFraction;    /* [indexCount]: per primitive, see above */
+} ommxDeviceStatsOutputs;
+OMM_MI355X_API ommResult ommxDebugGetStatsDevice(ommBaker baker, const ommCpuBakeResultDesc* deviceResult,
+                                                 const float* deviceTriangleAreas,            /* indexCount floats in HBM, or NULL */
+                                                 const ommxDeviceStatsOutputs* outputs,       /* or NULL */
+                                                 ommDebugStats* out, uint32_t* outSkippedPrimitives /* or NULL */, void* hipStream);
+OMM_MI355X_API ommResult ommxGetDeviceBakeResultTriangleAreas(ommxDeviceBakeResult result, const float** deviceAreas);
+OMM_MI355X_API ommResult ommxDebugGetStatsDevice2(ommBaker baker, ommxDeviceBakeResult result, ommDebugStats* out);
+
 #endif

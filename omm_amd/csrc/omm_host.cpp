@@ -10,6 +10,7 @@
 #include "host_tail.h"
 #include "host_expand.h"
 #include "lookup_kernels.h"
+#include "stats_kernels.h"
 
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
@@ -567,6 +568,7 @@ struct DeviceResult {
     void* index = nullptr; uint32_t numTris = 0; ommIndexFormat indexFormat = ommIndexFormat_UINT_32;
     uint32_t hist[2 * kNumLevels]; int bits = 2;
     const float* triAreaScratch = nullptr; // per-triangle UV areas in the bake's arena: valid until the session ends (ommCpuBake copies them out)
+    float* triArea = nullptr;              // ommxBakeDevice: the result's own device copy of them (ommxDebugGetStatsDevice2's side channel); null for sharded results
     std::shared_ptr<DevPool> pool;   // the baker's (results may outlive their baker)
     // ommCpuBake's compressed transfer: asked right before the gather, when the array's size is known and every OMM is a multiple of 16 bytes; may hand out a byte per
     // 16-byte unit and a zeroed word per 256-unit block (+ 1) for the gather to fill with the exchange codec's codes and raw counts (launch_gather_omms)
@@ -575,7 +577,7 @@ struct DeviceResult {
     DeviceResult(const DeviceResult&) = delete;
     DeviceResult& operator=(const DeviceResult&) = delete;
     void* dev_alloc(size_t bytes) { return pool ? pool->acquire(bytes) : nullptr; }
-    ~DeviceResult() { if (pool) { pool->release(arrayData); pool->release(descs); pool->release(index); } }
+    ~DeviceResult() { if (pool) { pool->release(arrayData); pool->release(descs); pool->release(index); pool->release(triArea); } }
 };
 
 struct DeviceInputs {           // raw triangle data, device resident
@@ -1216,6 +1218,14 @@ ommResult upload_host_tail(Baker& b, const HostTailResult& hres, ommIndexFormat 
     res->desc.indexBuffer = R.index; res->desc.indexCount = T; res->desc.indexFormat = ifmt;
     res->desc.indexHistogram = res->indexHist; res->desc.indexHistogramCount = (uint32_t)nIH;
     return ommResult_SUCCESS;
+}
+
+// ommxBakeDevice: the per-triangle UV areas leave the bake's arena with the result -- one device-to-device copy of T floats, released with the result
+bool keep_tri_areas(DeviceResult& R, const float* areaScratch, uint32_t T, hipStream_t stream)
+{
+    if (!T || !areaScratch) return true;
+    R.triArea = (float*)R.dev_alloc(sizeof(float) * (size_t)T);
+    return R.triArea && HIP_OK(hipMemcpyAsync(R.triArea, areaScratch, sizeof(float) * (size_t)T, hipMemcpyDeviceToDevice, stream)) && HIP_OK(hipStreamSynchronize(stream));
 }
 
 struct BakeSession { // device working set + streams of one bake in flight
@@ -1939,6 +1949,7 @@ OMM_MI355X_API ommResult ommxBakeDevice(ommBaker baker, const ommCpuBakeInputDes
         HostTailResult hres; ommIndexFormat ifmt = ommIndexFormat_UINT_32;
         if (hr == ommResult_SUCCESS) hr = run_host_tail_for(*desc, desc->indexCount / 3u, ht.items, hres, ifmt);
         if (hr == ommResult_SUCCESS) hr = upload_host_tail(*b, hres, ifmt, desc->indexCount / 3u, (int)desc->format, ses.stream, res);
+        if (hr == ommResult_SUCCESS && !keep_tri_areas(res->R, scratchR.triAreaScratch, desc->indexCount / 3u, ses.stream)) hr = b->log.failure("[Failure] - could not keep the triangle areas on the device");
         if (hr != ommResult_SUCCESS) { (void)hipStreamSynchronize(ses.stream); b->mem.destroy(res); return hr; }
         tm.totalMs = (float)(now_ms() - t0);
         { std::lock_guard<std::mutex> g(b->timingsMu); b->timings = tm; b->haveTimings = true; }
@@ -1946,6 +1957,7 @@ OMM_MI355X_API ommResult ommxBakeDevice(ommBaker baker, const ommCpuBakeInputDes
         return ommResult_SUCCESS;
     }
     r = bake_core(*b, *desc, din, nullptr, ses.arena, ses.states, ses.stream, et, res->R, tm);
+    if (r == ommResult_SUCCESS && !keep_tri_areas(res->R, res->R.triAreaScratch, desc->indexCount / 3u, ses.stream)) r = b->log.failure("[Failure] - could not keep the triangle areas on the device");
     if (r != ommResult_SUCCESS) { (void)hipStreamSynchronize(ses.stream); b->mem.destroy(res); return r; } // (pooled blocks go back only when the stream is idle)
     uint32_t nAH = 0, nIH = 0;
     for (uint32_t l = 0; l < (uint32_t)kNumLevels; ++l) {
@@ -2721,6 +2733,63 @@ OMM_MI355X_API ommResult ommxDestroyDeviceBakeResult(ommxDeviceBakeResult result
     const Allocator mem = r->mem;
     mem.destroy(r);
     return ommResult_SUCCESS;
+}
+
+OMM_MI355X_API ommResult ommxGetDeviceBakeResultTriangleAreas(ommxDeviceBakeResult result, const float** deviceAreas)
+{
+    if (result == 0 || deviceAreas == nullptr) return ommResult_INVALID_ARGUMENT;
+    *deviceAreas = ((DeviceBakeResult*)result)->R.triArea;
+    return ommResult_SUCCESS;
+}
+
+// ommDebugStats of a result whose arrays are device memory (include/omm_mi355x_ext.h; kernels in stats_kernels.hip): the integer fields are
+// collect_stats' own, 32-bit products included; the area metric is the same quantity summed in fp64 in a fixed order.
+namespace {
+ommResult stats_device(Baker& b, const ommCpuBakeResultDesc& r, const float* areas, const ommxDeviceStatsOutputs* outputs, ommDebugStats* out,
+                       uint32_t* outSkipped, hipStream_t stream)
+{
+    if (r.indexFormat != ommIndexFormat_UINT_8 && r.indexFormat != ommIndexFormat_UINT_16 && r.indexFormat != ommIndexFormat_UINT_32) return ommResult_INVALID_ARGUMENT;
+    ommDebugStats st; memset(&st, 0, sizeof st);
+    if (r.indexCount == 0) {   // nothing to launch; the host's 0 / 0 where areas were handed in
+        if (areas) { const float zero = 0.f; st.knownAreaMetric = zero / zero; }
+        *out = st; if (outSkipped) *outSkipped = 0;
+        return ommResult_SUCCESS;
+    }
+    if (r.indexBuffer == nullptr || (r.descArrayCount && (r.descArray == nullptr || (r.arrayData == nullptr && r.arrayDataSize)))) return ommResult_INVALID_ARGUMENT;
+    StatsArgs a; a.result = r; a.areas = areas;
+    a.stateCounts = outputs ? outputs->stateCounts : nullptr; a.referenceCounts = outputs ? outputs->referenceCounts : nullptr;
+    a.knownFraction = outputs ? outputs->knownFraction : nullptr;
+    const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
+    struct PoolBlock { DevPool* pool; void* p; ~PoolBlock() { if (p) pool->release(p); } } scratch{ b.devPool.get(), b.devPool->acquire(stats_scratch_bytes(a)) };
+    if (!scratch.p) return b.log.failure("[Failure] - out of device memory for the statistics scratch");
+    StatsTotals t;
+    if (launch_stats(a, scratch.p, &t, stream) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipStreamSynchronize(stream);   // (the scratch goes back only when nothing can still touch it)
+        return b.log.failure("[Failure] - the statistics kernels could not run");
+    }
+    st.totalTransparent = t.state[0]; st.totalOpaque = t.state[1]; st.totalUnknownTransparent = t.state[2]; st.totalUnknownOpaque = t.state[3];
+    st.totalFullyTransparent = t.special[0]; st.totalFullyOpaque = t.special[1]; st.totalFullyUnknownTransparent = t.special[2]; st.totalFullyUnknownOpaque = t.special[3];
+    st.knownAreaMetric = areas ? (float)(t.knownArea / t.totalArea) : 0.f;
+    *out = st; if (outSkipped) *outSkipped = t.skipped;
+    return ommResult_SUCCESS;
+}
+}
+
+OMM_MI355X_API ommResult ommxDebugGetStatsDevice(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const float* deviceTriangleAreas,
+                                                 const ommxDeviceStatsOutputs* outputs, ommDebugStats* out, uint32_t* outSkippedPrimitives, void* hipStream)
+{
+    if (baker == 0) return ommResult_INVALID_ARGUMENT;
+    if (tag_of(baker) != kCpuBaker && tag_of(baker) != kGpuBaker) return ommResult_INVALID_ARGUMENT;
+    if (deviceResult == nullptr || out == nullptr) return ommResult_INVALID_ARGUMENT;
+    Baker* b = untag<Baker>(baker);
+    return guarded(&b->log, [&] { return stats_device(*b, *deviceResult, deviceTriangleAreas, outputs, out, outSkippedPrimitives, (hipStream_t)hipStream); });
+}
+
+OMM_MI355X_API ommResult ommxDebugGetStatsDevice2(ommBaker baker, ommxDeviceBakeResult result, ommDebugStats* out)
+{
+    if (result == 0) return ommResult_INVALID_ARGUMENT;
+    const DeviceBakeResult* r = (const DeviceBakeResult*)result;
+    return ommxDebugGetStatsDevice(baker, &r->desc, r->R.triArea, nullptr, out, nullptr, nullptr);
 }
 
 // Any-hit resolution of hits against a device-resident result (include/omm_mi355x_ext.h; kernels in lookup_kernels.hip).  The desc is checked as
