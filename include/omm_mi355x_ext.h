@@ -282,4 +282,54 @@ OMM_MI355X_API ommResult ommxDebugGetStatsDevice(ommBaker baker, const ommCpuBak
 OMM_MI355X_API ommResult ommxGetDeviceBakeResultTriangleAreas(ommxDeviceBakeResult result, const float** deviceAreas);
 OMM_MI355X_API ommResult ommxDebugGetStatsDevice2(ommBaker baker, ommxDeviceBakeResult result, ommDebugStats* out);
 
+/* ---- an alpha texture from an image that is already in device memory ----
+ * ommxCreateTextureDevice  ommCpuCreateTexture for texels that live in HBM: ONE channel of an interleaved (or packed single-channel) image is read where
+ *                        it is; nothing is downloaded, restaged or uploaded.  The result is an ordinary ommCpuTexture, byte for byte the texture
+ *                        ommCpuCreateTexture makes from the extracted channel -- same texels, same summed-area table, same serialized blob -- and is
+ *                        accepted wherever a texture is: ommCpuBake, ommxBakeDevice, the sharded and multi-device bakes, ommxResolveHits,
+ *                        ommCpuGetTextureDesc, ommCpuSerialize, ommCpuDestroyTexture.
+ *   the source           pixel (x, y) of mip m starts at  (const char*)mips[m].deviceData + y * rowPitchInBytes + x * pixelStrideInBytes ; the channel is
+ *                        the channelFormat-typed value channelOffsetInBytes into it.  Examples: A of RGBA8 = { UNORM8, 4, 3 }; A of RGBA16F =
+ *                        { FP16, 8, 6 }; A of RGBA32F = { FP32, 16, 12 }; G of RGB8 = { UNORM8, 3, 1 }; a packed R8 / R16F / R32F image = { format, 0, 0 }.
+ *                        Only bytes of [row start, row start + width * pixelStrideInBytes) of each row are read, and only the channel's own bytes are
+ *                        used: the other channels and the pitch padding may hold anything.
+ *   the texture          UNORM8 -> an ommCpuTextureFormat_UNORM8 texture of those bytes; FP32 -> an FP32 texture of those bit patterns; FP16 -> an FP32
+ *                        texture holding the exact value of each half (subnormals included; a NaN stays a NaN, its payload is not promised).
+ *                        flags and alphaCutoff are recorded as by ommCpuCreateTexture: alphaCutoff >= 0 gives the texture its summed-area table,
+ *                        ommCpuTextureFlags_DisableZOrder only changes the layout of a serialized blob.  Mips are independent allocations of any size.
+ *   memory               deviceData is device memory of the BAKER'S device (the HIP device current when the baker's first texture is created; this call
+ *                        binds it if it is the first), managed memory or pinned host memory.  Each mip's first and last byte are asked of
+ *                        hipPointerGetAttributes before anything is launched: pageable host memory, a pointer the runtime does not know, or memory
+ *                        of another device is INVALID_ARGUMENT.
+ *   stream               the reads are enqueued on `hipStream` (a hipStream_t; null = the null stream) behind whatever the caller queued there, so a
+ *                        kernel or copy on that stream that produces the image needs no synchronisation.  The call synchronises the stream before it
+ *                        returns: the texture is complete then and the source may be overwritten or freed.
+ *   result codes         as ommCpuCreateTexture where the condition is the same (null baker / desc, a baker not of CPU type, mipCount 0 or above 17, a
+ *                        width or height of 0 or above 65536, null deviceData, a channelFormat that is not one of the three) plus, each INVALID_ARGUMENT
+ *                        with a log line of its own: a stride smaller than the channel; channelOffsetInBytes + the channel's size above the stride; a
+ *                        stride, offset, pitch or pointer that is not a multiple of the channel's size (1, 4, 2 bytes); a non-zero pitch below
+ *                        width * stride.  All of this is judged before the device is touched.  Without a usable HIP device: FAILURE (there is no CPU
+ *                        fallback).  *outTexture is written on SUCCESS only. */
+typedef enum ommxTexelFormat {
+    ommxTexelFormat_UNORM8  = 0,
+    ommxTexelFormat_FP32    = 1,
+    ommxTexelFormat_FP16    = 2,   /* IEEE binary16 */
+    ommxTexelFormat_MAX_NUM = 3
+} ommxTexelFormat;
+typedef struct ommxDeviceTextureMipDesc {
+    uint32_t    width, height;
+    uint32_t    rowPitchInBytes;       /* 0 = width * pixelStrideInBytes; ALWAYS bytes (ommCpuTextureMipDesc::rowPitch counts texels for Morton-Z textures) */
+    const void* deviceData;            /* first pixel of the mip */
+} ommxDeviceTextureMipDesc;
+typedef struct ommxDeviceTextureDesc {
+    ommxTexelFormat                 channelFormat;         /* type of the ONE channel that is read */
+    uint32_t                        pixelStrideInBytes;    /* 0 = size of one channel (single-channel, packed) */
+    uint32_t                        channelOffsetInBytes;  /* of that channel inside a pixel */
+    ommCpuTextureFlags              flags;
+    const ommxDeviceTextureMipDesc* mips;                  /* mip 0 first */
+    uint32_t                        mipCount;
+    float                           alphaCutoff;           /* >= 0: the texture carries a summed-area table of alpha > alphaCutoff; < 0: none */
+} ommxDeviceTextureDesc;
+OMM_MI355X_API ommResult ommxCreateTextureDevice(ommBaker baker, const ommxDeviceTextureDesc* desc, void* hipStream, ommCpuTexture* outTexture);
+
 #endif

@@ -11,6 +11,7 @@
 #include "host_expand.h"
 #include "lookup_kernels.h"
 #include "stats_kernels.h"
+#include "texture_kernels.h"
 
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
@@ -1653,32 +1654,72 @@ OMM_MI355X_API ommResult ommDestroyBaker(ommBaker baker)
 }
 
 namespace {
+// ---- texture creation: what ommCpuCreateTexture (texels from host memory) and ommxCreateTextureDevice (a channel of an image in device memory) share ----
+// texture_impl.cpp:44-65
+template <class Mip, class DataOf>
+ommResult check_texture_mips(const Logger& L, uint32_t mipCount, bool formatSet, const Mip* mips, DataOf dataOf)
+{
+    if (mipCount == 0) return L.invalid("[Invalid Arg] - mipCount must be non-zero");
+    if (!formatSet) return L.invalid("[Invalid Arg] - format is not set");
+    for (uint32_t i = 0; i < mipCount; ++i) {
+        if (!dataOf(mips[i])) return L.invalid("[Invalid Arg] - mips.textureData is not set");
+        if (mips[i].width == 0) return L.invalid("[Invalid Arg] - mips.width must be non-zero");
+        if (mips[i].height == 0) return L.invalid("[Invalid Arg] - mips.height must be non-zero");
+        if (mips[i].width > 65536) return L.invalid("[Invalid Arg] - mips.width must be less than kMaxDim.x (65536)");
+        if (mips[i].height > 65536) return L.invalid("[Invalid Arg] - mips.height must be less than kMaxDim.y (65536)");
+    }
+    if (mipCount > (uint32_t)kMaxMips) return L.invalid("[Invalid Arg] - more than 17 mips");
+    return ommResult_SUCCESS;
+}
+
+// The Texture under construction: its mips' device memory, the summed-area tables and their pooled scratch, and the one way out.  The caller fills the
+// texels of each mip between add_mip and build_sat, on the stream it hands to build_sat, and synchronises that stream before finish.
+struct TextureBuild {
+    Baker* b; Texture* t; bool ok = true; std::vector<void*> satScratch;
+    TextureBuild(Baker* baker, ommCpuTextureFormat format, ommCpuTextureFlags flags, float alphaCutoff) : b(baker), t(baker->mem.make<Texture>()) {
+        if (!t) return;
+        t->mem = b->mem; t->log = &b->log; t->format = format; t->flags = flags; t->alphaCutoff = alphaCutoff; t->device = b->bind_device(); t->owner = b;
+    }
+    size_t texel_bytes() const { return t->format == ommCpuTextureFormat_FP32 ? 4 : 1; }
+    bool enableSAT() const { return t->alphaCutoff >= 0; } // texture_impl.cpp:91
+    // (the mip is recorded whether or not its memory could be had: ~Texture frees what exists)
+    TexMip& add_mip(uint32_t w, uint32_t h) {
+        TexMip m; m.w = (int)w; m.h = (int)h;
+        ok = ok && HIP_OK(hipMalloc(&m.texels, texel_bytes() * (size_t)m.w * (size_t)m.h));
+        t->mips.push_back(m);
+        return t->mips.back();
+    }
+    void build_sat(TexMip& m, hipStream_t stream) {
+        if (!ok || !enableSAT()) return;
+        ok = HIP_OK(hipMalloc((void**)&m.sat, sizeof(uint32_t) * (size_t)m.w * (size_t)m.h));
+        if (!ok) return;   // (the pooled scratch block goes back after the caller's synchronisation, in finish)
+        uint32_t* scratch = (uint32_t*)b->devPool->acquire(sat_scratch_bytes(m.w, m.h));
+        ok = scratch != nullptr;
+        if (ok) { satScratch.push_back(scratch); launch_sat_build(m.texels, t->format == ommCpuTextureFormat_FP32, m.sat, scratch, m.w, m.h, t->alphaCutoff, stream); ok = HIP_OK(hipGetLastError()); }
+    }
+    ommResult finish(bool synchronised, ommCpuTexture* outTexture) {
+        ok = ok && synchronised;
+        for (void* p : satScratch) b->devPool->release(p);
+        if (!ok) { (void)hipGetLastError(); b->mem.destroy(t); return b->log.failure("[Failure] - could not create the texture on the HIP device (no CPU fallback)"); }
+        *outTexture = (ommCpuTexture)((uintptr_t)t | kTexture);
+        return ommResult_SUCCESS;
+    }
+};
+
 ommResult create_texture_impl(Baker* b, const ommCpuTextureDesc* desc, ommCpuTexture* outTexture)
 {
     const Logger& L = b->log;
     const DeviceScope onBakersDevice(b->bind_device());
-    // texture_impl.cpp:44-65
-    if (desc->mipCount == 0) return L.invalid("[Invalid Arg] - mipCount must be non-zero");
-    if (desc->format == ommCpuTextureFormat_MAX_NUM) return L.invalid("[Invalid Arg] - format is not set");
-    for (uint32_t i = 0; i < desc->mipCount; ++i) {
-        if (!desc->mips[i].textureData) return L.invalid("[Invalid Arg] - mips.textureData is not set");
-        if (desc->mips[i].width == 0) return L.invalid("[Invalid Arg] - mips.width must be non-zero");
-        if (desc->mips[i].height == 0) return L.invalid("[Invalid Arg] - mips.height must be non-zero");
-        if (desc->mips[i].width > 65536) return L.invalid("[Invalid Arg] - mips.width must be less than kMaxDim.x (65536)");
-        if (desc->mips[i].height > 65536) return L.invalid("[Invalid Arg] - mips.height must be less than kMaxDim.y (65536)");
-    }
-    if (desc->mipCount > (uint32_t)kMaxMips) return L.invalid("[Invalid Arg] - more than 17 mips");
-    Texture* t = b->mem.make<Texture>();
-    if (!t) return ommResult_FAILURE;
-    t->mem = b->mem; t->log = &b->log; t->format = desc->format; t->flags = desc->flags; t->alphaCutoff = desc->alphaCutoff; t->device = b->bind_device(); t->owner = b;
+    const ommResult checked = check_texture_mips(L, desc->mipCount, desc->format != ommCpuTextureFormat_MAX_NUM, desc->mips, [](const ommCpuTextureMipDesc& m) { return m.textureData; });
+    if (checked != ommResult_SUCCESS) return checked;
+    TextureBuild tb(b, desc->format, desc->flags, desc->alphaCutoff);
+    if (!tb.t) return ommResult_FAILURE;
     const bool linear = ((uint32_t)desc->flags & (uint32_t)ommCpuTextureFlags_DisableZOrder) != 0;
-    const size_t px = desc->format == ommCpuTextureFormat_FP32 ? 4 : 1;
-    const bool enableSAT = desc->alphaCutoff >= 0; // texture_impl.cpp:91
-    bool ok = true;
-    std::vector<uint8_t> staging; std::vector<void*> satScratch;
-    for (uint32_t mi = 0; mi < desc->mipCount && ok; ++mi) {
+    const size_t px = tb.texel_bytes();
+    std::vector<uint8_t> staging;
+    for (uint32_t mi = 0; mi < desc->mipCount && tb.ok; ++mi) {
         const ommCpuTextureMipDesc& md = desc->mips[mi];
-        TexMip m; m.w = (int)md.width; m.h = (int)md.height;
+        TexMip& m = tb.add_mip(md.width, md.height);
         const size_t rowBytes = px * (size_t)m.w, bytes = rowBytes * (size_t)m.h;
         // rowPitch is in bytes for DisableZOrder textures and in texels otherwise (texture_impl.cpp:141-142,169,179)
         const size_t pitch = linear ? (md.rowPitch == 0 ? rowBytes : (size_t)md.rowPitch) : px * (md.rowPitch == 0 ? (size_t)md.width : (size_t)md.rowPitch);
@@ -1688,22 +1729,62 @@ ommResult create_texture_impl(Baker* b, const ommCpuTextureDesc* desc, ommCpuTex
             for (int j = 0; j < m.h; ++j) memcpy(staging.data() + rowBytes * (size_t)j, src + pitch * (size_t)j, rowBytes);
             src = staging.data();
         }
-        ok = HIP_OK(hipMalloc(&m.texels, bytes)) && HIP_OK(hipMemcpy(m.texels, src, bytes, hipMemcpyHostToDevice));
-        if (ok && enableSAT) {
-            ok = HIP_OK(hipMalloc((void**)&m.sat, sizeof(uint32_t) * (size_t)m.w * (size_t)m.h));
-            if (ok) {   // (null stream; the pooled scratch block goes back after the device synchronisation below)
-                uint32_t* scratch = (uint32_t*)b->devPool->acquire(sat_scratch_bytes(m.w, m.h));
-                ok = scratch != nullptr;
-                if (ok) { satScratch.push_back(scratch); launch_sat_build(m.texels, desc->format == ommCpuTextureFormat_FP32, m.sat, scratch, m.w, m.h, desc->alphaCutoff, nullptr); ok = HIP_OK(hipGetLastError()); }
-            }
-        }
-        t->mips.push_back(m);
+        tb.ok = tb.ok && HIP_OK(hipMemcpy(m.texels, src, bytes, hipMemcpyHostToDevice));
+        tb.build_sat(m, nullptr);   // (null stream)
     }
-    if (ok) ok = HIP_OK(hipDeviceSynchronize()); else (void)hipDeviceSynchronize();
-    for (void* p : satScratch) b->devPool->release(p);
-    if (!ok) { (void)hipGetLastError(); b->mem.destroy(t); return L.failure("[Failure] - could not create the texture on the HIP device (no CPU fallback)"); }
-    *outTexture = (ommCpuTexture)((uintptr_t)t | kTexture);
-    return ommResult_SUCCESS;
+    return tb.finish(HIP_OK(hipDeviceSynchronize()), outTexture);
+}
+
+// memory a kernel of device `dev` may read: device memory of that device, managed memory, pinned host memory.  Anything the runtime does not know
+// (pageable host memory, a stale pointer) or that lives on another device must never reach a launch.
+bool device_readable(const void* p, int dev)
+{
+    hipPointerAttribute_t a; memset(&a, 0, sizeof a);
+    if (!HIP_OK(hipPointerGetAttributes(&a, p))) { (void)hipGetLastError(); return false; }
+    if (a.type == hipMemoryTypeDevice) return a.device == dev;
+    return a.type == hipMemoryTypeHost || a.type == hipMemoryTypeManaged;
+}
+
+ommResult create_texture_device_impl(Baker* b, const ommxDeviceTextureDesc* desc, hipStream_t stream, ommCpuTexture* outTexture)
+{
+    const Logger& L = b->log;
+    // ---- everything that can be judged without a device ----
+    if (desc->mipCount != 0 && desc->mips == nullptr) return L.invalid("[Invalid Arg] - mips is not set");
+    const ommResult checked = check_texture_mips(L, desc->mipCount, (unsigned)desc->channelFormat < (unsigned)ommxTexelFormat_MAX_NUM, desc->mips, [](const ommxDeviceTextureMipDesc& m) { return m.deviceData; });
+    if (checked != ommResult_SUCCESS) return checked;
+    const int gatherFormat = desc->channelFormat == ommxTexelFormat_UNORM8 ? kTexGatherUnorm8 : desc->channelFormat == ommxTexelFormat_FP16 ? kTexGatherFp16 : kTexGatherFp32;
+    const uint64_t cb = tex_gather_channel_bytes(gatherFormat);
+    const uint64_t stride = desc->pixelStrideInBytes ? (uint64_t)desc->pixelStrideInBytes : cb, off = desc->channelOffsetInBytes;
+    if (stride < cb) return L.invalid("[Invalid Arg] - pixelStrideInBytes is smaller than one channel of channelFormat");
+    if (off + cb > stride) return L.invalid("[Invalid Arg] - channelOffsetInBytes + the size of the channel exceeds pixelStrideInBytes");
+    if (stride % cb != 0 || off % cb != 0) return L.invalid("[Invalid Arg] - pixelStrideInBytes and channelOffsetInBytes must be multiples of the size of the channel");
+    for (uint32_t i = 0; i < desc->mipCount; ++i) {
+        const ommxDeviceTextureMipDesc& md = desc->mips[i];
+        if (md.rowPitchInBytes != 0 && (uint64_t)md.rowPitchInBytes < (uint64_t)md.width * stride) return L.invalid("[Invalid Arg] - mips.rowPitchInBytes is smaller than width * pixelStrideInBytes");
+        if ((uint64_t)md.rowPitchInBytes % cb != 0 || (uintptr_t)md.deviceData % cb != 0) return L.invalid("[Invalid Arg] - mips.rowPitchInBytes and mips.deviceData must be multiples of the size of the channel");
+    }
+    // ---- the device ----
+    const int dev = b->bind_device();
+    int deviceCount = 0;
+    if (dev < 0 || !HIP_OK(hipGetDeviceCount(&deviceCount)) || deviceCount < 1) { (void)hipGetLastError(); return L.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)"); }
+    const DeviceScope onBakersDevice(dev);
+    for (uint32_t i = 0; i < desc->mipCount; ++i) {   // first and last byte of every mip, before any launch
+        const ommxDeviceTextureMipDesc& md = desc->mips[i];
+        const uint64_t pitch = md.rowPitchInBytes ? (uint64_t)md.rowPitchInBytes : (uint64_t)md.width * stride;
+        const uint8_t* first = (const uint8_t*)md.deviceData;
+        if (!device_readable(first, dev) || !device_readable(first + (uint64_t)(md.height - 1) * pitch + (uint64_t)md.width * stride - 1, dev))
+            return L.invalid("[Invalid Arg] - mips.deviceData is not memory the baker's device can read (device memory of that device, managed or pinned host memory)");
+    }
+    TextureBuild tb(b, desc->channelFormat == ommxTexelFormat_UNORM8 ? ommCpuTextureFormat_UNORM8 : ommCpuTextureFormat_FP32, desc->flags, desc->alphaCutoff);
+    if (!tb.t) return ommResult_FAILURE;
+    for (uint32_t mi = 0; mi < desc->mipCount && tb.ok; ++mi) {
+        const ommxDeviceTextureMipDesc& md = desc->mips[mi];
+        const uint64_t pitch = md.rowPitchInBytes ? (uint64_t)md.rowPitchInBytes : (uint64_t)md.width * stride;
+        TexMip& m = tb.add_mip(md.width, md.height);
+        if (tb.ok) { (void)launch_texture_gather(md.deviceData, (size_t)pitch, (uint32_t)stride, (uint32_t)off, gatherFormat, m.texels, m.w, m.h, stream); tb.ok = HIP_OK(hipGetLastError()); }
+        tb.build_sat(m, stream);
+    }
+    return tb.finish(HIP_OK(hipStreamSynchronize(stream)), outTexture);
 }
 } // namespace
 
@@ -1714,6 +1795,18 @@ OMM_MI355X_API ommResult ommCpuCreateTexture(ommBaker baker, const ommCpuTexture
     if (desc == 0) return b->log.invalid("texture desc was not set");
     if (tag_of(baker) != kCpuBaker) return b->log.invalid("Baker was not created as the right type");
     return guarded(&b->log, [&] { return create_texture_impl(b, desc, outTexture); });
+}
+
+// A texture from one channel of an image that is already in device memory (include/omm_mi355x_ext.h): the gather kernel of texture_kernels.hip in place of
+// the host staging and the upload, everything behind it as for ommCpuCreateTexture.
+OMM_MI355X_API ommResult ommxCreateTextureDevice(ommBaker baker, const ommxDeviceTextureDesc* desc, void* hipStream, ommCpuTexture* outTexture)
+{
+    if (baker == 0) return ommResult_INVALID_ARGUMENT;
+    Baker* b = untag<Baker>(baker);
+    if (desc == 0) return b->log.invalid("texture desc was not set");
+    if (tag_of(baker) != kCpuBaker) return b->log.invalid("Baker was not created as the right type");
+    if (outTexture == nullptr) return b->log.invalid("[Invalid Arg] - outTexture is not set");
+    return guarded(&b->log, [&] { return create_texture_device_impl(b, desc, (hipStream_t)hipStream, outTexture); });
 }
 
 OMM_MI355X_API ommResult ommCpuGetTextureDesc(ommCpuTexture texture, ommCpuTextureDesc* outDesc)
