@@ -1,0 +1,131 @@
+// bake_host.h -- the host-side rules of a bake that need no device: flag bits, index formats, the raw triangle upload, histogram lists, the result descriptor
+// and the carve of the working set.  Plain C++ (no HIP): omm_host.cpp calls each directly, tests/native/bake_host_check.cpp runs them under sanitizers.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include "../../include/omm_mi355x.h"
+
+namespace ommx {
+struct SetupCounters;   // bake_kernels.h (only pointed at here)
+
+// constants of the kernel headers, restated so that this header stands alone; omm_host.cpp asserts each against its origin
+constexpr int kBakeLevels = 13;                 // kNumLevels
+constexpr size_t kBakeFineWords = 256 * 16;     // kFineSlots * kFineStride
+constexpr size_t kBakeMaxRanks = 16, kBakePreviewSlotBytes = 256, kBakeStreamCtlWords = 100;   // kMaxRanks, kPreviewSlotBytes, kStreamCtlWords
+constexpr size_t kBakeCountersSlot = 256;       // arena slot of SetupCounters: BakeHead (omm_host.cpp) fills it and the digest table behind it in ONE copy
+inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// ---- bake flags: bits 0-6 by their public ommCpuBakeFlags_* names, the internal ones (bake_cpu_impl.cpp:43-48) named here ----
+constexpr uint32_t kBakeFlag_EnableAABBTesting = 1u << 7;              // bake_cpu_impl.cpp:43
+constexpr uint32_t kBakeFlag_DisableLevelLineIntersection = 1u << 8;   // bake_cpu_impl.cpp:44
+constexpr uint32_t kBakeFlag_DisableFineClassification = 1u << 9;      // bake_cpu_impl.cpp:45
+constexpr uint32_t kBakeFlag_NearDuplicateBruteForce = 1u << 10;       // bake_cpu_impl.cpp:46
+constexpr uint32_t kBakeFlag_EnableEdgeHeuristic = 1u << 11;           // bake_cpu_impl.cpp:48
+inline bool has_flag(uint32_t flags, uint32_t bit) { return (flags & bit) != 0; }
+// near-duplicate merging / a size budget: the reference's serial reducers, run on the host over the classified states (host_tail.cpp)
+inline bool wants_host_tail(const ommCpuBakeInputDesc& d)
+{
+    return has_flag((uint32_t)d.bakeFlags, ommCpuBakeFlags_EnableNearDuplicateDetection | kBakeFlag_NearDuplicateBruteForce) || d.maxArrayDataSize != 0xFFFFFFFFu;
+}
+// no fine pass with the 2-state format: unresolved micro-triangles keep UnknownOpaque (3), which has no 1-bit form (bake_cpu_impl.cpp:1811)
+inline bool no_fine_two_state(const ommCpuBakeInputDesc& d) { return has_flag((uint32_t)d.bakeFlags, kBakeFlag_DisableFineClassification) && d.format == ommFormat_OC1_2_State; }
+
+// ---- index formats: the result's depends on the triangle count alone, the reference narrows int32 to int8 / int16 (bake_cpu_impl.cpp:1872-1902) ----
+inline ommIndexFormat index_format_for(uint32_t numTris, uint32_t flags)
+{
+    if (has_flag(flags, ommCpuBakeFlags_Force32BitIndices)) return ommIndexFormat_UINT_32;
+    if (has_flag(flags, ommCpuBakeFlags_Allow8BitIndices) && numTris <= INT8_MAX) return ommIndexFormat_UINT_8;
+    return numTris <= INT16_MAX ? ommIndexFormat_UINT_16 : ommIndexFormat_UINT_32;
+}
+inline size_t index_bytes(ommIndexFormat f) { return f == ommIndexFormat_UINT_8 ? 1 : (f == ommIndexFormat_UINT_16 ? 2 : 4); }
+
+// ---- the caller's raw triangle data as one device block: texture coordinates | indices | per-triangle levels, each from a 256-byte boundary ----
+inline size_t uv_element_bytes(ommTexCoordFormat f) { return f == ommTexCoordFormat_UV32_FLOAT ? 8 : 4; }
+inline uint32_t uv_stride(const ommCpuBakeInputDesc& d) { return d.texCoordStrideInBytes ? d.texCoordStrideInBytes : (uint32_t)uv_element_bytes(d.texCoordFormat); }
+struct RawInputLayout { size_t uvBytes, idxBytes, lvlBytes, offUv, offIdx, offLvl, total; };   // total: with 256 bytes of slack behind the last region
+// (the C ABI gives no vertex count: it is max(index) + 1, as serialize_impl.cpp:60-79)
+inline RawInputLayout raw_input_layout(const ommCpuBakeInputDesc& d, uint32_t numTris, uint32_t maxIndex)
+{
+    RawInputLayout L;
+    L.uvBytes = numTris ? (size_t)uv_stride(d) * maxIndex + uv_element_bytes(d.texCoordFormat) : 0;
+    L.idxBytes = index_bytes(d.indexFormat) * 3 * (size_t)numTris;
+    L.lvlBytes = d.subdivisionLevels ? numTris : 0;
+    L.offUv = 0; L.offIdx = pad256(L.uvBytes); L.offLvl = L.offIdx + pad256(L.idxBytes);
+    L.total = L.offLvl + pad256(L.lvlBytes) + 256;
+    return L;
+}
+
+// ---- histograms: format {2-state, 4-state} x level ascending, non-zero entries only (bake_cpu_impl.cpp:1833-1850); one global format per bake ----
+// hist: kBakeLevels counts of the OMM array, then kBakeLevels of the index buffer; the lists hold up to 2 * kBakeLevels entries
+inline void compact_histograms(const uint32_t* hist, int bits, ommCpuOpacityMicromapUsageCount* outArray, ommCpuOpacityMicromapUsageCount* outIndex, uint32_t* nArray, uint32_t* nIndex)
+{
+    *nArray = 0; *nIndex = 0;
+    for (int l = 0; l < kBakeLevels; ++l) {
+        if (hist[l]) outArray[(*nArray)++] = ommCpuOpacityMicromapUsageCount{ hist[l], (uint16_t)l, (uint16_t)bits };
+        if (hist[kBakeLevels + l]) outIndex[(*nIndex)++] = ommCpuOpacityMicromapUsageCount{ hist[kBakeLevels + l], (uint16_t)l, (uint16_t)bits };
+    }
+}
+inline uint32_t clamp_hist_count(size_t n) { return n < 2 * (size_t)kBakeLevels ? (uint32_t)n : 2u * (uint32_t)kBakeLevels; }
+// The one place that writes an ommCpuBakeResultDesc.  A bake without OMMs reports null arrays of size zero whatever the caller holds; the histogram
+// lists are the caller's arrays of 2 * kBakeLevels entries: their counts are clamped to that.
+inline void fill_result_desc(ommCpuBakeResultDesc* out, const void* arrayData, uint64_t arrayDataSize, const ommCpuOpacityMicromapDesc* descs, uint32_t numDescs,
+                             const void* indexBuffer, uint32_t numTris, ommIndexFormat indexFormat,
+                             const ommCpuOpacityMicromapUsageCount* arrayHist, size_t numArrayHist, const ommCpuOpacityMicromapUsageCount* indexHist, size_t numIndexHist)
+{
+    out->arrayData = numDescs ? arrayData : nullptr; out->arrayDataSize = numDescs ? (uint32_t)arrayDataSize : 0;
+    out->descArray = numDescs ? descs : nullptr; out->descArrayCount = numDescs;
+    out->descArrayHistogram = arrayHist; out->descArrayHistogramCount = clamp_hist_count(numArrayHist);
+    out->indexBuffer = indexBuffer; out->indexCount = numTris; out->indexFormat = indexFormat;
+    out->indexHistogram = indexHist; out->indexHistogramCount = clamp_hist_count(numIndexHist);
+}
+// micro-triangles of a bake: 4^level per work item (levelCount: SetupCounters)
+inline uint64_t micro_triangles_of(const uint32_t* levelCount) { uint64_t n = 0; for (int l = 0; l < kBakeLevels; ++l) n += (uint64_t)levelCount[l] << (2 * l); return n; }
+
+// ---- the working set of a bake (worst case: every triangle is its own work item) ----
+// ONE function walks the slots in order over a bump cursor: from base 0 it gives the bytes to reserve (`bytes`; the pointers are then offsets), from the arena's
+// base the pointers.  Two contracts rest on the order: `uniformDigest` lies kBakeCountersSlot behind `counters` (one host-to-device copy fills both), and
+// `arrayHist`, `indexHist`, `err`, `fine` are consecutive (one device-to-host copy reads them back).
+struct BakeTables {
+    float* uv; uint8_t *level, *degen, *active; uint64_t *stateOfs, *digests; uint32_t *itemIds, *activeIds; int32_t *triToItem, *index;
+    uint32_t *mask, *known; int32_t* special; uint32_t *rep, *order, *dstOfs, *sizes; int32_t* itemValue; float* triArea;
+    SetupCounters* counters; uint64_t* uniformDigest; uint32_t *arrayHist, *indexHist, *err; unsigned long long* fine;   // fine: striped statistic counter (bake_types.h)
+    uint8_t* scratch; size_t scratchBytes;   // setup / tail / stream scratch
+    uint32_t* meta; uint8_t* owner; uint64_t *cofs, *totals;   // sharded bake: metadata words of the active items, owner rank, offsets in the contributions, bytes per rank
+    // streamed result: placed offset per item, cursor + control words; preview: collapsed UVs, 256-byte state slots, offsets, masks, early flags
+    uint64_t* placed; unsigned long long* cursor; uint32_t* streamCtl;
+    float* uv2; uint8_t* states2; uint64_t* ofs2; uint32_t* mask2; uint8_t* early; uint32_t *earlyList, *earlyLead; unsigned long long* fine2;
+    size_t bytes;   // end of the last slot, from the base
+    size_t readback_bytes() const { return (size_t)((uintptr_t)fine - (uintptr_t)arrayHist) + kBakeFineWords * sizeof(unsigned long long); }   // [arrayHist, end of fine)
+};
+struct CarveCursor {   // (an integer, not a pointer: the sizing pass has no memory to point into)
+    uintptr_t at;
+    template <class T> T* take(size_t count) { T* p = reinterpret_cast<T*>(at); at += pad256(count * sizeof(T)); return p; }
+};
+inline BakeTables carve_bake_tables(uintptr_t base, uint32_t maxItems, size_t scratchBytes, bool sharded, bool streamed)
+{
+    BakeTables t = BakeTables(); CarveCursor c{ base }; const size_t n = maxItems;
+    t.uv = c.take<float>(n * 6);
+    t.level = c.take<uint8_t>(n); t.degen = c.take<uint8_t>(n); t.active = c.take<uint8_t>(n);
+    t.stateOfs = c.take<uint64_t>(n); t.digests = c.take<uint64_t>(n);
+    t.itemIds = c.take<uint32_t>(n); t.activeIds = c.take<uint32_t>(n);
+    t.triToItem = c.take<int32_t>(n); t.index = c.take<int32_t>(n);
+    t.mask = c.take<uint32_t>(n); t.known = c.take<uint32_t>(n);
+    t.special = c.take<int32_t>(n); t.rep = c.take<uint32_t>(n);
+    t.order = c.take<uint32_t>(n); t.dstOfs = c.take<uint32_t>(n);
+    t.sizes = c.take<uint32_t>(n); t.itemValue = c.take<int32_t>(n);
+    t.triArea = c.take<float>(n);
+    t.counters = reinterpret_cast<SetupCounters*>(c.take<uint8_t>(kBakeCountersSlot));
+    t.uniformDigest = c.take<uint64_t>((size_t)kBakeLevels * 4);
+    t.arrayHist = c.take<uint32_t>(kBakeLevels); t.indexHist = c.take<uint32_t>(kBakeLevels); t.err = c.take<uint32_t>(1);
+    t.fine = c.take<unsigned long long>(kBakeFineWords);
+    t.scratch = c.take<uint8_t>(scratchBytes); t.scratchBytes = scratchBytes;
+    if (sharded) { t.meta = c.take<uint32_t>(n * 4); t.owner = c.take<uint8_t>(n); t.cofs = c.take<uint64_t>(n); t.totals = c.take<uint64_t>(kBakeMaxRanks); }
+    if (streamed) {
+        t.placed = c.take<uint64_t>(n); t.cursor = c.take<unsigned long long>(1); t.streamCtl = c.take<uint32_t>(kBakeStreamCtlWords);
+        t.uv2 = c.take<float>(n * 6); t.states2 = c.take<uint8_t>(n * kBakePreviewSlotBytes); t.ofs2 = c.take<uint64_t>(n);
+        t.mask2 = c.take<uint32_t>(n); t.early = c.take<uint8_t>(n); t.earlyList = c.take<uint32_t>(n); t.earlyLead = c.take<uint32_t>(n); t.fine2 = c.take<unsigned long long>(kBakeFineWords);
+    }
+    t.bytes = (size_t)(c.at - base);
+    return t;
+}
+} // namespace ommx

@@ -7,6 +7,7 @@
 #include "../../include/omm_mi355x_ext.h"
 #include "bake_types.h"
 #include "bake_kernels.h"
+#include "bake_host.h"
 #include "host_tail.h"
 #include "host_expand.h"
 #include "lookup_kernels.h"
@@ -128,7 +129,6 @@ struct DeviceArena {
         T* p = (T*)(base + used); used += bytes; return p;
     }
 };
-inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // The device working set of one bake in flight: per-item tables + scratch, packed states + tile queue, and (sharded bakes) the exchange
 // buffers.  A baker keeps a small pool of these sets: a bake takes one for its duration -- concurrent bakes on one baker get different
@@ -383,6 +383,16 @@ struct Baker {
     Baker() { for (auto& k : knobs) k.store(0); }
     uint64_t knob(ommxBakerKnob k) const { return knobs[k].load(std::memory_order_relaxed); }
 };
+void store_timings(Baker& b, const ommxBakeTimings& tm) { std::lock_guard<std::mutex> g(b.timingsMu); b.timings = tm; b.haveTimings = true; }
+// helper threads of an expansion: three quarters of the CPUs the process may use, at most 12 -- the probe's rate is flat from 12 threads on, and a process that runs
+// as many busy threads as its cgroup quota allows is throttled for the rest of the scheduler period as soon as anything else (the HIP runtime's threads, the
+// caller's) runs beside them: measured 6 - 19 ms per expansion with 16 threads on 16 CPUs of quota (ommxBakerKnob_ExpandThreads overrides)
+unsigned expand_thread_count(const Baker& b)
+{
+    if (const uint64_t k = b.knob(ommxBakerKnob_ExpandThreads)) return (unsigned)k;
+    const unsigned n = effective_cpus() * 3u / 4u;
+    return n > 12u ? 12u : (n < 1u ? 1u : n);
+}
 
 // HIP events on the bake's own stream (torch / the caller never see this stream)
 struct EventTimer {
@@ -417,6 +427,21 @@ struct BakeResult {
     BakeResult() { memset(&desc, 0, sizeof desc); }
     ~BakeResult() { if (pool) pool->release(arrayData); else mem.release(arrayData); mem.release(descs); mem.release(arrayHist); mem.release(indexHist); mem.release(index); mem.release(triArea); }
 };
+// Whatever a host BakeResult still lacks of its arrays: arrayData and descriptors of E OMMs, index buffer, triangle areas, the two histogram lists.
+// (ommCpuBake's main path arrives with all but the histograms: ArrayAlloc places its array, the others are allocated ahead of the copies that fill them.)
+ommResult alloc_host_result(Baker& baker, BakeResult* res, uint32_t E, size_t arrayBytes, uint32_t T)
+{
+    const Allocator& mem = baker.mem;
+    if (E && !res->arrayData) res->arrayData = mem.allocate(arrayBytes, 64);
+    if (E && !res->descs) res->descs = (ommCpuOpacityMicromapDesc*)mem.allocate(sizeof(ommCpuOpacityMicromapDesc) * (size_t)E, 16);
+    if (!res->index) res->index = (int32_t*)mem.allocate(sizeof(int32_t) * (size_t)(T ? T : 1), 16);
+    if (!res->triArea) res->triArea = (float*)mem.allocate(sizeof(float) * (size_t)(T ? T : 1), 16);
+    if (!res->arrayHist) res->arrayHist = (ommCpuOpacityMicromapUsageCount*)mem.allocate(sizeof(ommCpuOpacityMicromapUsageCount) * 2 * kNumLevels, 16);
+    if (!res->indexHist) res->indexHist = (ommCpuOpacityMicromapUsageCount*)mem.allocate(sizeof(ommCpuOpacityMicromapUsageCount) * 2 * kNumLevels, 16);
+    if ((E && (!res->arrayData || !res->descs)) || !res->index || !res->triArea || !res->arrayHist || !res->indexHist)
+        return baker.log.failure("[Failure] - the memory allocator returned null for the bake result");
+    return ommResult_SUCCESS;
+}
 
 // ---- XXH64 of a constant byte stream: digests of uniform OMMs (bake_cpu_impl.cpp:1038-1040 applied to 4^level equal bytes) ----
 struct UniformDigests {
@@ -451,7 +476,9 @@ const UniformDigests& uniform_digests() { static const UniformDigests t; return 
 // what a bake's first transfer carries: the zeroed counters block (its 256-byte arena slot) and, in the slot behind it, the digest table -- one copy instead
 // of a copy and a fill (two fill launches: 200 bytes are not a multiple of 16)
 struct BakeHead { uint8_t counters[256]; uint64_t uniform[kNumLevels * 4]; BakeHead() { memset(counters, 0, sizeof counters); memcpy(uniform, uniform_digests().v, sizeof uniform); } };
-static_assert(sizeof(SetupCounters) <= 256, "the counters block must fit its arena slot");
+static_assert(sizeof(SetupCounters) <= kBakeCountersSlot && sizeof(BakeHead) == kBakeCountersSlot + sizeof(uint64_t) * kNumLevels * 4, "the counters block must fit its arena slot, the digest table the one behind it");
+static_assert(kBakeLevels == kNumLevels && kBakeFineWords == (size_t)kFineSlots * kFineStride && kBakeMaxRanks == (size_t)kMaxRanks && kBakePreviewSlotBytes == kPreviewSlotBytes && kBakeStreamCtlWords == kStreamCtlWords,
+              "bake_host.h restates these constants of the kernel headers");
 const BakeHead& bake_head() { static const BakeHead h; return h; }
 
 // ---- x86 conversion semantics used by the reference's host-side arithmetic ----
@@ -480,7 +507,7 @@ int32_t level_for_primitive(const ommCpuBakeInputDesc& d, uint32_t flags, uint32
     if (!(d.dynamicSubdivisionScale > 0)) return d.maxSubdivisionLevel;
     const float fw = (float)(uint32_t)w, fh = (float)(uint32_t)h;
     const float* p = t.p;
-    if (tri_degenerate(t) || (flags & (1u << 11))) { // edge heuristic (glibc log2f, stays on the host)
+    if (tri_degenerate(t) || has_flag(flags, kBakeFlag_EnableEdgeHeuristic)) { // edge heuristic (glibc log2f, stays on the host)
         const float e0x = fw * (p[2] - p[0]), e0y = fh * (p[3] - p[1]);
         const float e1x = fw * (p[4] - p[0]), e1y = fh * (p[5] - p[1]);
         const float e2x = fw * (p[4] - p[2]), e2y = fh * (p[5] - p[3]);
@@ -528,9 +555,9 @@ ommResult validate_desc(const Baker& b, const ommCpuBakeInputDesc& d)
         snprintf(buf, sizeof buf, "[Invalid Argument] - maxSubdivisionLevel (%d) is greater than maximum supported (%d)", d.maxSubdivisionLevel, kMaxLevel);
         return L.invalid(buf);
     }
-    if ((flags & ((1u << 4) | (1u << 10))) && (flags & (1u << 3)))
+    if ((flags & (ommCpuBakeFlags_EnableNearDuplicateDetection | kBakeFlag_NearDuplicateBruteForce)) && has_flag(flags, ommCpuBakeFlags_DisableDuplicateDetection))
         return L.invalid("[Invalid Argument] - EnableNearDuplicateDetection or EnableNearDuplicateDetectionBruteForce is used together with DisableDuplicateDetection");
-    if ((flags & (1u << 5)) && !L.has())
+    if (has_flag(flags, ommCpuBakeFlags_EnableValidation) && !L.has())
         return L.invalid("[Invalid Argument] - EnableValidation is set but no message callback was provided");
     const Texture* tex = untag<Texture>(d.texture);
     if (tex->alphaCutoff >= 0.f && tex->alphaCutoff != d.alphaCutoff) {
@@ -592,16 +619,15 @@ struct ShardCtx {
     ShardBounds bounds;
     TailInputs ti; TailOutputs to; TailCounts counts;
     SetupCounters hc;
-    uint8_t *dStates = nullptr, *dActive = nullptr, *dLevel = nullptr, *dScratch = nullptr; uint64_t* dStateOfs = nullptr; uint32_t *dMask = nullptr, *dActiveIds = nullptr;
-    int32_t* dIndex = nullptr; uint32_t *dArrayHist = nullptr, *dIndexHist = nullptr;
-    size_t scratchBytes = 0; uint32_t flags = 0, T = 0; int bits = 2; bool asyncBegin = false;
+    BakeTables tab = BakeTables();   // the working set bake_core carved from the session's tables arena (bake_host.h): phases 2 and 3 read through it
+    uint8_t* dStates = nullptr;      // (from the states arena)
+    uint32_t flags = 0, T = 0; int bits = 2; bool asyncBegin = false;
     bool mergeStates = false;   // host-tail bakes: the packed states are zeroed first so that a SUM all-reduce over them is a merge
     int ev[5] = { -1, -1, -1, -1, -1 };   // HIP event marks of Begin: setup | triage | classify | digest
-    // exchange buffers: carved from the session's arenas (tables: dMeta .. dTotals; xchg: contribution + gather staging), nothing to free
-    uint32_t* dMeta = nullptr; uint8_t* dOwner = nullptr; uint64_t *dCofs = nullptr, *dTotals = nullptr; uint8_t *dContrib = nullptr, *dGathered = nullptr;
+    // exchange buffers: carved from the session's arenas (tables: tab.meta .. tab.totals; xchg: contribution + gather staging), nothing to free
+    uint8_t *dContrib = nullptr, *dGathered = nullptr;
     uint8_t *dComp = nullptr, *dGatherComp = nullptr, *dCodecScratch = nullptr; uint32_t* dCompSize = nullptr; uint64_t compCap = 0; size_t codecScratchBytes = 0;   // block exchange codec (RCCL path): own stream, all ranks' streams, own size word, count / scan scratch
     uint64_t totals[kMaxRanks]; uint64_t strideBytes = 0;
-    const float* dTriArea = nullptr;   // per-triangle UV areas in the session's arena (ommDebugGetStats2's side channel)
 };
 
 // opt-in lossy reducers (near-duplicate merge, maxArrayDataSize): classification on the device, serial tail on the host
@@ -721,15 +747,14 @@ ommResult gather_host_items(const Logger& L, hipStream_t stream, uint32_t U, uin
 ommResult run_host_tail_for(const ommCpuBakeInputDesc& d, uint32_t T, std::vector<HostItem>& items, HostTailResult& hres, ommIndexFormat& ifmt)
 {
     const uint32_t fl = (uint32_t)d.bakeFlags;
-    HostTailDesc td; td.format = (int)d.format; td.disableSpecial = (fl & (1u << 1)) != 0; td.disableDedup = (fl & (1u << 3)) != 0;
-    td.nearDup = (fl & (1u << 4)) != 0; td.nearDupBrute = (fl & (1u << 10)) != 0; td.rejectionThreshold = d.rejectionThreshold;
+    HostTailDesc td; td.format = (int)d.format; td.disableSpecial = has_flag(fl, ommCpuBakeFlags_DisableSpecialIndices); td.disableDedup = has_flag(fl, ommCpuBakeFlags_DisableDuplicateDetection);
+    td.nearDup = has_flag(fl, ommCpuBakeFlags_EnableNearDuplicateDetection); td.nearDupBrute = has_flag(fl, kBakeFlag_NearDuplicateBruteForce); td.rejectionThreshold = d.rejectionThreshold;
     td.nearDupFactor = d.nearDuplicateDeduplicationFactor; td.maxArrayDataSize = d.maxArrayDataSize; td.numTris = T; td.unresolved = (int32_t)d.unresolvedTriState;
     if (run_host_tail(td, items, hres)) return ommResult_FAILURE;
     hres.index.resize(T ? T : 1);
-    ifmt = ommIndexFormat_UINT_32;
-    const bool allow8 = (fl & (1u << 6)) != 0, force32 = (fl & (1u << 2)) != 0;
-    if (allow8 && T <= 127 && !force32) { int8_t* p8 = (int8_t*)hres.index.data(); for (uint32_t i = 0; i < T; ++i) { const int32_t v = hres.index[i]; p8[i] = (int8_t)v; } ifmt = ommIndexFormat_UINT_8; }
-    else if (T <= 32767 && !force32) { int16_t* p16 = (int16_t*)hres.index.data(); for (uint32_t i = 0; i < T; ++i) { const int32_t v = hres.index[i]; p16[i] = (int16_t)v; } ifmt = ommIndexFormat_UINT_16; }
+    ifmt = index_format_for(T, fl);
+    if (ifmt == ommIndexFormat_UINT_8) { int8_t* p8 = (int8_t*)hres.index.data(); for (uint32_t i = 0; i < T; ++i) { const int32_t v = hres.index[i]; p8[i] = (int8_t)v; } }
+    else if (ifmt == ommIndexFormat_UINT_16) { int16_t* p16 = (int16_t*)hres.index.data(); for (uint32_t i = 0; i < T; ++i) { const int32_t v = hres.index[i]; p16[i] = (int16_t)v; } }
     return ommResult_SUCCESS;
 }
 
@@ -749,69 +774,42 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
     // DisableFineClassification with the 2-state format (internal flag bit 9): unresolved micro-triangles keep UnknownOpaque (3), which has no 1-bit form -- the
     // reference digests the unpacked states and ORs `3 << (i & 7)` into the packed bytes (bake_cpu_impl.cpp:1811).  The states are therefore kept in the
     // 2-bit packing up to the final gather, which applies that rule (launch_gather_omms: storeBits != bits).
-    const int storeBits = (bits == 1 && (flags & (1u << 9))) ? 2 : bits;
+    const int storeBits = no_fine_two_state(d) ? 2 : bits;
     const uint32_t maxItems = T ? T : 1;
 
     // ---- device layout (worst case: every triangle is its own work item) ----
     const size_t setupBytes = setup_scratch_bytes(T), tailBytes = tail_scratch_bytes(maxItems, T), streamScratch = so ? stream_scratch_bytes(maxItems) : 0;
     const size_t scratchBytes = std::max(std::max(setupBytes, tailBytes), streamScratch);
-    const size_t i32 = pad256((size_t)maxItems * 4), i64 = pad256((size_t)maxItems * 8);
-    const size_t shardBytes = sh ? pad256((size_t)maxItems * 16) + pad256(maxItems) + i64 + pad256(sizeof(uint64_t) * kMaxRanks) : 0;
-    // streamed result: placed offset per item, cursor + control words; preview: collapsed UVs, 16-byte state slots, offsets, masks, early flags
-    const size_t streamBytes = so ? i64 + 512 + pad256((size_t)maxItems * 24) + pad256((size_t)maxItems * kPreviewSlotBytes) + i64 + i32 * 3 + pad256(maxItems) + pad256(sizeof(unsigned long long) * kFineSlots * kFineStride) : 0;
-    const size_t need = pad256((size_t)maxItems * 24) + 3 * pad256(maxItems) + i64 * 2 + i32 * 13 + pad256(sizeof(SetupCounters)) + 4096 + pad256(sizeof(unsigned long long) * kFineSlots * kFineStride) + pad256(scratchBytes) + shardBytes + streamBytes;
-    if (!arena->reserve(need)) return L.failure("[Failure] - out of device memory for the bake working set");
-    float* dUv = arena->take<float>((size_t)maxItems * 6);
-    uint8_t* dLevel = arena->take<uint8_t>(maxItems); uint8_t* dDegen = arena->take<uint8_t>(maxItems); uint8_t* dActive = arena->take<uint8_t>(maxItems);
-    uint64_t* dStateOfs = arena->take<uint64_t>(maxItems); uint64_t* dDigests = arena->take<uint64_t>(maxItems);
-    uint32_t* dItemIds = arena->take<uint32_t>(maxItems); uint32_t* dActiveIds = arena->take<uint32_t>(maxItems);
-    int32_t* dTriToItem = arena->take<int32_t>(maxItems); int32_t* dIndex = arena->take<int32_t>(maxItems);
-    uint32_t* dMask = arena->take<uint32_t>(maxItems); uint32_t* dKnown = arena->take<uint32_t>(maxItems);
-    int32_t* dSpecial = arena->take<int32_t>(maxItems); uint32_t* dRep = arena->take<uint32_t>(maxItems);
-    uint32_t* dOrder = arena->take<uint32_t>(maxItems); uint32_t* dDstOfs = arena->take<uint32_t>(maxItems);
-    uint32_t* dSizes = arena->take<uint32_t>(maxItems); int32_t* dItemValue = arena->take<int32_t>(maxItems);
-    float* dTriArea = arena->take<float>(maxItems); R.triAreaScratch = dTriArea;
-    SetupCounters* dCounters = arena->take<SetupCounters>(1);
-    uint64_t* dUniformDigest = arena->take<uint64_t>(kNumLevels * 4);
-    uint32_t* dArrayHist = arena->take<uint32_t>(kNumLevels); uint32_t* dIndexHist = arena->take<uint32_t>(kNumLevels); uint32_t* dErr = arena->take<uint32_t>(1);
-    unsigned long long* dFine = arena->take<unsigned long long>(kFineSlots * kFineStride); // striped statistic counter (bake_types.h)
-    uint8_t* dScratch = arena->take<uint8_t>(scratchBytes);
-    if (sh) { sh->dMeta = arena->take<uint32_t>((size_t)maxItems * 4); sh->dOwner = arena->take<uint8_t>(maxItems); sh->dCofs = arena->take<uint64_t>(maxItems); sh->dTotals = arena->take<uint64_t>(kMaxRanks); }
-    uint64_t* dPlaced = nullptr; unsigned long long* dCursor = nullptr; uint32_t* dStreamCtl = nullptr;
-    float* dUv2 = nullptr; uint8_t *dStates2 = nullptr, *dEarly = nullptr; uint32_t *dEarlyList = nullptr, *dEarlyLead = nullptr; uint64_t* dOfs2 = nullptr; uint32_t* dMask2 = nullptr; unsigned long long* dFine2 = nullptr;
-    if (so) {
-        dPlaced = arena->take<uint64_t>(maxItems); dCursor = arena->take<unsigned long long>(1); dStreamCtl = arena->take<uint32_t>(kStreamCtlWords);
-        dUv2 = arena->take<float>((size_t)maxItems * 6); dStates2 = arena->take<uint8_t>((size_t)maxItems * kPreviewSlotBytes); dOfs2 = arena->take<uint64_t>(maxItems);
-        dMask2 = arena->take<uint32_t>(maxItems); dEarly = arena->take<uint8_t>(maxItems); dEarlyList = arena->take<uint32_t>(maxItems); dEarlyLead = arena->take<uint32_t>(maxItems); dFine2 = arena->take<unsigned long long>(kFineSlots * kFineStride);
-    }
-    if (arena->used > arena->cap) return L.failure("[Failure] - internal error: the working-set layout exceeds its reservation");
+    // size and pointers from the same traversal (bake_host.h): first over offsets, then over the arena
+    if (!arena->reserve(carve_bake_tables(0, maxItems, scratchBytes, sh != nullptr, so != nullptr).bytes)) return L.failure("[Failure] - out of device memory for the bake working set");
+    const BakeTables tab = carve_bake_tables((uintptr_t)arena->base, maxItems, scratchBytes, sh != nullptr, so != nullptr);
+    R.triAreaScratch = tab.triArea;
 
     // ---- SetupWorkItems (bake_cpu_impl.cpp:589-660) on the device ----
     const double coreT0 = now_ms();
     const int e0 = et.mark();
     SetupParams S; memset(&S, 0, sizeof S);
     S.texCoords = din.texCoords; S.indices = din.indices; S.perTriLevels = din.perTriLevels;
-    S.stride = d.texCoordStrideInBytes ? d.texCoordStrideInBytes : (d.texCoordFormat == ommTexCoordFormat_UV32_FLOAT ? 8u : 4u);
+    S.stride = uv_stride(d);
     S.uvFormat = d.texCoordFormat; S.indexFormat = d.indexFormat; S.numTris = T;
-    S.globalLevel = d.maxSubdivisionLevel; S.dynScale = d.dynamicSubdivisionScale; S.edgeHeuristic = (flags & (1u << 11)) != 0;   // (EnableEdgeHeuristic, bake_cpu_impl.cpp:48,547)
-    S.texW = tex.mips[0].w; S.texH = tex.mips[0].h; S.disableDedup = (flags & (1u << 3)) != 0;
+    S.globalLevel = d.maxSubdivisionLevel; S.dynScale = d.dynamicSubdivisionScale; S.edgeHeuristic = has_flag(flags, kBakeFlag_EnableEdgeHeuristic);   // (bake_cpu_impl.cpp:48,547)
+    S.texW = tex.mips[0].w; S.texH = tex.mips[0].h; S.disableDedup = has_flag(flags, ommCpuBakeFlags_DisableDuplicateDetection);
     S.wantWorkload = 1;   // (also the input of the two shape decisions below: streamed result, deferred generic pass)
-    S.degenerateInvalid = (flags & (1u << 8)) != 0;
-    const bool checkWorkload = ((flags & (1u << 5)) != 0) || d.maxWorkloadSize != 0xFFFFFFFFFFFFFFFFull;
+    S.degenerateInvalid = has_flag(flags, kBakeFlag_DisableLevelLineIntersection);
+    const bool checkWorkload = has_flag(flags, ommCpuBakeFlags_EnableWorkloadValidation) || d.maxWorkloadSize != 0xFFFFFFFFFFFFFFFFull;
     S.format = (int)d.format;   // (per-triangle formats other than the global one are refused above: one format per bake)
-    bool ok = (const uint8_t*)dUniformDigest == (const uint8_t*)dCounters + 256   // (adjacent arena slots: see BakeHead)
-           && HIP_OK(hipMemcpyAsync(dCounters, &bake_head(), sizeof(BakeHead), hipMemcpyHostToDevice, stream));
-    ok = ok && HIP_OK(run_setup_fetch(S, dScratch, scratchBytes, dCounters, dKnown, maxItems, (uint32_t*)dFine, 2u * kFineSlots * kFineStride, dTriArea, stream));
+    bool ok = HIP_OK(hipMemcpyAsync(tab.counters, &bake_head(), sizeof(BakeHead), hipMemcpyHostToDevice, stream));   // (counters and digest table are adjacent slots of the carve: see BakeHead)
+    ok = ok && HIP_OK(run_setup_fetch(S, tab.scratch, tab.scratchBytes, tab.counters, tab.known, maxItems, (uint32_t*)tab.fine, 2u * kFineSlots * kFineStride, tab.triArea, stream));
     if (!ok) return L.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)");
     SetupCounters hc; memset(&hc, 0, sizeof hc);
     if (d.dynamicSubdivisionScale > 0.f && T) { // degenerate triangles under dynamic subdivision need glibc's log2f: host (bake_cpu_impl.cpp:511-528)
-        if (!HIP_OK(hipMemcpyAsync(&hc, dCounters, sizeof hc, hipMemcpyDeviceToHost, stream)) || !HIP_OK(hipStreamSynchronize(stream)))
+        if (!HIP_OK(hipMemcpyAsync(&hc, tab.counters, sizeof hc, hipMemcpyDeviceToHost, stream)) || !HIP_OK(hipStreamSynchronize(stream)))
             return L.failure("[Failure] - device work-item setup failed");
         if (hc.numPending) {
             std::vector<uint32_t> pend(hc.numPending); std::vector<float> puv((size_t)hc.numPending * 6); std::vector<uint8_t> plv(hc.numPending);
             struct PoolBlock { DevPool* pool; void* p; ~PoolBlock() { if (p) pool->release(p); } } tmp{ baker.devPool.get(), baker.devPool->acquire((size_t)hc.numPending * 24 + 256) };
             if (!tmp.p) return L.failure("[Failure] - device work-item setup failed");
-            if (!HIP_OK(copy_pending_to_host(dScratch, scratchBytes, T, hc.numPending, pend.data(), puv.data(), tmp.p, stream))) return L.failure("[Failure] - device work-item setup failed");
+            if (!HIP_OK(copy_pending_to_host(tab.scratch, tab.scratchBytes, T, hc.numPending, pend.data(), puv.data(), tmp.p, stream))) return L.failure("[Failure] - device work-item setup failed");
             {   // (tiny triangles under dynamic subdivision are degenerate by the tens of thousands -- configs[4]: 1.5 ms of log2f on one thread; four share it)
                 ommCpuBakeInputDesc tmpDesc = d; tmpDesc.subdivisionLevels = nullptr;   // per-triangle overrides were already honoured on the device
                 auto part = [&](uint32_t k0, uint32_t k1) {
@@ -830,10 +828,10 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
                 for (auto& h : helpers) h.join();
                 for (uint32_t w = started + 1u; w < ways; ++w) part((uint32_t)((uint64_t)n * w / ways), (uint32_t)((uint64_t)n * (w + 1u) / ways));   // (shares whose thread did not start)
             }
-            if (!HIP_OK(run_setup_fix_pending(S, dScratch, scratchBytes, pend.data(), plv.data(), hc.numPending, tmp.p, stream))) return L.failure("[Failure] - device work-item setup failed");
+            if (!HIP_OK(run_setup_fix_pending(S, tab.scratch, tab.scratchBytes, pend.data(), plv.data(), hc.numPending, tmp.p, stream))) return L.failure("[Failure] - device work-item setup failed");
         }
     }
-    if (!HIP_OK(run_setup_items(S, dScratch, scratchBytes, dCounters, dUv, dLevel, dDegen, dTriToItem, dItemIds, stream)))
+    if (!HIP_OK(run_setup_items(S, tab.scratch, tab.scratchBytes, tab.counters, tab.uv, tab.level, tab.degen, tab.triToItem, tab.itemIds, stream)))
         return L.failure("[Failure] - device work-item setup failed");
     const int e1 = et.mark();
 
@@ -855,20 +853,20 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
     P.useCoarse = tex.mips[0].sat != nullptr && P.mipCount == 1 && P.filterLinear;
     P.cutoff = d.alphaCutoff; P.borderAlpha = d.runtimeSamplerDesc.borderAlpha;
     P.wantKnownCount = d.rejectionThreshold > 0.f;
-    P.noFine = (flags & (1u << 9)) != 0;   // DisableFineClassification (bake_cpu_impl.cpp:45,822-823)
-    P.altKernel = (flags & (1u << 8)) ? ((flags & (1u << 7)) ? 2 : 1) : 0;   // DisableLevelLineIntersection (+ EnableAABBTesting), bake_cpu_impl.cpp:44-45,915-966
+    P.noFine = has_flag(flags, kBakeFlag_DisableFineClassification);   // (bake_cpu_impl.cpp:45,822-823)
+    P.altKernel = has_flag(flags, kBakeFlag_DisableLevelLineIntersection) ? (has_flag(flags, kBakeFlag_EnableAABBTesting) ? 2 : 1) : 0;   // (bake_cpu_impl.cpp:44-45,915-966)
 
     // ---- level-0 hierarchical query per item + compaction of the items that need per-micro-triangle work; ONE sync ----
-    launch_triage(P, dUv, dLevel, dDegen, dCounters, maxItems, dMask, dActive, dScratch, stream);
+    launch_triage(P, tab.uv, tab.level, tab.degen, tab.counters, maxItems, tab.mask, tab.active, tab.scratch, stream);
     uint8_t* const hostBlock = arena->host_block();   // layout: [0, 256) counters, [256, 512) tail summary, [1 KiB, ..) the final read-backs
     SetupCounters* const hcDst = hostBlock ? (SetupCounters*)hostBlock : &hc;
-    if (!HIP_OK(run_prep(dItemIds, dActive, dLevel, storeBits, maxItems, dCounters, dActiveIds, dStateOfs, dScratch, scratchBytes, stream)) ||
-        !HIP_OK(hipMemcpyAsync(hcDst, dCounters, sizeof hc, hipMemcpyDeviceToHost, stream)) || !HIP_OK(hipStreamSynchronize(stream)))
+    if (!HIP_OK(run_prep(tab.itemIds, tab.active, tab.level, storeBits, maxItems, tab.counters, tab.activeIds, tab.stateOfs, tab.scratch, tab.scratchBytes, stream)) ||
+        !HIP_OK(hipMemcpyAsync(hcDst, tab.counters, sizeof hc, hipMemcpyDeviceToHost, stream)) || !HIP_OK(hipStreamSynchronize(stream)))
         return L.failure("[Failure] - device work-list compaction failed");
     if (hostBlock) memcpy(&hc, hcDst, sizeof hc);
 
     uint32_t U = hc.numItems;
-    if ((flags & (1u << 5)) && hc.numDisabled != 0) { // bake_cpu_impl.cpp:652-657
+    if (has_flag(flags, ommCpuBakeFlags_EnableValidation) && hc.numDisabled != 0) { // bake_cpu_impl.cpp:652-657
         char buf[256];
         snprintf(buf, sizeof buf, "[Info] - The workload consists of %d unclassifiable triangles, these will be classified as unresolvedTriState = %s.", hc.numDisabled, special_name(d.unresolvedTriState));
         L.msg(ommMessageSeverity_Info, buf);
@@ -876,14 +874,14 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
     // ---- ValidateWorkloadSize (bake_cpu_impl.cpp:662-713) ----
     if (checkWorkload) {
         if (d.maxWorkloadSize != 0xFFFFFFFFFFFFFFFFull && hc.workload > d.maxWorkloadSize) return ommResult_WORKLOAD_TOO_BIG;
-        if ((flags & (1u << 5)) && hc.workload > (1ull << 27)) {
+        if (has_flag(flags, ommCpuBakeFlags_EnableWorkloadValidation) && hc.workload > (1ull << 27)) {
             char buf[256];
             snprintf(buf, sizeof buf, "[Perf Warning] - The workload consists of %lld work items (number of texels to classify), which corresponds to roughly %lld 1024x1024 textures."
                      " This is unusually large and may result in long bake times.", (long long)hc.workload, (long long)(hc.workload >> 20));
             L.msg(ommMessageSeverity_PerfWarning, buf);
         }
     }
-    if ((flags & (1u << 7)) && !(flags & (1u << 8)))   // bake_cpu_impl.cpp:718-719 (ResampleCoarse is the first to look, behind the workload validation)
+    if (has_flag(flags, kBakeFlag_EnableAABBTesting) && !has_flag(flags, kBakeFlag_DisableLevelLineIntersection))   // bake_cpu_impl.cpp:718-719 (ResampleCoarse is the first to look, behind the workload validation)
         return L.invalid("[Invalid Arg] - EnableAABBTesting can't be used without also setting DisableLevelLineIntersection");
     // rank ranges of the per-level active lists (single GPU: every range is the whole level group)
     ShardBounds bounds; memset(&bounds, 0, sizeof bounds);
@@ -896,11 +894,11 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
     }
     // packed states of the active items + the queue of open tiles (48-byte records, bake_kernels.hip) + its 4 control words
     const size_t stateBytes = pad256(hc.stateBytes ? (size_t)hc.stateBytes : 256), ctlBytes = pad256(sizeof(uint32_t) * kClassifyCtlWords);
-    double microAll = 0; for (int l = 0; l < kNumLevels; ++l) microAll += (double)hc.levelCount[l] * (double)(1ull << (2 * l));
+    const double microAll = (double)micro_triangles_of(hc.levelCount);
     // ---- streamed result (ommCpuBake)?  Worth it when the packed states are large enough for the copy to matter ----
     uint32_t streamChunks = 0; const uint32_t numActiveAll = hc.activeStart[kNumLevels];
     uint8_t* hostArray = nullptr; unsigned long long* hCursor = nullptr; bool hostPinned = false;
-    if (so && numActiveAll && !(flags & (1u << 1)) && !P.altKernel && storeBits == bits) {   // (with special indices disabled every uniform item is a block too: the plain path handles that)
+    if (so && numActiveAll && !has_flag(flags, ommCpuBakeFlags_DisableSpecialIndices) && !P.altKernel && storeBits == bits) {   // (with special indices disabled every uniform item is a block too: the plain path handles that)
         uint32_t k = so->chunksWanted;
         if (!so->forced) {
             // >= 64 MiB of packed states: one range per 32 MiB, at most 32 (round 3, classification-bound, at 1.27 GB: 8 / 16 / 24 / 32 ranges = 38.4 / 36.7 / 36.2 / 36.2 ms)
@@ -949,21 +947,21 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
     const int e1b = et.mark();
 
     // ---- ResampleCoarse + ResampleFine (bake_cpu_impl.cpp:715-1029) on the active items ----
-    ItemArrays A; A.uv = dUv; A.degenerate = dDegen; A.stateOfs = dStateOfs; A.states = dStates; A.stateMask = dMask; A.knownCount = dKnown; A.fineCount = dFine;
-    // (dFine was zeroed by the first set-up launch, with the known counts)
+    ItemArrays A; A.uv = tab.uv; A.degenerate = tab.degen; A.stateOfs = tab.stateOfs; A.states = dStates; A.stateMask = tab.mask; A.knownCount = tab.known; A.fineCount = tab.fine;
+    // (tab.fine was zeroed by the first set-up launch, with the known counts)
     if (sh && sh->mergeStates && !HIP_OK(hipMemsetAsync(dStates, 0, stateBytes, stream))) return L.failure("[Failure] - device memset failed");
     if (sh && sh->world > 1) { // even out the per-rank cost: interleave every level's active list (tail_kernels.hip: shard_interleave)
         // the permuted copy goes through the (idle) setup / tail scratch block: no allocation, no synchronisation, stream ordered
-        uint32_t* tmp = (uint32_t*)dScratch;
-        bool okp = (size_t)hc.activeStart[kNumLevels] * 4 <= scratchBytes;
+        uint32_t* tmp = (uint32_t*)tab.scratch;
+        bool okp = (size_t)hc.activeStart[kNumLevels] * 4 <= tab.scratchBytes;
         for (int l = 0; l < kNumLevels && okp; ++l) {
             const uint32_t a = hc.activeStart[l], cnt = hc.activeStart[l + 1] - hc.activeStart[l];
             if (cnt < 3) continue;
             uint32_t stride = (uint32_t)((double)cnt * 0.6180339887498949); if (stride < 1) stride = 1;
             auto gcd = [](uint32_t x, uint32_t y) { while (y) { const uint32_t t = x % y; x = y; y = t; } return x; };
             while (gcd(stride, cnt) != 1) ++stride;   // (cnt - 1 is always coprime: terminates)
-            launch_shard_interleave(dActiveIds + a, tmp + a, cnt, stride % cnt, stream);
-            okp = HIP_OK(hipMemcpyAsync(dActiveIds + a, tmp + a, (size_t)cnt * 4, hipMemcpyDeviceToDevice, stream));
+            launch_shard_interleave(tab.activeIds + a, tmp + a, cnt, stride % cnt, stream);
+            okp = HIP_OK(hipMemcpyAsync(tab.activeIds + a, tmp + a, (size_t)cnt * 4, hipMemcpyDeviceToDevice, stream));
         }
         if (!okp) return L.failure("[Failure] - shard permutation failed");
     }
@@ -971,41 +969,41 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
     struct EventList { hipEvent_t ev[2 * kMaxClassifyChunks + 3]; uint32_t n = 0; ~EventList() { for (uint32_t k = 0; k < n; ++k) (void)hipEventDestroy(ev[k]); } } chunkEvents;   // placement done [K + 1] | fences [K + 2]
     StreamCtx sc; ClassifyChunks cc; memset(&cc, 0, sizeof cc); cc.count = 1;
     MarkCtx mk; mk.et = &et; mk.mark = -1; mk.markGeneric = -1;
-    const bool noDedup = (flags & (1u << 3)) != 0;
+    const bool noDedup = has_flag(flags, ommCpuBakeFlags_DisableDuplicateDetection);
     int pv0 = -1, pv1 = -1;   // HIP event marks around the preview of a streamed bake
     if (streamChunks) {
-        bool oks = HIP_OK(hipMemsetAsync(dPlaced, 0xFF, (size_t)maxItems * 8, stream)) && HIP_OK(hipMemsetAsync(dCursor, 0, 8, stream)) && HIP_OK(hipMemsetAsync(dStreamCtl, 0, sizeof(uint32_t) * kStreamCtlWords, stream));
-        oks = oks && HIP_OK(run_stream_begin(dActiveIds, numActiveAll, dUv, dLevel, dScratch, scratchBytes, stream));
+        bool oks = HIP_OK(hipMemsetAsync(tab.placed, 0xFF, (size_t)maxItems * 8, stream)) && HIP_OK(hipMemsetAsync(tab.cursor, 0, 8, stream)) && HIP_OK(hipMemsetAsync(tab.streamCtl, 0, sizeof(uint32_t) * kStreamCtlWords, stream));
+        oks = oks && HIP_OK(run_stream_begin(tab.activeIds, numActiveAll, tab.uv, tab.level, tab.scratch, tab.scratchBytes, stream));
         for (uint32_t k = 0; oks && k < 2u * streamChunks + 3u; ++k) { oks = HIP_OK(hipEventCreateWithFlags(&chunkEvents.ev[k], hipEventDisableTiming)); chunkEvents.n += oks ? 1u : 0u; }
         if (!oks) return L.failure("[Failure] - could not set up the streamed result");
-        sc.stream = stream; sc.place = so->placeStream; sc.fences = chunkEvents.ev + streamChunks + 1u; sc.activeIds = dActiveIds; sc.numActive = numActiveAll; sc.scratch = dScratch; sc.scratchBytes = scratchBytes; sc.digests = dDigests;
-        sc.cursor = dCursor; sc.stage = dStage; sc.placed = dPlaced; sc.ctl = dStreamCtl; sc.hostCursor = hCursor; sc.events = chunkEvents.ev; sc.numEvents = streamChunks + 1u; sc.recorded = 0; sc.ok = true;
+        sc.stream = stream; sc.place = so->placeStream; sc.fences = chunkEvents.ev + streamChunks + 1u; sc.activeIds = tab.activeIds; sc.numActive = numActiveAll; sc.scratch = tab.scratch; sc.scratchBytes = tab.scratchBytes; sc.digests = tab.digests;
+        sc.cursor = tab.cursor; sc.stage = dStage; sc.placed = tab.placed; sc.ctl = tab.streamCtl; sc.hostCursor = hCursor; sc.events = chunkEvents.ev; sc.numEvents = streamChunks + 1u; sc.recorded = 0; sc.ok = true;
         memset(&sc.proto, 0, sizeof sc.proto);
-        sc.proto.stateMask = dMask; sc.proto.knownCount = dKnown; sc.proto.digests = dDigests; sc.proto.states = dStates; sc.proto.stateOfs = dStateOfs;
+        sc.proto.stateMask = tab.mask; sc.proto.knownCount = tab.known; sc.proto.digests = tab.digests; sc.proto.states = dStates; sc.proto.stateOfs = tab.stateOfs;
         sc.proto.rejectionThreshold = d.rejectionThreshold; sc.proto.bits = bits; sc.proto.disableDedup = noDedup ? 1 : 0;
         cc.count = streamChunks; cc.after = stream_hook; cc.mark = stream_mark_hook; cc.user = &sc; cc.early = nullptr; sc.queueCtl = dQueueCtl;
-        sc.paired = streamChunks > 1; sc.earlyList = nullptr; sc.earlyCapacity = 0; sc.itemLevel = dLevel;
+        sc.paired = streamChunks > 1; sc.earlyList = nullptr; sc.earlyCapacity = 0; sc.itemLevel = tab.level;
         sc.waitSeconds = 4.0 + 100.0 * 1e-3 * (2.5e-10 * microAll + 4e-9 * (double)hc.workload);   // (100 x the estimate of the whole classification, never below 4 s)
         // preview (tail_kernels.hip): level-5 classification of the items of level >= 6 into buffers of its own; items that share their preview are classified early
         const uint32_t first6 = hc.activeStart[6], count6 = numActiveAll - hc.activeStart[6];
         if (count6 && streamChunks > 1) {
             pv0 = et.mark();
             ClassifyParams P2 = P; P2.format = 2; P2.promotion = 1; P2.wantKnownCount = 0; P2.noFine = 0;
-            ItemArrays A2 = A; A2.uv = dUv2; A2.stateOfs = dOfs2; A2.states = dStates2; A2.stateMask = dMask2; A2.fineCount = dFine2;   // (its level-line statistic goes nowhere)
-            bool okp = HIP_OK(hipMemsetAsync(dEarly, 0, maxItems, stream)) && HIP_OK(hipMemsetAsync(dMask2, 0, (size_t)maxItems * 4, stream));
-            launch_stream_preview_prepare(dActiveIds + first6, count6, dUv, P.mips[0].fw, P.mips[0].fh, dUv2, dOfs2, dEarly, stream);
+            ItemArrays A2 = A; A2.uv = tab.uv2; A2.stateOfs = tab.ofs2; A2.states = tab.states2; A2.stateMask = tab.mask2; A2.fineCount = tab.fine2;   // (its level-line statistic goes nowhere)
+            bool okp = HIP_OK(hipMemsetAsync(tab.early, 0, maxItems, stream)) && HIP_OK(hipMemsetAsync(tab.mask2, 0, (size_t)maxItems * 4, stream));
+            launch_stream_preview_prepare(tab.activeIds + first6, count6, tab.uv, P.mips[0].fw, P.mips[0].fh, tab.uv2, tab.ofs2, tab.early, stream);
             {   // the preview items as ONE level-5 class of the ordinary classification: a 1024-tile each, tile triage (most previews are settled by one SAT
                 // query), LDS window and the single-texel pass for the rest -- through the bake's own tile queue, which is free until the real launch
                 static_assert(kPreviewLevel == 5, "the preview is the 1024-tile class");
                 uint32_t first2[kNumLevels], count2[kNumLevels];
                 for (int l = 0; l < kNumLevels; ++l) { first2[l] = 0; count2[l] = 0; }
                 first2[kPreviewLevel] = first6; count2[kPreviewLevel] = count6;
-                okp = okp && HIP_OK(launch_classify(P2, A2, dActiveIds, first2, count2, dTileQueue, dQueueCtl, device_cu_count(), stream, nullptr));
+                okp = okp && HIP_OK(launch_classify(P2, A2, tab.activeIds, first2, count2, dTileQueue, dQueueCtl, device_cu_count(), stream, nullptr));
             }
             ClassifyPlan plan; classify_plan(lvlFirst, lvlCount, streamChunks, &plan);   // (the ranges launch_classify will cut)
-            okp = okp && HIP_OK(run_stream_preview_flags(dActiveIds + first6, count6, first6, numActiveAll, dStates2, dLevel, dEarly, dStreamCtl, dScratch, scratchBytes, dEarlyLead, dEarlyList, plan, stream));
+            okp = okp && HIP_OK(run_stream_preview_flags(tab.activeIds + first6, count6, first6, numActiveAll, tab.states2, tab.level, tab.early, tab.streamCtl, tab.scratch, tab.scratchBytes, tab.earlyLead, tab.earlyList, plan, stream));
             if (!okp) return L.failure("[Failure] - could not set up the streamed result");
-            cc.early = dEarly; cc.earlyLead = dEarlyLead; cc.earlyStage = dStage; sc.proto.early = dEarly; sc.earlyList = dEarlyList; sc.earlyCapacity = count6;
+            cc.early = tab.early; cc.earlyLead = tab.earlyLead; cc.earlyStage = dStage; sc.proto.early = tab.early; sc.earlyList = tab.earlyList; sc.earlyCapacity = count6;
             pv1 = et.mark();
         }
     } else { cc.mark = mark_hook; cc.user = &mk; cc.early = nullptr; }   // (HIP event in front of the persistent launch of the levels >= 6)
@@ -1014,17 +1012,17 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
         cc.generic.count = (unsigned long long*)dGeneric; cc.generic.entries = (uint2*)(dGeneric + 256); cc.generic.capacity = (uint32_t)genericCapacity;
         cc.markGeneric = mark_generic_hook;   // (cc.user is the MarkCtx: a deferred pass and a streamed result exclude each other)
     }
-    if (!HIP_OK(launch_classify(P, A, dActiveIds, lvlFirst, lvlCount, dTileQueue, dQueueCtl, device_cu_count(), stream, &cc))) return L.failure("[Failure] - kernel launch failed");
+    if (!HIP_OK(launch_classify(P, A, tab.activeIds, lvlFirst, lvlCount, dTileQueue, dQueueCtl, device_cu_count(), stream, &cc))) return L.failure("[Failure] - kernel launch failed");
     if (streamChunks && !sc.ok) return L.failure("[Failure] - kernel launch failed");
     const int e2 = et.mark();
     if (ht) { // bring the per-micro-triangle states to the host for the serial tail (host_tail.cpp)
-        const ommResult gr = gather_host_items(L, stream, U, T, hc, dUv, dLevel, dActive, dMask, dStateOfs, dStates, dTriToItem, bits, ht->items);
+        const ommResult gr = gather_host_items(L, stream, U, T, hc, tab.uv, tab.level, tab.active, tab.mask, tab.stateOfs, dStates, tab.triToItem, bits, ht->items);
         tm.setupMs = et.ms(e0, e1); tm.triageMs = et.ms(e1, e1b); tm.classifyMs = et.ms(e1b, e2); tm.uniqueItems = U;
         return gr;
     }
     // ---- CalcDigest (bake_cpu_impl.cpp:1038-1040): active items here, uniform ones from the table in the tail ----
     if (!noDedup && !streamChunks)   // (a streamed bake computed them range by range)
-        launch_digest_levels(dStates, dStateOfs, dActiveIds, lvlFirst, lvlCount, (uint32_t)storeBits, dDigests, stream);
+        launch_digest_levels(dStates, tab.stateOfs, tab.activeIds, lvlFirst, lvlCount, (uint32_t)storeBits, tab.digests, stream);
     if (!HIP_OK(hipGetLastError())) return L.failure("[Failure] - kernel launch failed");
     const int e3 = et.mark();
     // ---- streamed result: everything is enqueued; follow the classification launches and send what each one placed ----
@@ -1051,37 +1049,33 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
     }
     // ---- promote / dedup / sort / offsets on the device ----
     TailInputs ti; memset(&ti, 0, sizeof ti);
-    ti.numItems = U; ti.numTris = T; ti.uv = dUv; ti.level = dLevel; ti.stateMask = dMask; ti.knownCount = dKnown; ti.digests = dDigests;
-    ti.uniformDigest = dUniformDigest; ti.triToItem = dTriToItem; ti.format = bits;
+    ti.numItems = U; ti.numTris = T; ti.uv = tab.uv; ti.level = tab.level; ti.stateMask = tab.mask; ti.knownCount = tab.known; ti.digests = tab.digests;
+    ti.uniformDigest = tab.uniformDigest; ti.triToItem = tab.triToItem; ti.format = bits;
     // every work item outside the active lists is uniform, and uniform items of one level and state share a digest: at most 13 x 4 of those
     ti.maxDistinctDigests = hc.activeStart[kNumLevels] + 64u;
-    ti.disableSpecial = (flags & (1u << 1)) != 0; ti.disableDedup = (flags & (1u << 3)) != 0;
-    ti.rejectionThreshold = d.rejectionThreshold; ti.unresolved = (int32_t)d.unresolvedTriState; ti.errorFlag = dErr;
+    ti.disableSpecial = has_flag(flags, ommCpuBakeFlags_DisableSpecialIndices); ti.disableDedup = noDedup;
+    ti.rejectionThreshold = d.rejectionThreshold; ti.unresolved = (int32_t)d.unresolvedTriState; ti.errorFlag = tab.err;
     TailOutputs to; memset(&to, 0, sizeof to);
-    to.special = dSpecial; to.rep = dRep; to.order = dOrder; to.dstOfs = dDstOfs; to.sizes = dSizes; to.itemValue = dItemValue;
-    to.indexBuffer = dIndex; to.arrayHist = dArrayHist; to.indexHist = dIndexHist;
+    to.special = tab.special; to.rep = tab.rep; to.order = tab.order; to.dstOfs = tab.dstOfs; to.sizes = tab.sizes; to.itemValue = tab.itemValue;
+    to.indexBuffer = tab.index; to.arrayHist = tab.arrayHist; to.indexHist = tab.indexHist;
     if (sh) { // sharded bake: hand the per-item metadata of this rank's share to the caller and stop here (ommxShardedBegin)
         const uint32_t numActive = hc.activeStart[kNumLevels];
-        sh->bounds = bounds; sh->ti = ti; sh->to = to; sh->hc = hc; sh->dStates = dStates; sh->dActive = dActive; sh->dLevel = dLevel; sh->dScratch = dScratch;
-        sh->dStateOfs = dStateOfs; sh->dMask = dMask; sh->dActiveIds = dActiveIds; sh->dIndex = dIndex; sh->dArrayHist = dArrayHist; sh->dIndexHist = dIndexHist; sh->dTriArea = dTriArea;
-        sh->scratchBytes = scratchBytes; sh->flags = flags; sh->T = T; sh->bits = bits;
-        launch_shard_pack_meta(bounds, dActiveIds, numActive, dMask, dKnown, dDigests, sh->dMeta, stream);
+        sh->bounds = bounds; sh->ti = ti; sh->to = to; sh->hc = hc; sh->dStates = dStates; sh->tab = tab;
+        sh->flags = flags; sh->T = T; sh->bits = bits;
+        launch_shard_pack_meta(bounds, tab.activeIds, numActive, tab.mask, tab.known, tab.digests, tab.meta, stream);
         if (!sh->asyncBegin && !HIP_OK(hipStreamSynchronize(stream))) return L.failure("[Failure] - sharded classification failed");   // (the one-call RCCL path stays on the stream)
         sh->ev[0] = e0; sh->ev[1] = e1; sh->ev[2] = e1b; sh->ev[3] = e2; sh->ev[4] = e3;   // (read in Finish, when the events are complete)
         tm.uniqueItems = U; tm.activeItems = numActive; tm.stateBytes = hc.stateBytes;
-        for (int l = 0; l < kNumLevels; ++l) tm.microTriangles += (uint64_t)hc.levelCount[l] << (2 * l);
+        tm.microTriangles += micro_triangles_of(hc.levelCount);
         return ommResult_SUCCESS;
     }
     // the index format depends on the triangle count alone: the tail's index kernel writes the narrowed buffer next to the int32 one (bake_cpu_impl.cpp:1872-1902)
-    const bool allow8 = (flags & (1u << 6)) != 0, force32 = (flags & (1u << 2)) != 0;
-    int idxBytes = 4; R.indexFormat = ommIndexFormat_UINT_32;
-    if (allow8 && T <= 127 && !force32) { idxBytes = 1; R.indexFormat = ommIndexFormat_UINT_8; }
-    else if (T <= 32767 && !force32) { idxBytes = 2; R.indexFormat = ommIndexFormat_UINT_16; }
+    R.indexFormat = index_format_for(T, flags);
     R.index = R.dev_alloc((size_t)(T ? T : 1) * 4); // the reference narrows in place inside an int32 vector (:1882-1900)
     if (!R.index) return L.failure("[Failure] - could not allocate the device result");
-    to.narrowIndex = R.index; to.narrowBytes = idxBytes;
+    to.narrowIndex = R.index; to.narrowBytes = (int)index_bytes(R.indexFormat);
     TailCounts counts;
-    if (!HIP_OK(run_tail(ti, to, dScratch, scratchBytes, &counts, stream, hostBlock ? hostBlock + 256 : nullptr))) return L.failure("[Failure] - device tail failed");
+    if (!HIP_OK(run_tail(ti, to, tab.scratch, tab.scratchBytes, &counts, stream, hostBlock ? hostBlock + 256 : nullptr))) return L.failure("[Failure] - device tail failed");
     if (counts.arrayDataSize > 0xFFFFFFFFull) return ommResult_FAILURE; // bake_cpu_impl.cpp:1774-1775
     const int e4 = et.mark();
 
@@ -1094,8 +1088,8 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
         // the blocks are (or will shortly be) at their final offsets in the caller's array, provided the speculative placement equals the exact layout the
         // tail has just produced: compare, and fall back to the ordinary gather + copy otherwise
         uint32_t hctl[4] = { 0u, 0u, 0u, 0u };
-        launch_stream_verify(dOrder, dDstOfs, E, dPlaced, dStreamCtl, stream);
-        if (!HIP_OK(hipMemcpyAsync(hctl, dStreamCtl, sizeof hctl, hipMemcpyDeviceToHost, stream)) || !HIP_OK(hipStreamSynchronize(stream)))
+        launch_stream_verify(tab.order, tab.dstOfs, E, tab.placed, tab.streamCtl, stream);
+        if (!HIP_OK(hipMemcpyAsync(hctl, tab.streamCtl, sizeof hctl, hipMemcpyDeviceToHost, stream)) || !HIP_OK(hipStreamSynchronize(stream)))
             return L.failure("[Failure] - could not verify the streamed result");
         streamed = hctl[2] == 0u && sent == R.arrayDataSize;
         if (!streamed) {
@@ -1116,14 +1110,14 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
             if (!streamed) {
                 uint8_t* unitCodes = nullptr; uint32_t* blockRawCounts = nullptr;
                 if (R.gatherCodes && storeBits == bits && counts.smallOmms == 0 && !R.gatherCodes(counts.arrayDataSize, &unitCodes, &blockRawCounts)) { unitCodes = nullptr; blockRawCounts = nullptr; }
-                launch_gather_omms(dStates, dStateOfs, dActive, dMask, dLevel, bits, storeBits, dOrder, dDstOfs, dSizes, E, R.arrayData, stream, unitCodes, blockRawCounts, R.descs);
-            } else launch_write_descs(dOrder, dDstOfs, dLevel, bits, E, R.descs, stream);   // (the gather writes the descriptors of its OMMs itself)
+                launch_gather_omms(dStates, tab.stateOfs, tab.active, tab.mask, tab.level, bits, storeBits, tab.order, tab.dstOfs, tab.sizes, E, R.arrayData, stream, unitCodes, blockRawCounts, R.descs);
+            } else launch_write_descs(tab.order, tab.dstOfs, tab.level, bits, E, R.descs, stream);   // (the gather writes the descriptors of its OMMs itself)
         }
     }
     // the two histograms, the consistency word and the striped statistic counters were taken from the arena back to back: ONE read-back
     unsigned long long fineCount = 0;
     std::vector<unsigned long long> fineSlots((size_t)kFineSlots * kFineStride, 0ull);
-    const size_t spanBytes = (size_t)((const uint8_t*)(dFine + fineSlots.size()) - (const uint8_t*)dArrayHist);
+    const size_t spanBytes = tab.readback_bytes();
     // (into the arena's pinned block when there is one: three copies queued, ONE wait -- into pageable memory each copy is a wait of its own)
     uint32_t hostCtlLocal[kClassifyCtlWords];
     unsigned long long genericLocal[3] = { 0, 0, 0 };   // reservations (incl. null padding), the pass's cursor, micro-triangles it classified
@@ -1134,7 +1128,7 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
     uint32_t* const hostCtl = pinnedBack ? (uint32_t*)(hostBlock + ctlAt) : hostCtlLocal;
     unsigned long long* const genericWords = pinnedBack ? (unsigned long long*)(hostBlock + genAt) : genericLocal;
     memset(hostCtl, 0, sizeof hostCtlLocal); memset(genericWords, 0, sizeof genericLocal);
-    ok = ok && HIP_OK(hipMemcpyAsync(span, dArrayHist, spanBytes, hipMemcpyDeviceToHost, stream));
+    ok = ok && HIP_OK(hipMemcpyAsync(span, tab.arrayHist, spanBytes, hipMemcpyDeviceToHost, stream));
     uint32_t queueTails[2] = { 0u, 0u };   // open tiles of the two tile sizes (statistics)
     if (hc.activeStart[kNumLevels]) ok = ok && HIP_OK(hipMemcpyAsync(hostCtl, dQueueCtl, sizeof hostCtlLocal, hipMemcpyDeviceToHost, stream));
     if (dGeneric) ok = ok && HIP_OK(hipMemcpyAsync(genericWords, dGeneric, sizeof genericLocal, hipMemcpyDeviceToHost, stream));
@@ -1143,8 +1137,8 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
     // (a streamed result may still be on its way to the host: the caller queues its small read-backs first and then waits, StreamOut::finish)
     if (!ok) return L.failure("[Failure] - could not materialise the bake result on the device");
     memcpy(R.hist, span, sizeof(uint32_t) * kNumLevels);
-    memcpy(R.hist + kNumLevels, span + ((const uint8_t*)dIndexHist - (const uint8_t*)dArrayHist), sizeof(uint32_t) * kNumLevels);
-    memcpy(fineSlots.data(), span + ((const uint8_t*)dFine - (const uint8_t*)dArrayHist), sizeof(unsigned long long) * fineSlots.size());
+    memcpy(R.hist + kNumLevels, span + ((const uint8_t*)tab.indexHist - (const uint8_t*)tab.arrayHist), sizeof(uint32_t) * kNumLevels);
+    memcpy(fineSlots.data(), span + ((const uint8_t*)tab.fine - (const uint8_t*)tab.arrayHist), sizeof(unsigned long long) * fineSlots.size());
 
     tm.uploadMs = 0.f; tm.hostSetupMs = 0.f; tm.setupMs = et.ms(e0, e1); tm.triageMs = et.ms(e1, e1b); tm.classifyMs = et.ms(e1b, e2); tm.digestMs = et.ms(e2, e3);
     tm.streamPreviewMs = pv0 >= 0 ? et.ms(pv0, pv1) : 0.f;
@@ -1153,8 +1147,7 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
     for (int k = 0; k < kFineSlots; ++k) fineCount += fineSlots[(size_t)k * kFineStride];
     queueTails[1] = hostCtl[kCtl1024 + kSecTails]; for (uint32_t k = 0; k < kMaxClassifyChunks; ++k) queueTails[0] += hostCtl[kSecTails + k];   // (1024-tile queue; sections of the 4096-tile queue)
     tm.openTiles = queueTails[0] + queueTails[1]; tm.openTileMicroTriangles = (uint64_t)queueTails[0] * 4096u + (uint64_t)queueTails[1] * 1024u;
-    tm.fineMicroTriangles = fineCount; tm.uniqueItems = U; tm.activeItems = hc.activeStart[kNumLevels]; tm.stateBytes = hc.stateBytes; tm.microTriangles = 0;
-    for (int l = 0; l < kNumLevels; ++l) tm.microTriangles += (uint64_t)hc.levelCount[l] << (2 * l);
+    tm.fineMicroTriangles = fineCount; tm.uniqueItems = U; tm.activeItems = hc.activeStart[kNumLevels]; tm.stateBytes = hc.stateBytes; tm.microTriangles = micro_triangles_of(hc.levelCount);
     {   // classify_tiles launches: one per level below 5, one for level 5, ONE for all levels >= 6 (bake_kernels.hip)
         bool big = false;
         for (int l = 0; l < kNumLevels; ++l) { const bool any = hc.activeStart[l + 1] != hc.activeStart[l]; if (l < 6) tm.classifyLaunches += any; else big = big || any; }
@@ -1163,12 +1156,9 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
     return ommResult_SUCCESS;
 }
 
-inline bool wants_host_tail(const ommCpuBakeInputDesc& d) { return ((uint32_t)d.bakeFlags & ((1u << 4) | (1u << 10))) != 0 || d.maxArrayDataSize != 0xFFFFFFFFu; }
-
 ommResult scope_fences(const Baker& baker, const ommCpuBakeInputDesc& d, bool formatsOnHost, bool hostTailOk = true, bool plainEntry = true)
 {
     const Logger& L = baker.log;
-    const uint32_t flags = (uint32_t)d.bakeFlags;
     if (wants_host_tail(d) && !hostTailOk) // the serial reducers run on the host over the merged states: not in the caller-driven four-phase protocol
         { L.msg(ommMessageSeverity_Fatal, "[Not Implemented] - near-duplicate merging / maxArrayDataSize budgets are available through ommCpuBake, ommxBakeDevice and ommxShardedBakeRccl, not through ommxShardedBegin/Tail/Finish"); return ommResult_NOT_IMPLEMENTED; }
     // internal flags (bake_cpu_impl.cpp:43-48): EnableAABBTesting (7) / DisableLevelLineIntersection (8) select the reference's ConservativeBilinearKernel
@@ -1176,7 +1166,7 @@ ommResult scope_fences(const Baker& baker, const ommCpuBakeInputDesc& d, bool fo
     // without the fine pass unresolved micro-triangles keep the state UnknownOpaque (3), which the reference ORs into ONE bit of a 2-state block together with
     // its neighbour's (bake_cpu_impl.cpp:1811) while digesting the unpacked value: bake_core keeps such a bake in the 2-bit packing up to the final gather --
     // on the two single-device entry points; not where blocks travel between ranks or to the host tail in their packed form
-    if ((flags & (1u << 9)) != 0 && d.format == ommFormat_OC1_2_State && (!plainEntry || wants_host_tail(d)))
+    if (no_fine_two_state(d) && (!plainEntry || wants_host_tail(d)))
         { L.msg(ommMessageSeverity_Fatal, "[Not Implemented] - internal bake flag DisableFineClassification (bit 9) with OC1_2_State is supported by ommCpuBake / ommxBakeDevice without near-duplicate merging or a size budget"); return ommResult_NOT_IMPLEMENTED; }
     if (d.formats) { // the reference sizes its arrays from the global format only (bake_cpu_impl.cpp:1763-1772): mixed formats corrupt its heap
         if (!formatsOnHost) return L.failure("[Failure] - per-triangle formats are not supported on the device-resident entry point");
@@ -1187,11 +1177,36 @@ ommResult scope_fences(const Baker& baker, const ommCpuBakeInputDesc& d, bool fo
     return ommResult_SUCCESS;
 }
 
+// What every bake entry point checks first, in the reference's order.  `outIsSet`: ommxBakeDevice reports a null result pointer together with a null desc.
+ommResult check_bake_entry(ommBaker baker, const ommCpuBakeInputDesc* desc, Baker** outB, bool outIsSet = true)
+{
+    if (baker == 0) return ommResult_INVALID_ARGUMENT;
+    Baker* b = untag<Baker>(baker);
+    if (desc == 0 || !outIsSet) return b->log.invalid("input desc was not set");
+    if (tag_of(baker) != kCpuBaker) return b->log.invalid("Baker was not created as the right type");
+    if (desc->texture == 0) return b->log.invalid("[Invalid Argument] - ommCpuBakeInputDesc has no texture set"); // bake_cpu_impl.cpp:97-103
+    // the dispatch table lookup precedes ValidateDesc (bake_cpu_impl.cpp:297-304): unknown sampler enums -> FAILURE
+    if (tag_of(desc->texture) == kTexture &&
+        ((unsigned)desc->runtimeSamplerDesc.addressingMode >= (unsigned)ommTextureAddressMode_MAX_NUM ||
+         (unsigned)desc->runtimeSamplerDesc.filter >= (unsigned)ommTextureFilterMode_MAX_NUM))
+        return ommResult_FAILURE;
+    *outB = b;
+    return validate_desc(*b, *desc);
+}
+
 struct DeviceBakeResult {
     Allocator mem; DeviceResult R;
     ommCpuOpacityMicromapUsageCount arrayHist[2 * kNumLevels], indexHist[2 * kNumLevels];
     ommCpuBakeResultDesc desc;
 };
+// histogram lists and descriptor of a device-resident result whose arrays and R.hist are complete (ommxBakeDevice, the sharded bake's phase 3)
+void finish_device_result(DeviceBakeResult* res)
+{
+    const DeviceResult& R = res->R;
+    uint32_t nAH = 0, nIH = 0;
+    compact_histograms(R.hist, R.bits, res->arrayHist, res->indexHist, &nAH, &nIH);
+    fill_result_desc(&res->desc, R.arrayData, R.arrayDataSize, R.descs, R.numDescs, R.index, R.numTris, R.indexFormat, res->arrayHist, nAH, res->indexHist, nIH);
+}
 
 // result of the serial host tail -> device-resident result (ommxBakeDevice / ommxShardedBakeRccl with the opt-in lossy reducers)
 ommResult upload_host_tail(Baker& b, const HostTailResult& hres, ommIndexFormat ifmt, uint32_t T, int bits, hipStream_t stream, DeviceBakeResult* res)
@@ -1210,14 +1225,9 @@ ommResult upload_host_tail(Baker& b, const HostTailResult& hres, ommIndexFormat 
     ok = ok && R.index && (!T || HIP_OK(hipMemcpyAsync(R.index, hres.index.data(), (size_t)T * 4, hipMemcpyHostToDevice, stream)));
     ok = ok && HIP_OK(hipStreamSynchronize(stream));
     if (!ok) return b.log.failure("[Failure] - could not materialise the bake result on the device");
-    const size_t nAH = hres.arrayHist.size() < 2 * (size_t)kNumLevels ? hres.arrayHist.size() : 2 * (size_t)kNumLevels, nIH = hres.indexHist.size() < 2 * (size_t)kNumLevels ? hres.indexHist.size() : 2 * (size_t)kNumLevels;
-    memcpy(res->arrayHist, hres.arrayHist.data(), sizeof(ommCpuOpacityMicromapUsageCount) * nAH);
-    memcpy(res->indexHist, hres.indexHist.data(), sizeof(ommCpuOpacityMicromapUsageCount) * nIH);
-    res->desc.arrayData = E ? R.arrayData : nullptr; res->desc.arrayDataSize = (uint32_t)R.arrayDataSize;
-    res->desc.descArray = E ? R.descs : nullptr; res->desc.descArrayCount = E;
-    res->desc.descArrayHistogram = res->arrayHist; res->desc.descArrayHistogramCount = (uint32_t)nAH;
-    res->desc.indexBuffer = R.index; res->desc.indexCount = T; res->desc.indexFormat = ifmt;
-    res->desc.indexHistogram = res->indexHist; res->desc.indexHistogramCount = (uint32_t)nIH;
+    memcpy(res->arrayHist, hres.arrayHist.data(), sizeof(ommCpuOpacityMicromapUsageCount) * clamp_hist_count(hres.arrayHist.size()));
+    memcpy(res->indexHist, hres.indexHist.data(), sizeof(ommCpuOpacityMicromapUsageCount) * clamp_hist_count(hres.indexHist.size()));
+    fill_result_desc(&res->desc, R.arrayData, R.arrayDataSize, R.descs, E, R.index, T, ifmt, res->arrayHist, hres.arrayHist.size(), res->indexHist, hres.indexHist.size());
     return ommResult_SUCCESS;
 }
 
@@ -1264,6 +1274,18 @@ uint32_t max_index(const void* idx, ommIndexFormat fmt, size_t n)
 }
 
 ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult* out, uint32_t devices);   // (below, next to the sharded bake it is made of)
+// Sizes of the device block that holds the codec stream of `arrayBytes` of arrayData: size word (256 B) | scan scratch | [unit codes | block counts] | the stream.
+// (here, not with host_codec_layout in host_expand.h: the scratch size is the device code's to say, bake_kernels.h)
+struct CodecBlockLayout { uint64_t padded = 0, cap = 0; HostCodecLayout L{}; size_t scratchBytes = 0; bool fits = false; };
+CodecBlockLayout codec_block_layout(uint64_t arrayBytes)
+{
+    CodecBlockLayout B;
+    B.padded = (arrayBytes + 255u) & ~255ull; B.L = host_codec_layout(B.padded);
+    B.cap = B.L.offRaw + B.padded / 2u + 16u;   // a stream that does not shrink below half takes the plain copy
+    B.scratchBytes = pad256(shard_codec_scratch_bytes(B.padded));
+    B.fits = B.L.blocks < 0x7FFFFFFFull;
+    return B;
+}
 constexpr uint64_t kCompressedMinBytes = 32ull << 20;   // smaller arrays cross the link as they are (0.6 ms at 57 GB/s)
 // ommCpuBake: host arrays in, host arrays out
 ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult* out)
@@ -1277,28 +1299,24 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
     // several devices behind the one call (ommxBakerKnob_Devices): the work items are shared out, every device hands its own blocks to the host
     // (not where blocks cannot travel in their packed form -- the lossy reducers, bit 9 with the 2-state format -- and not with per-triangle formats: one device)
     if (const uint64_t nd = baker.knob(ommxBakerKnob_Devices))
-        if (nd >= 2 && !wants_host_tail(d) && !d.formats && !(((uint32_t)d.bakeFlags & (1u << 9)) != 0 && d.format == ommFormat_OC1_2_State)) return bake_impl_multi(baker, d, out, (uint32_t)nd);
+        if (nd >= 2 && !wants_host_tail(d) && !d.formats && !no_fine_two_state(d)) return bake_impl_multi(baker, d, out, (uint32_t)nd);
     const DeviceScope onBakersDevice(baker.bind_device());
     BakeSession ses(baker);
     if (!ses.open()) return L.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)");
     hipStream_t stream = ses.stream;
 
     // ---- upload the caller's triangle data (the C ABI gives no vertex count: it is max(index)+1, as serialize_impl.cpp:60-79) ----
-    const size_t idxSize = d.indexFormat == ommIndexFormat_UINT_8 ? 1 : (d.indexFormat == ommIndexFormat_UINT_16 ? 2 : 4);
-    const uint32_t maxIndex = max_index(d.indexBuffer, d.indexFormat, 3ull * T);
-    const uint32_t stride = d.texCoordStrideInBytes ? d.texCoordStrideInBytes : (d.texCoordFormat == ommTexCoordFormat_UV32_FLOAT ? 8u : 4u);
-    const size_t elem = d.texCoordFormat == ommTexCoordFormat_UV32_FLOAT ? 8 : 4;
-    const size_t uvBytes = T ? (size_t)stride * maxIndex + elem : 0, idxBytes = idxSize * 3ull * T, lvlBytes = d.subdivisionLevels ? T : 0;
-    uint8_t* dRaw = (uint8_t*)baker.devPool->acquire(pad256(uvBytes) + pad256(idxBytes) + pad256(lvlBytes) + 256);
+    const RawInputLayout raw = raw_input_layout(d, T, max_index(d.indexBuffer, d.indexFormat, 3ull * T));
+    uint8_t* dRaw = (uint8_t*)baker.devPool->acquire(raw.total);
     if (!dRaw) return L.failure("[Failure] - out of device memory for the triangle data");
     struct RawGuard { DevPool* pool; uint8_t* p; ~RawGuard() { pool->release(p); } } rawGuard{ baker.devPool.get(), dRaw };
     EventTimer et(stream);
     const int u0 = et.mark();
-    DeviceInputs din; din.texCoords = dRaw; din.indices = dRaw + pad256(uvBytes); din.perTriLevels = lvlBytes ? dRaw + pad256(uvBytes) + pad256(idxBytes) : nullptr;
+    DeviceInputs din; din.texCoords = dRaw + raw.offUv; din.indices = dRaw + raw.offIdx; din.perTriLevels = raw.lvlBytes ? dRaw + raw.offLvl : nullptr;
     bool ok = true;
-    if (uvBytes) ok = ok && HIP_OK(hipMemcpyAsync(dRaw, d.texCoords, uvBytes, hipMemcpyHostToDevice, stream));
-    if (idxBytes) ok = ok && HIP_OK(hipMemcpyAsync(dRaw + pad256(uvBytes), d.indexBuffer, idxBytes, hipMemcpyHostToDevice, stream));
-    if (lvlBytes) ok = ok && HIP_OK(hipMemcpyAsync(dRaw + pad256(uvBytes) + pad256(idxBytes), d.subdivisionLevels, lvlBytes, hipMemcpyHostToDevice, stream));
+    if (raw.uvBytes) ok = ok && HIP_OK(hipMemcpyAsync(dRaw + raw.offUv, d.texCoords, raw.uvBytes, hipMemcpyHostToDevice, stream));
+    if (raw.idxBytes) ok = ok && HIP_OK(hipMemcpyAsync(dRaw + raw.offIdx, d.indexBuffer, raw.idxBytes, hipMemcpyHostToDevice, stream));
+    if (raw.lvlBytes) ok = ok && HIP_OK(hipMemcpyAsync(dRaw + raw.offLvl, d.subdivisionLevels, raw.lvlBytes, hipMemcpyHostToDevice, stream));
     if (!ok) return L.failure("[Failure] - host to device transfer failed");
     const int u1 = et.mark();
 
@@ -1316,28 +1334,16 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
         if (!res) return ommResult_FAILURE;
         res->mem = baker.mem;
         const uint32_t E = (uint32_t)hres.descs.size();
-        if (E) {
-            res->arrayData = baker.mem.allocate(hres.arrayData.size(), 64); res->descs = (ommCpuOpacityMicromapDesc*)baker.mem.allocate(sizeof(ommCpuOpacityMicromapDesc) * (size_t)E, 16);
-        }
-        res->index = (int32_t*)baker.mem.allocate(sizeof(int32_t) * (size_t)(T ? T : 1), 16);
-        res->triArea = (float*)baker.mem.allocate(sizeof(float) * (size_t)(T ? T : 1), 16);
-        res->arrayHist = (ommCpuOpacityMicromapUsageCount*)baker.mem.allocate(sizeof(ommCpuOpacityMicromapUsageCount) * 2 * kNumLevels, 16);
-        res->indexHist = (ommCpuOpacityMicromapUsageCount*)baker.mem.allocate(sizeof(ommCpuOpacityMicromapUsageCount) * 2 * kNumLevels, 16);
-        if ((E && (!res->arrayData || !res->descs)) || !res->index || !res->triArea || !res->arrayHist || !res->indexHist)
-            { baker.mem.destroy(res); return L.failure("[Failure] - the memory allocator returned null for the bake result"); }
+        if (alloc_host_result(baker, res, E, hres.arrayData.size(), T) != ommResult_SUCCESS) { baker.mem.destroy(res); return ommResult_FAILURE; }
         if (T && (!HIP_OK(hipMemcpyAsync(res->triArea, R.triAreaScratch, sizeof(float) * (size_t)T, hipMemcpyDeviceToHost, stream)) || !HIP_OK(hipStreamSynchronize(stream))))
             { baker.mem.destroy(res); return L.failure("[Failure] - device to host transfer of the bake result failed"); }
         if (E) { memcpy(res->arrayData, hres.arrayData.data(), hres.arrayData.size()); memcpy(res->descs, hres.descs.data(), sizeof(ommCpuOpacityMicromapDesc) * (size_t)E); }
         memcpy(res->index, hres.index.data(), sizeof(int32_t) * (size_t)T);
-        memcpy(res->arrayHist, hres.arrayHist.data(), sizeof(ommCpuOpacityMicromapUsageCount) * hres.arrayHist.size());
-        memcpy(res->indexHist, hres.indexHist.data(), sizeof(ommCpuOpacityMicromapUsageCount) * hres.indexHist.size());
-        res->desc.arrayData = E ? res->arrayData : nullptr; res->desc.arrayDataSize = E ? (uint32_t)hres.arrayData.size() : 0;
-        res->desc.descArray = E ? res->descs : nullptr; res->desc.descArrayCount = E;
-        res->desc.descArrayHistogram = res->arrayHist; res->desc.descArrayHistogramCount = (uint32_t)hres.arrayHist.size();
-        res->desc.indexBuffer = res->index; res->desc.indexCount = T; res->desc.indexFormat = ifmt;
-        res->desc.indexHistogram = res->indexHist; res->desc.indexHistogramCount = (uint32_t)hres.indexHist.size();
+        memcpy(res->arrayHist, hres.arrayHist.data(), sizeof(ommCpuOpacityMicromapUsageCount) * clamp_hist_count(hres.arrayHist.size()));
+        memcpy(res->indexHist, hres.indexHist.data(), sizeof(ommCpuOpacityMicromapUsageCount) * clamp_hist_count(hres.indexHist.size()));
+        fill_result_desc(&res->desc, res->arrayData, hres.arrayData.size(), res->descs, E, res->index, T, ifmt, res->arrayHist, hres.arrayHist.size(), res->indexHist, hres.indexHist.size());
         tm.totalMs = (float)(now_ms() - t0);
-        { std::lock_guard<std::mutex> g(baker.timingsMu); baker.timings = tm; baker.haveTimings = true; }
+        store_timings(baker, tm);
         *out = (ommCpuBakeResult)res;
         return ommResult_SUCCESS;
     }
@@ -1398,11 +1404,7 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
     // (ommCpuBakeFlags_EnableInternalThreads, omm.h:303) and CPUs to run them on (below six, the STREAMED form -- blocks placed and copied by the DMA engine
     // while the classification runs -- is the faster one: one thread expands 30 GB/s).
     const uint64_t transferKnob = baker.knob(ommxBakerKnob_ResultTransfer);
-    // threads: three quarters of the CPUs the process may use, at most 12 -- the probe's rate is flat from 12 threads on, and a process that runs as many
-    // busy threads as its cgroup quota allows is throttled for the rest of the scheduler period as soon as anything else (the HIP runtime's threads, the
-    // caller's) runs beside them: measured 6 - 19 ms per expansion with 16 threads on 16 CPUs of quota (ommxBakerKnob_ExpandThreads overrides)
-    unsigned expandThreads = effective_cpus() * 3u / 4u; expandThreads = expandThreads > 12u ? 12u : (expandThreads < 1u ? 1u : expandThreads);
-    if (const uint64_t k = baker.knob(ommxBakerKnob_ExpandThreads)) expandThreads = (unsigned)k;
+    const unsigned expandThreads = expand_thread_count(baker);
     const bool wantCompressed = !so.forced && (transferKnob == ommxResultTransfer_Compressed ||
                                                (transferKnob == ommxResultTransfer_Auto && ((uint32_t)d.bakeFlags & (uint32_t)ommCpuBakeFlags_EnableInternalThreads) != 0 && effective_cpus() >= 6u));
     // (automatic choice with threads: both transfers are on offer, bake_core prices them once it knows the size of the bake -- a classification of 100 ms hides the
@@ -1410,17 +1412,14 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
     so.compressedAvailable = wantCompressed && transferKnob == ommxResultTransfer_Auto;
     const bool canStream = (!wantCompressed || so.compressedAvailable) && transferKnob != ommxResultTransfer_Plain && ses.open_comm() && ses.open_place();
     so.copyStream = ses.commStream; so.placeStream = ses.placeStream; so.device = baker.bind_device();
-    struct CodecOut { uint8_t* dBlock = nullptr; DevPool* pool = nullptr; uint8_t* dComp = nullptr; uint32_t* dSize = nullptr; HostCodecLayout L{}; uint64_t padded = 0, cap = 0; bool on = false;
-                      uint8_t* unitCodes = nullptr; uint32_t* blockRawCounts = nullptr; size_t scratchBytes = 0;   // (set when the gather produces the codes)
+    struct CodecOut : CodecBlockLayout { uint8_t* dBlock = nullptr; DevPool* pool = nullptr; uint8_t* dComp = nullptr; uint32_t* dSize = nullptr; bool on = false;
+                      uint8_t* unitCodes = nullptr; uint32_t* blockRawCounts = nullptr;   // (set when the gather produces the codes)
                       ~CodecOut() { if (dBlock) pool->release(dBlock); } } co;
-    // one device block for the codec: size word (256 B) | scan scratch | [unit codes | block counts] | the stream
     auto codec_block = [&](uint64_t arrayDataSize, bool withCodes) -> bool {
-        co.padded = (arrayDataSize + 255u) & ~255ull; co.L = host_codec_layout(co.padded);
-        co.cap = co.L.offRaw + co.padded / 2u + 16u;   // a stream that does not shrink below half takes the plain copy
-        co.scratchBytes = pad256(shard_codec_scratch_bytes(co.padded));
+        static_cast<CodecBlockLayout&>(co) = codec_block_layout(arrayDataSize);
         const size_t codeBytes = withCodes ? pad256((size_t)(co.padded / 16u)) : 0, countBytes = withCodes ? pad256(((size_t)co.L.blocks + 1) * 4) : 0;
         co.pool = baker.devPool.get(); co.dBlock = (uint8_t*)baker.devPool->acquire(256 + co.scratchBytes + codeBytes + countBytes + (size_t)co.cap);
-        if (!co.dBlock || co.L.blocks >= 0x7FFFFFFFull) return false;
+        if (!co.dBlock || !co.fits) return false;
         co.dSize = (uint32_t*)co.dBlock; co.dComp = co.dBlock + 256 + co.scratchBytes + codeBytes + countBytes;
         if (withCodes) { co.unitCodes = co.dBlock + 256 + co.scratchBytes; co.blockRawCounts = (uint32_t*)(co.unitCodes + codeBytes); }
         return true;
@@ -1485,7 +1484,7 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
     res->index = (int32_t*)baker.mem.allocate(sizeof(int32_t) * (size_t)(T ? T : 1), 16);
     res->triArea = (float*)baker.mem.allocate(sizeof(float) * (size_t)(T ? T : 1), 16);
     ok = ok && res->index != nullptr && res->triArea != nullptr;
-    const size_t outIdx = R.indexFormat == ommIndexFormat_UINT_8 ? 1 : (R.indexFormat == ommIndexFormat_UINT_16 ? 2 : 4);
+    const size_t outIdx = index_bytes(R.indexFormat);
     // descriptors, index buffer and triangle areas (8.6 MB at the metric configuration, into the caller's pageable arrays: each copy holds its thread until it is done).
     // With a compressed result they cross the link on the second stream WHILE the helper threads expand the array (one of the expansion's tasks issues them);
     // otherwise here, in front of the wait.
@@ -1591,21 +1590,12 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
     if (!ok) { return L.failure("[Failure] - device to host transfer of the bake result failed"); }
 
     // histograms: format {2-state, 4-state} x level ascending, non-zero entries only (:1833-1850); one global format here
-    res->arrayHist = (ommCpuOpacityMicromapUsageCount*)baker.mem.allocate(sizeof(ommCpuOpacityMicromapUsageCount) * 2 * kNumLevels, 16);
-    res->indexHist = (ommCpuOpacityMicromapUsageCount*)baker.mem.allocate(sizeof(ommCpuOpacityMicromapUsageCount) * 2 * kNumLevels, 16);
-    if (!res->arrayHist || !res->indexHist) { return L.failure("[Failure] - the memory allocator returned null for the bake result"); }
+    if (alloc_host_result(baker, res, E, (size_t)R.arrayDataSize, T) != ommResult_SUCCESS) return ommResult_FAILURE;   // (the lists: everything else is in place)
     uint32_t nAH = 0, nIH = 0;
-    for (uint32_t l = 0; l < (uint32_t)kNumLevels; ++l) {
-        if (R.hist[l]) { res->arrayHist[nAH].count = R.hist[l]; res->arrayHist[nAH].subdivisionLevel = (uint16_t)l; res->arrayHist[nAH].format = (uint16_t)R.bits; nAH++; }
-        if (R.hist[kNumLevels + l]) { res->indexHist[nIH].count = R.hist[kNumLevels + l]; res->indexHist[nIH].subdivisionLevel = (uint16_t)l; res->indexHist[nIH].format = (uint16_t)R.bits; nIH++; }
-    }
-    res->desc.arrayData = E ? res->arrayData : nullptr; res->desc.arrayDataSize = E ? (uint32_t)R.arrayDataSize : 0;
-    res->desc.descArray = E ? res->descs : nullptr; res->desc.descArrayCount = E;
-    res->desc.descArrayHistogram = res->arrayHist; res->desc.descArrayHistogramCount = nAH;
-    res->desc.indexBuffer = res->index; res->desc.indexCount = T; res->desc.indexFormat = R.indexFormat;
-    res->desc.indexHistogram = res->indexHist; res->desc.indexHistogramCount = nIH;
+    compact_histograms(R.hist, R.bits, res->arrayHist, res->indexHist, &nAH, &nIH);
+    fill_result_desc(&res->desc, res->arrayData, R.arrayDataSize, res->descs, E, res->index, T, R.indexFormat, res->arrayHist, nAH, res->indexHist, nIH);
     tm.uploadMs = et.ms(u0, u1); tm.downloadMs = et.ms(d0, d1); tm.totalMs = (float)(now_ms() - t0);
-    { std::lock_guard<std::mutex> g(baker.timingsMu); baker.timings = tm; baker.haveTimings = true; }
+    store_timings(baker, tm);
     *out = (ommCpuBakeResult)res;
     res = nullptr;   // (handed over: the guard lets go)
     return ommResult_SUCCESS;
@@ -1838,17 +1828,8 @@ OMM_MI355X_API ommResult ommCpuDestroyTexture(ommBaker baker, ommCpuTexture text
 
 OMM_MI355X_API ommResult ommCpuBake(ommBaker baker, const ommCpuBakeInputDesc* desc, ommCpuBakeResult* outBakeResult)
 {
-    if (baker == 0) return ommResult_INVALID_ARGUMENT;
-    Baker* b = untag<Baker>(baker);
-    if (desc == 0) return b->log.invalid("input desc was not set");
-    if (tag_of(baker) != kCpuBaker) return b->log.invalid("Baker was not created as the right type");
-    if (desc->texture == 0) return b->log.invalid("[Invalid Argument] - ommCpuBakeInputDesc has no texture set"); // bake_cpu_impl.cpp:97-103
-    // the dispatch table lookup precedes ValidateDesc (bake_cpu_impl.cpp:297-304): unknown sampler enums -> FAILURE
-    if (tag_of(desc->texture) == kTexture &&
-        ((unsigned)desc->runtimeSamplerDesc.addressingMode >= (unsigned)ommTextureAddressMode_MAX_NUM ||
-         (unsigned)desc->runtimeSamplerDesc.filter >= (unsigned)ommTextureFilterMode_MAX_NUM))
-        return ommResult_FAILURE;
-    const ommResult v = validate_desc(*b, *desc);
+    Baker* b = nullptr;
+    const ommResult v = check_bake_entry(baker, desc, &b);
     if (v != ommResult_SUCCESS) return v;
     return guarded(&b->log, [&] { return bake_impl(*b, *desc, outBakeResult); });
 }
@@ -2011,16 +1992,8 @@ OMM_MI355X_API ommResult ommDebugSaveAsImages(ommBaker baker, const ommCpuBakeIn
 
 OMM_MI355X_API ommResult ommxBakeDevice(ommBaker baker, const ommCpuBakeInputDesc* desc, ommxDeviceBakeResult* outResult)
 {
-    if (baker == 0) return ommResult_INVALID_ARGUMENT;
-    Baker* b = untag<Baker>(baker);
-    if (desc == 0 || outResult == 0) return b->log.invalid("input desc was not set");
-    if (tag_of(baker) != kCpuBaker) return b->log.invalid("Baker was not created as the right type");
-    if (desc->texture == 0) return b->log.invalid("[Invalid Argument] - ommCpuBakeInputDesc has no texture set");
-    if (tag_of(desc->texture) == kTexture &&
-        ((unsigned)desc->runtimeSamplerDesc.addressingMode >= (unsigned)ommTextureAddressMode_MAX_NUM ||
-         (unsigned)desc->runtimeSamplerDesc.filter >= (unsigned)ommTextureFilterMode_MAX_NUM))
-        return ommResult_FAILURE;
-    ommResult r = validate_desc(*b, *desc);
+    Baker* b = nullptr;
+    ommResult r = check_bake_entry(baker, desc, &b, outResult != 0);
     if (r != ommResult_SUCCESS) return r;
     r = scope_fences(*b, *desc, false);
     if (r != ommResult_SUCCESS) return r;
@@ -2045,25 +2018,16 @@ OMM_MI355X_API ommResult ommxBakeDevice(ommBaker baker, const ommCpuBakeInputDes
         if (hr == ommResult_SUCCESS && !keep_tri_areas(res->R, scratchR.triAreaScratch, desc->indexCount / 3u, ses.stream)) hr = b->log.failure("[Failure] - could not keep the triangle areas on the device");
         if (hr != ommResult_SUCCESS) { (void)hipStreamSynchronize(ses.stream); b->mem.destroy(res); return hr; }
         tm.totalMs = (float)(now_ms() - t0);
-        { std::lock_guard<std::mutex> g(b->timingsMu); b->timings = tm; b->haveTimings = true; }
+        store_timings(*b, tm);
         *outResult = (ommxDeviceBakeResult)res;
         return ommResult_SUCCESS;
     }
     r = bake_core(*b, *desc, din, nullptr, ses.arena, ses.states, ses.stream, et, res->R, tm);
     if (r == ommResult_SUCCESS && !keep_tri_areas(res->R, res->R.triAreaScratch, desc->indexCount / 3u, ses.stream)) r = b->log.failure("[Failure] - could not keep the triangle areas on the device");
     if (r != ommResult_SUCCESS) { (void)hipStreamSynchronize(ses.stream); b->mem.destroy(res); return r; } // (pooled blocks go back only when the stream is idle)
-    uint32_t nAH = 0, nIH = 0;
-    for (uint32_t l = 0; l < (uint32_t)kNumLevels; ++l) {
-        if (res->R.hist[l]) { res->arrayHist[nAH].count = res->R.hist[l]; res->arrayHist[nAH].subdivisionLevel = (uint16_t)l; res->arrayHist[nAH].format = (uint16_t)res->R.bits; nAH++; }
-        if (res->R.hist[kNumLevels + l]) { res->indexHist[nIH].count = res->R.hist[kNumLevels + l]; res->indexHist[nIH].subdivisionLevel = (uint16_t)l; res->indexHist[nIH].format = (uint16_t)res->R.bits; nIH++; }
-    }
-    res->desc.arrayData = res->R.arrayData; res->desc.arrayDataSize = (uint32_t)res->R.arrayDataSize;
-    res->desc.descArray = res->R.descs; res->desc.descArrayCount = res->R.numDescs;
-    res->desc.descArrayHistogram = res->arrayHist; res->desc.descArrayHistogramCount = nAH;
-    res->desc.indexBuffer = res->R.index; res->desc.indexCount = res->R.numTris; res->desc.indexFormat = res->R.indexFormat;
-    res->desc.indexHistogram = res->indexHist; res->desc.indexHistogramCount = nIH;
+    finish_device_result(res);
     tm.totalMs = (float)(now_ms() - t0);
-    { std::lock_guard<std::mutex> g(b->timingsMu); b->timings = tm; b->haveTimings = true; }
+    store_timings(*b, tm);
     *outResult = (ommxDeviceBakeResult)res;
     return ommResult_SUCCESS;
     });
@@ -2200,21 +2164,8 @@ uint64_t shard_chunk_bytes(const Baker& b, uint64_t strideBytes)
 
 ommResult sharded_checks(ommBaker baker, const ommCpuBakeInputDesc* desc, Baker** outB, bool hostTailOk)
 {
-    if (baker == 0) return ommResult_INVALID_ARGUMENT;
-    Baker* b = untag<Baker>(baker);
-    if (desc == 0) return b->log.invalid("input desc was not set");
-    if (tag_of(baker) != kCpuBaker) return b->log.invalid("Baker was not created as the right type");
-    if (desc->texture == 0) return b->log.invalid("[Invalid Argument] - ommCpuBakeInputDesc has no texture set");
-    if (tag_of(desc->texture) == kTexture &&
-        ((unsigned)desc->runtimeSamplerDesc.addressingMode >= (unsigned)ommTextureAddressMode_MAX_NUM ||
-         (unsigned)desc->runtimeSamplerDesc.filter >= (unsigned)ommTextureFilterMode_MAX_NUM))
-        return ommResult_FAILURE;
-    ommResult r = validate_desc(*b, *desc);
-    if (r != ommResult_SUCCESS) return r;
-    r = scope_fences(*b, *desc, false, hostTailOk, false);
-    if (r != ommResult_SUCCESS) return r;
-    *outB = b;
-    return ommResult_SUCCESS;
+    const ommResult r = check_bake_entry(baker, desc, outB);
+    return r != ommResult_SUCCESS ? r : scope_fences(**outB, *desc, false, hostTailOk, false);
 }
 
 // phase 1: replicated setup + triage, classification and digests of this rank's share, metadata words packed for the all-reduce.
@@ -2241,11 +2192,11 @@ ommResult sharded_tail(ShardedBake* sb)
 {
     ShardCtx& c = sb->ctx; const Logger& L = sb->baker->log; hipStream_t stream = sb->ses.stream;
     const uint32_t numActive = c.hc.activeStart[kNumLevels];
-    if (!HIP_OK(hipMemsetAsync(c.dOwner, 0xFF, c.ti.numItems ? c.ti.numItems : 1, stream))) return L.failure("[Failure] - device memset failed");
-    launch_shard_unpack_meta(c.bounds, c.dActiveIds, numActive, c.dMeta, c.dMask, (uint32_t*)c.ti.knownCount, c.ti.digests, c.dOwner, stream);
-    if (!HIP_OK(run_tail(c.ti, c.to, c.dScratch, c.scratchBytes, &c.counts, stream))) return L.failure("[Failure] - device tail failed");
+    if (!HIP_OK(hipMemsetAsync(c.tab.owner, 0xFF, c.ti.numItems ? c.ti.numItems : 1, stream))) return L.failure("[Failure] - device memset failed");
+    launch_shard_unpack_meta(c.bounds, c.tab.activeIds, numActive, c.tab.meta, c.tab.mask, (uint32_t*)c.ti.knownCount, c.ti.digests, c.tab.owner, stream);
+    if (!HIP_OK(run_tail(c.ti, c.to, c.tab.scratch, c.tab.scratchBytes, &c.counts, stream))) return L.failure("[Failure] - device tail failed");
     if (c.counts.arrayDataSize > 0xFFFFFFFFull) return ommResult_FAILURE; // bake_cpu_impl.cpp:1774-1775
-    if (!HIP_OK(run_shard_layout(c.to.order, c.to.sizes, c.dActive, c.dOwner, c.counts.numOmms, c.world, c.dCofs, c.dTotals, c.totals, c.dScratch, c.scratchBytes, stream)))
+    if (!HIP_OK(run_shard_layout(c.to.order, c.to.sizes, c.tab.active, c.tab.owner, c.counts.numOmms, c.world, c.tab.cofs, c.tab.totals, c.totals, c.tab.scratch, c.tab.scratchBytes, stream)))
         return L.failure("[Failure] - sharded layout failed");
     uint64_t mx = 0; for (uint32_t r = 0; r < c.world; ++r) mx = c.totals[r] > mx ? c.totals[r] : mx;
     c.strideBytes = (mx + 255) & ~255ull; if (c.strideBytes == 0) c.strideBytes = 256;
@@ -2263,7 +2214,7 @@ ommResult sharded_tail(ShardedBake* sb)
     if (codecBytes) { c.dComp = sb->ses.set->xchg.take<uint8_t>((size_t)c.compCap); c.dGatherComp = sb->ses.set->xchg.take<uint8_t>((size_t)c.compCap * c.world); c.dCompSize = sb->ses.set->xchg.take<uint32_t>(1); c.dCodecScratch = sb->ses.set->xchg.take<uint8_t>(c.codecScratchBytes); }
     // (the padding behind this rank's blocks travels too: zeros, which the codec folds away)
     if (c.strideBytes > c.totals[c.rank] && !HIP_OK(hipMemsetAsync(c.dContrib + c.totals[c.rank], 0, (size_t)(c.strideBytes - c.totals[c.rank]), stream))) return L.failure("[Failure] - device memset failed");
-    launch_shard_gather(c.dStates, c.dStateOfs, c.dActive, c.dOwner, c.rank, c.to.order, c.dCofs, c.to.sizes, c.counts.numOmms, c.dContrib, stream);
+    launch_shard_gather(c.dStates, c.tab.stateOfs, c.tab.active, c.tab.owner, c.rank, c.to.order, c.tab.cofs, c.to.sizes, c.counts.numOmms, c.dContrib, stream);
     return HIP_OK(hipGetLastError()) ? ommResult_SUCCESS : L.failure("[Failure] - shard gather failed");
 }
 
@@ -2284,34 +2235,22 @@ ommResult sharded_finish(ShardedBake* sb, ScatterFn&& scatter, ommxDeviceBakeRes
         R.arrayData = wantArray ? (uint8_t*)R.dev_alloc((size_t)c.counts.arrayDataSize) : nullptr; R.descs = (ommCpuOpacityMicromapDesc*)R.dev_alloc(sizeof(ommCpuOpacityMicromapDesc) * (size_t)E);
         ok = (R.arrayData != nullptr || !wantArray) && R.descs != nullptr;
         ok = scatter(ok ? R.arrayData : nullptr) && ok;   // (called either way: the RCCL form agrees on the allocation across ranks before its all-gathers)
-        if (ok) launch_write_descs(c.to.order, c.to.dstOfs, c.dLevel, c.bits, E, R.descs, stream);
+        if (ok) launch_write_descs(c.to.order, c.to.dstOfs, c.tab.level, c.bits, E, R.descs, stream);
     }
-    const bool allow8 = (c.flags & (1u << 6)) != 0, force32 = (c.flags & (1u << 2)) != 0;
-    int idxBytes = 4; R.indexFormat = ommIndexFormat_UINT_32;
-    if (allow8 && T <= 127 && !force32) { idxBytes = 1; R.indexFormat = ommIndexFormat_UINT_8; }
-    else if (T <= 32767 && !force32) { idxBytes = 2; R.indexFormat = ommIndexFormat_UINT_16; }
+    R.indexFormat = index_format_for(T, c.flags);
     R.index = R.dev_alloc((size_t)(T ? T : 1) * 4);
     ok = ok && R.index != nullptr;
-    if (ok) launch_narrow_indices(c.dIndex, T, idxBytes, R.index, stream);
-    ok = ok && HIP_OK(hipMemcpyAsync(R.hist, c.dArrayHist, sizeof(uint32_t) * kNumLevels, hipMemcpyDeviceToHost, stream));
-    ok = ok && HIP_OK(hipMemcpyAsync(R.hist + kNumLevels, c.dIndexHist, sizeof(uint32_t) * kNumLevels, hipMemcpyDeviceToHost, stream));
+    if (ok) launch_narrow_indices(c.tab.index, T, (int)index_bytes(R.indexFormat), R.index, stream);
+    ok = ok && HIP_OK(hipMemcpyAsync(R.hist, c.tab.arrayHist, sizeof(uint32_t) * kNumLevels, hipMemcpyDeviceToHost, stream));
+    ok = ok && HIP_OK(hipMemcpyAsync(R.hist + kNumLevels, c.tab.indexHist, sizeof(uint32_t) * kNumLevels, hipMemcpyDeviceToHost, stream));
     ok = ok && HIP_OK(hipStreamSynchronize(stream));
     if (!ok) { (void)hipStreamSynchronize(stream); b->mem.destroy(res); return L.failure("[Failure] - could not materialise the merged bake result on the device"); }
-    uint32_t nAH = 0, nIH = 0;
-    for (uint32_t l = 0; l < (uint32_t)kNumLevels; ++l) {
-        if (R.hist[l]) { res->arrayHist[nAH].count = R.hist[l]; res->arrayHist[nAH].subdivisionLevel = (uint16_t)l; res->arrayHist[nAH].format = (uint16_t)R.bits; nAH++; }
-        if (R.hist[kNumLevels + l]) { res->indexHist[nIH].count = R.hist[kNumLevels + l]; res->indexHist[nIH].subdivisionLevel = (uint16_t)l; res->indexHist[nIH].format = (uint16_t)R.bits; nIH++; }
-    }
-    res->desc.arrayData = R.arrayData; res->desc.arrayDataSize = (uint32_t)R.arrayDataSize;
-    res->desc.descArray = R.descs; res->desc.descArrayCount = R.numDescs;
-    res->desc.descArrayHistogram = res->arrayHist; res->desc.descArrayHistogramCount = nAH;
-    res->desc.indexBuffer = R.index; res->desc.indexCount = R.numTris; res->desc.indexFormat = R.indexFormat;
-    res->desc.indexHistogram = res->indexHist; res->desc.indexHistogramCount = nIH;
+    finish_device_result(res);
     // the bake's HIP events are complete now (Begin may have returned without synchronising)
     const int* e = c.ev;
     sb->tm.setupMs = sb->et->ms(e[0], e[1]); sb->tm.triageMs = sb->et->ms(e[1], e[2]); sb->tm.classifyMs = sb->et->ms(e[2], e[3]); sb->tm.digestMs = sb->et->ms(e[3], e[4]);
     sb->tm.totalMs = (float)(now_ms() - sb->t0);
-    { std::lock_guard<std::mutex> g(b->timingsMu); b->timings = sb->tm; b->haveTimings = true; }
+    store_timings(*b, sb->tm);
     *outResult = (ommxDeviceBakeResult)res;
     return ommResult_SUCCESS;
 }
@@ -2403,11 +2342,7 @@ ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBake
         ranks[r].tex = texture_on_device(tex0, ranks[r].dev);
         if (!ranks[r].baker || !ranks[r].tex) return L.failure("[Failure] - multi-device bake: could not set up a device (texture copy / memory)");
     }
-    const size_t idxSize = d.indexFormat == ommIndexFormat_UINT_8 ? 1 : (d.indexFormat == ommIndexFormat_UINT_16 ? 2 : 4);
-    const uint32_t maxIndex = max_index(d.indexBuffer, d.indexFormat, 3ull * T);
-    const uint32_t stride = d.texCoordStrideInBytes ? d.texCoordStrideInBytes : (d.texCoordFormat == ommTexCoordFormat_UV32_FLOAT ? 8u : 4u);
-    const size_t elem = d.texCoordFormat == ommTexCoordFormat_UV32_FLOAT ? 8 : 4;
-    const size_t uvBytes = T ? (size_t)stride * maxIndex + elem : 0, idxBytes = idxSize * 3ull * T, lvlBytes = d.subdivisionLevels ? T : 0;
+    const RawInputLayout raw = raw_input_layout(d, T, max_index(d.indexBuffer, d.indexFormat, 3ull * T));
 
     RankTeam team; team.n = N;
     std::vector<uint32_t> metaSum; size_t metaWords = 0;
@@ -2418,14 +2353,14 @@ ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBake
         const DeviceScope onDev(R.dev);
         Baker& sub = *R.baker;
         bool ok = true;
-        R.dRaw = (uint8_t*)sub.devPool->acquire(pad256(uvBytes) + pad256(idxBytes) + pad256(lvlBytes) + 256);
+        R.dRaw = (uint8_t*)sub.devPool->acquire(raw.total);
         ok = R.dRaw != nullptr;
-        if (ok && uvBytes) ok = HIP_OK(hipMemcpy(R.dRaw, d.texCoords, uvBytes, hipMemcpyHostToDevice));
-        if (ok && idxBytes) ok = HIP_OK(hipMemcpy(R.dRaw + pad256(uvBytes), d.indexBuffer, idxBytes, hipMemcpyHostToDevice));
-        if (ok && lvlBytes) ok = HIP_OK(hipMemcpy(R.dRaw + pad256(uvBytes) + pad256(idxBytes), d.subdivisionLevels, lvlBytes, hipMemcpyHostToDevice));
+        if (ok && raw.uvBytes) ok = HIP_OK(hipMemcpy(R.dRaw + raw.offUv, d.texCoords, raw.uvBytes, hipMemcpyHostToDevice));
+        if (ok && raw.idxBytes) ok = HIP_OK(hipMemcpy(R.dRaw + raw.offIdx, d.indexBuffer, raw.idxBytes, hipMemcpyHostToDevice));
+        if (ok && raw.lvlBytes) ok = HIP_OK(hipMemcpy(R.dRaw + raw.offLvl, d.subdivisionLevels, raw.lvlBytes, hipMemcpyHostToDevice));
         ommCpuBakeInputDesc dd = d;
         dd.texture = (ommCpuTexture)((uintptr_t)R.tex | kTexture);
-        dd.texCoords = R.dRaw; dd.indexBuffer = R.dRaw + pad256(uvBytes); dd.subdivisionLevels = lvlBytes ? R.dRaw + pad256(uvBytes) + pad256(idxBytes) : nullptr;
+        dd.texCoords = R.dRaw + raw.offUv; dd.indexBuffer = R.dRaw + raw.offIdx; dd.subdivisionLevels = raw.lvlBytes ? R.dRaw + raw.offLvl : nullptr;
         if (ok) { R.status = sharded_begin(&sub, &dd, r, N, false, &R.sb); ok = R.status == ommResult_SUCCESS; if (!ok) R.sb = nullptr; }
         else R.status = ommResult_FAILURE;
         if (!team.barrier(ok)) return;
@@ -2433,33 +2368,30 @@ ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBake
         ShardCtx& c = R.sb->ctx; hipStream_t stream = R.sb->ses.stream;
         const size_t words = 4ull * c.hc.activeStart[kNumLevels];
         R.meta.resize(words ? words : 1);
-        if (words) ok = HIP_OK(hipMemcpy(R.meta.data(), c.dMeta, words * 4, hipMemcpyDeviceToHost));
+        if (words) ok = HIP_OK(hipMemcpy(R.meta.data(), c.tab.meta, words * 4, hipMemcpyDeviceToHost));
         if (r == 0) { metaWords = words; metaSum.assign(words ? words : 1, 0u); }
         if (!team.barrier(ok)) return;
         if (!team.barrier(words == metaWords)) return;   // (every rank ran the same set-up: anything else is an internal error -- and nobody may read a shorter copy)
         for (size_t k = metaWords * r / N; k < metaWords * (r + 1) / N; ++k) { uint32_t a = 0; for (uint32_t q = 0; q < N; ++q) a += ranks[q].meta[k]; metaSum[k] = a; }
         if (!team.barrier(true)) return;
-        if (words) ok = HIP_OK(hipMemcpy(c.dMeta, metaSum.data(), words * 4, hipMemcpyHostToDevice));
+        if (words) ok = HIP_OK(hipMemcpy(c.tab.meta, metaSum.data(), words * 4, hipMemcpyHostToDevice));
         // ---- replicated tail, layout, this rank's blocks packed into its contribution ----
         if (ok) { R.status = sharded_tail(R.sb); ok = R.status == ommResult_SUCCESS; }
         // ---- the contribution as a codec stream, over this device's own link ----
-        const uint64_t padded = c.strideBytes;
-        const HostCodecLayout Lc = host_codec_layout(padded);
-        const uint64_t cap = Lc.offRaw + padded / 2u + 16u;
-        const size_t scratchBytes = pad256(shard_codec_scratch_bytes(padded));
-        if (ok) { R.dCodec = (uint8_t*)sub.devPool->acquire(256 + scratchBytes + (size_t)cap); ok = R.dCodec != nullptr && Lc.blocks < 0x7FFFFFFFull; }
+        const CodecBlockLayout cb = codec_block_layout(c.strideBytes);   // (a multiple of 256 already: cb.padded is the stride)
+        if (ok) { R.dCodec = (uint8_t*)sub.devPool->acquire(256 + cb.scratchBytes + (size_t)cb.cap); ok = R.dCodec != nullptr && cb.fits; }
         uint64_t streamBytes = 0;
         if (ok) {
-            uint8_t* dComp = R.dCodec + 256 + scratchBytes;
-            ok = HIP_OK(run_shard_compress(c.dContrib, padded, dComp, cap, (uint32_t*)R.dCodec, R.dCodec + 256, scratchBytes, stream))
+            uint8_t* dComp = R.dCodec + 256 + cb.scratchBytes;
+            ok = HIP_OK(run_shard_compress(c.dContrib, cb.padded, dComp, cb.cap, (uint32_t*)R.dCodec, R.dCodec + 256, cb.scratchBytes, stream))
               && HIP_OK(hipMemcpyAsync(&streamBytes, dComp, 8, hipMemcpyDeviceToHost, stream)) && HIP_OK(hipStreamSynchronize(stream));
-            R.raw = ok && (streamBytes > cap || streamBytes < Lc.offRaw);
+            R.raw = ok && (streamBytes > cb.cap || streamBytes < cb.L.offRaw);
             const uint64_t take = R.raw ? c.totals[r] : streamBytes;
             ok = ok && R.sb->ses.set->pinned.reserve((size_t)take + 4096);
             if (ok && take) ok = HIP_OK(hipMemcpyAsync(R.sb->ses.set->pinned.base, R.raw ? c.dContrib : dComp, (size_t)take, hipMemcpyDeviceToHost, stream)) && HIP_OK(hipStreamSynchronize(stream));
             R.hStream = R.sb->ses.set->pinned.base;
         }
-        if (r == 0) { layout = Lc; strideBytes = padded; }
+        if (r == 0) { layout = cb.L; strideBytes = cb.padded; }
         (void)team.barrier(ok);
     };
     // rank 0 is the calling thread; a rank whose thread cannot be started is run by the caller AFTER the others would deadlock the barriers: refuse instead
@@ -2494,9 +2426,9 @@ ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBake
     const SyncOnExit drainBeforeVectors{ stream0 };
     bool ok = true;
     if (E) ok = HIP_OK(hipMemcpyAsync(hOrder.data(), c0.to.order, (size_t)E * 4, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(hDstOfs.data(), c0.to.dstOfs, (size_t)E * 4, hipMemcpyDeviceToHost, stream0))
-              && HIP_OK(hipMemcpyAsync(hSizes.data(), c0.to.sizes, (size_t)E * 4, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(hCofs.data(), c0.dCofs, (size_t)E * 8, hipMemcpyDeviceToHost, stream0));
-    if (ok && U) ok = HIP_OK(hipMemcpyAsync(hActive.data(), c0.dActive, U, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(hOwner.data(), c0.dOwner, U, hipMemcpyDeviceToHost, stream0))
-                   && HIP_OK(hipMemcpyAsync(hLevel.data(), c0.dLevel, U, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(hMask.data(), c0.dMask, (size_t)U * 4, hipMemcpyDeviceToHost, stream0));
+              && HIP_OK(hipMemcpyAsync(hSizes.data(), c0.to.sizes, (size_t)E * 4, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(hCofs.data(), c0.tab.cofs, (size_t)E * 8, hipMemcpyDeviceToHost, stream0));
+    if (ok && U) ok = HIP_OK(hipMemcpyAsync(hActive.data(), c0.tab.active, U, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(hOwner.data(), c0.tab.owner, U, hipMemcpyDeviceToHost, stream0))
+                   && HIP_OK(hipMemcpyAsync(hLevel.data(), c0.tab.level, U, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(hMask.data(), c0.tab.mask, (size_t)U * 4, hipMemcpyDeviceToHost, stream0));
     ommxDeviceBakeResult dres = nullptr;
     if (ok) { const ommResult fr = sharded_finish(sb0, [](uint8_t*) { return true; }, &dres, false); if (fr != ommResult_SUCCESS) return fr; }   // (synchronises the stream: the copies above are complete)
     if (!ok) return L.failure("[Failure] - device to host transfer of the bake result failed");
@@ -2509,19 +2441,11 @@ ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBake
     res->mem = baker.mem;
     struct ResGuard { Baker& b; BakeResult*& r; ~ResGuard() { if (r) b.mem.destroy(r); } } resGuard{ baker, res };
     const SyncOnExit drainBeforeResult{ stream0 };
-    if (E) {
-        if (baker.mem.alloc == default_alloc && baker.hostPool->wants((size_t)DR.arrayDataSize)) { res->arrayData = baker.hostPool->acquire((size_t)DR.arrayDataSize); if (res->arrayData) res->pool = baker.hostPool; }
-        if (!res->arrayData) res->arrayData = baker.mem.allocate((size_t)DR.arrayDataSize, 64);
-        res->descs = (ommCpuOpacityMicromapDesc*)baker.mem.allocate(sizeof(ommCpuOpacityMicromapDesc) * (size_t)E, 16);
-    }
-    res->index = (int32_t*)baker.mem.allocate(sizeof(int32_t) * (size_t)(T ? T : 1), 16);
-    res->triArea = (float*)baker.mem.allocate(sizeof(float) * (size_t)(T ? T : 1), 16);
-    res->arrayHist = (ommCpuOpacityMicromapUsageCount*)baker.mem.allocate(sizeof(ommCpuOpacityMicromapUsageCount) * 2 * kNumLevels, 16);
-    res->indexHist = (ommCpuOpacityMicromapUsageCount*)baker.mem.allocate(sizeof(ommCpuOpacityMicromapUsageCount) * 2 * kNumLevels, 16);
-    if ((E && (!res->arrayData || !res->descs)) || !res->index || !res->triArea || !res->arrayHist || !res->indexHist) return L.failure("[Failure] - the memory allocator returned null for the bake result");
-    const size_t outIdx = DR.indexFormat == ommIndexFormat_UINT_8 ? 1 : (DR.indexFormat == ommIndexFormat_UINT_16 ? 2 : 4);
+    if (E && baker.mem.alloc == default_alloc && baker.hostPool->wants((size_t)DR.arrayDataSize)) { res->arrayData = baker.hostPool->acquire((size_t)DR.arrayDataSize); if (res->arrayData) res->pool = baker.hostPool; }
+    if (alloc_host_result(baker, res, E, (size_t)DR.arrayDataSize, T) != ommResult_SUCCESS) return ommResult_FAILURE;
+    const size_t outIdx = index_bytes(DR.indexFormat);
     if (E) ok = HIP_OK(hipMemcpyAsync(res->descs, DR.descs, sizeof(ommCpuOpacityMicromapDesc) * (size_t)E, hipMemcpyDeviceToHost, stream0));
-    if (ok && T) ok = HIP_OK(hipMemcpyAsync(res->index, DR.index, outIdx * T, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(res->triArea, c0.dTriArea, sizeof(float) * (size_t)T, hipMemcpyDeviceToHost, stream0));
+    if (ok && T) ok = HIP_OK(hipMemcpyAsync(res->index, DR.index, outIdx * T, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(res->triArea, c0.tab.triArea, sizeof(float) * (size_t)T, hipMemcpyDeviceToHost, stream0));
     // the blocks: OMM ranges of ~2 MiB each to the helper threads, while the small arrays above are on their way
     uint32_t threadsUsed = 1;
     if (ok && E) {
@@ -2533,9 +2457,7 @@ ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBake
         std::vector<uint32_t> cut; cut.push_back(0);
         uint64_t acc = 0; for (uint32_t j = 0; j < E; ++j) { acc += hSizes[j]; if (acc >= ((uint64_t)2 << 20)) { cut.push_back(j + 1); acc = 0; } }
         if (cut.back() != E) cut.push_back(E);
-        unsigned nth = effective_cpus() * 3u / 4u; nth = nth > 12u ? 12u : (nth < 1u ? 1u : nth);
-        if (const uint64_t k = baker.knob(ommxBakerKnob_ExpandThreads)) nth = (unsigned)k;
-        const std::shared_ptr<WorkerPool> pool = baker.worker_pool(nth);
+        const std::shared_ptr<WorkerPool> pool = baker.worker_pool(expand_thread_count(baker));
         if (baker.knob(ommxBakerKnob_HelperAffinity) == 0) (void)pool->bind_near(res->arrayData);
         pool->run((uint32_t)cut.size() - 1u, [&](uint32_t t) { codec_scatter_omms(S, cut[t], cut[t + 1]); });
         threadsUsed = pool->workers() + 1u;
@@ -2544,11 +2466,7 @@ ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBake
     if (!ok) return L.failure("[Failure] - device to host transfer of the bake result failed");
     memcpy(res->arrayHist, dr->arrayHist, sizeof(ommCpuOpacityMicromapUsageCount) * 2 * kNumLevels);
     memcpy(res->indexHist, dr->indexHist, sizeof(ommCpuOpacityMicromapUsageCount) * 2 * kNumLevels);
-    res->desc.arrayData = E ? res->arrayData : nullptr; res->desc.arrayDataSize = E ? (uint32_t)DR.arrayDataSize : 0;
-    res->desc.descArray = E ? res->descs : nullptr; res->desc.descArrayCount = E;
-    res->desc.descArrayHistogram = res->arrayHist; res->desc.descArrayHistogramCount = dr->desc.descArrayHistogramCount;
-    res->desc.indexBuffer = res->index; res->desc.indexCount = T; res->desc.indexFormat = DR.indexFormat;
-    res->desc.indexHistogram = res->indexHist; res->desc.indexHistogramCount = dr->desc.indexHistogramCount;
+    fill_result_desc(&res->desc, res->arrayData, DR.arrayDataSize, res->descs, E, res->index, T, DR.indexFormat, res->arrayHist, dr->desc.descArrayHistogramCount, res->indexHist, dr->desc.indexHistogramCount);
     {
         std::lock_guard<std::mutex> g(baker.timingsMu);   // (sharded_finish stored rank 0's phase clocks)
         uint64_t wire = 0; for (uint32_t r = 0; r < N; ++r) wire += ranks[r].raw ? c0.totals[r] : (ranks[r].hStream ? *(const uint64_t*)ranks[r].hStream : 0);
@@ -2581,7 +2499,7 @@ OMM_MI355X_API ommResult ommxShardedGetMeta(ommxShardedBake h, void** deviceWord
 {
     if (h == 0 || deviceWords == nullptr || numWords == nullptr) return ommResult_INVALID_ARGUMENT;
     ShardedBake* sb = (ShardedBake*)h;
-    *deviceWords = sb->ctx.dMeta; *numWords = 4ull * sb->ctx.hc.activeStart[kNumLevels];
+    *deviceWords = sb->ctx.tab.meta; *numWords = 4ull * sb->ctx.hc.activeStart[kNumLevels];
     return ommResult_SUCCESS;
 }
 
@@ -2615,7 +2533,7 @@ OMM_MI355X_API ommResult ommxShardedFinish(ommxShardedBake h, const void* gather
             const uint64_t chunkBytes = shard_chunk_bytes(*sb->baker, c.strideBytes);
             for (uint64_t lo = 0; lo < c.strideBytes; lo += chunkBytes) {
                 const uint64_t hi = lo + chunkBytes < c.strideBytes ? lo + chunkBytes : c.strideBytes;
-                launch_shard_scatter((const uint8_t*)gathered + lo, c.strideBytes, lo, hi, c.dActive, c.dOwner, c.dMask, c.dLevel, c.bits, c.to.order, c.dCofs, c.to.dstOfs, c.to.sizes,
+                launch_shard_scatter((const uint8_t*)gathered + lo, c.strideBytes, lo, hi, c.tab.active, c.tab.owner, c.tab.mask, c.tab.level, c.bits, c.to.order, c.tab.cofs, c.to.dstOfs, c.to.sizes,
                                      c.counts.numOmms, arrayData, sb->ses.stream);
             }
             return true;
@@ -2731,12 +2649,12 @@ OMM_MI355X_API ommResult ommxShardedBakeRccl(ommBaker baker, const ommCpuBakeInp
             // Every rank classified its share into a zeroed buffer, so SUM all-reduces of the metadata words and of the packed states merge
             // them; each rank then runs the identical serial tail on the host and uploads the (identical) result.
             const size_t words = 4ull * c.hc.activeStart[kNumLevels], stateWords = (size_t)(c.hc.stateBytes / 4);
-            int e = words ? rc->all_reduce(c.dMeta, c.dMeta, words, kRcclSum, stream) : 0;
+            int e = words ? rc->all_reduce(c.tab.meta, c.tab.meta, words, kRcclSum, stream) : 0;
             if (e == 0 && stateWords) e = rc->all_reduce(c.dStates, c.dStates, stateWords, kRcclSum, stream);
             if (e != 0) return nccl_fail(e, "ncclAllReduce of the micro-triangle states");
-            launch_shard_unpack_meta(c.bounds, c.dActiveIds, c.hc.activeStart[kNumLevels], c.dMeta, c.dMask, (uint32_t*)c.ti.knownCount, c.ti.digests, c.dOwner, stream);
+            launch_shard_unpack_meta(c.bounds, c.tab.activeIds, c.hc.activeStart[kNumLevels], c.tab.meta, c.tab.mask, (uint32_t*)c.ti.knownCount, c.ti.digests, c.tab.owner, stream);
             std::vector<HostItem> items;
-            r = gather_host_items(L, stream, c.ti.numItems, c.T, c.hc, c.ti.uv, c.dLevel, c.dActive, c.dMask, c.dStateOfs, c.dStates, c.ti.triToItem, c.bits, items);
+            r = gather_host_items(L, stream, c.ti.numItems, c.T, c.hc, c.ti.uv, c.tab.level, c.tab.active, c.tab.mask, c.tab.stateOfs, c.dStates, c.ti.triToItem, c.bits, items);
             HostTailResult hres; ommIndexFormat ifmt = ommIndexFormat_UINT_32;
             if (r == ommResult_SUCCESS) r = run_host_tail_for(*desc, c.T, items, hres, ifmt);
             if (r != ommResult_SUCCESS) return r;
@@ -2748,13 +2666,13 @@ OMM_MI355X_API ommResult ommxShardedBakeRccl(ommBaker baker, const ommCpuBakeInp
             const int* ev = c.ev;
             sb->tm.setupMs = sb->et->ms(ev[0], ev[1]); sb->tm.triageMs = sb->et->ms(ev[1], ev[2]); sb->tm.classifyMs = sb->et->ms(ev[2], ev[3]);
             sb->tm.tailMs = (float)(now_ms() - t1); sb->tm.totalMs = (float)(now_ms() - sb->t0);
-            { std::lock_guard<std::mutex> g(b->timingsMu); b->timings = sb->tm; b->haveTimings = true; }
+            store_timings(*b, sb->tm);
             *outResult = (ommxDeviceBakeResult)res;
             return ommResult_SUCCESS;
         }
         // exchange 1: per-item metadata, SUM all-reduce in place, on the bake's own stream right behind the digests
         const size_t words = 4ull * c.hc.activeStart[kNumLevels];
-        if (words) { const int e = rc->all_reduce(c.dMeta, c.dMeta, words, kRcclSum, stream); if (e != 0) return nccl_fail(e, "ncclAllReduce of the work-item metadata"); }
+        if (words) { const int e = rc->all_reduce(c.tab.meta, c.tab.meta, words, kRcclSum, stream); if (e != 0) return nccl_fail(e, "ncclAllReduce of the work-item metadata"); }
         r = sharded_tail(sb);
         if (!rccl_agree(rc, stream, r == ommResult_SUCCESS, L, "tail of the bake")) return r != ommResult_SUCCESS ? r : ommResult_FAILURE;
         sb->tm.tailMs = (float)(now_ms() - t1);
@@ -2780,7 +2698,7 @@ OMM_MI355X_API ommResult ommxShardedBakeRccl(ommBaker baker, const ommCpuBakeInp
                 const int e = rc->all_gather(c.dComp, c.dGatherComp, sendBytes, stream);
                 if (e != 0) { (void)nccl_fail(e, "ncclAllGather of the OMM blocks"); (void)hipEventDestroy(ready); return false; }
                 // every block straight from its owner's stream to its final offset (no expanded copy of the contributions)
-                launch_shard_scatter_streams(c.dGatherComp, sendBytes, c.strideBytes, c.dActive, c.dOwner, c.dMask, c.dLevel, c.bits, c.to.order, c.dCofs, c.to.dstOfs, c.to.sizes, E, arrayData, stream);
+                launch_shard_scatter_streams(c.dGatherComp, sendBytes, c.strideBytes, c.tab.active, c.tab.owner, c.tab.mask, c.tab.level, c.bits, c.to.order, c.tab.cofs, c.to.dstOfs, c.to.sizes, E, arrayData, stream);
                 ok = HIP_OK(hipGetLastError()) && HIP_OK(hipStreamSynchronize(stream));
                 (void)hipEventDestroy(ready);
                 return ok;
@@ -2797,7 +2715,7 @@ OMM_MI355X_API ommResult ommxShardedBakeRccl(ommBaker baker, const ommCpuBakeInp
                 uint8_t* stage = c.dGathered + lo * (uint64_t)rc->world;               // chunk k of all ranks: world x (hi - lo) bytes
                 ncclErr = rc->all_gather(c.dContrib + lo, stage, (size_t)(hi - lo), cs);
                 ok = ncclErr == 0 && HIP_OK(hipEventCreateWithFlags(&done[k], hipEventDisableTiming)) && HIP_OK(hipEventRecord(done[k], cs)) && HIP_OK(hipStreamWaitEvent(stream, done[k], 0));
-                if (ok) launch_shard_scatter(stage, hi - lo, lo, hi, c.dActive, c.dOwner, c.dMask, c.dLevel, c.bits, c.to.order, c.dCofs, c.to.dstOfs, c.to.sizes, E, arrayData, stream);
+                if (ok) launch_shard_scatter(stage, hi - lo, lo, hi, c.tab.active, c.tab.owner, c.tab.mask, c.tab.level, c.bits, c.to.order, c.tab.cofs, c.to.dstOfs, c.to.sizes, E, arrayData, stream);
             }
             ok = ok && HIP_OK(hipStreamSynchronize(stream));
             (void)hipStreamSynchronize(cs);
