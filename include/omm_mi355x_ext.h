@@ -332,4 +332,64 @@ typedef struct ommxDeviceTextureDesc {
 } ommxDeviceTextureDesc;
 OMM_MI355X_API ommResult ommxCreateTextureDevice(ommBaker baker, const ommxDeviceTextureDesc* desc, void* hipStream, ommCpuTexture* outTexture);
 
+/* ---- an alpha texture straight from BC1..BC5 blocks ----
+ * A bake must see the alpha the runtime shader samples: for a block-compressed texture that is the DECODED value, not the source art.  The MI355X has
+ * no texture unit that decodes BC blocks, so these two calls decode the alpha of the blocks with a kernel and return an ordinary ommCpuTexture, accepted
+ * wherever a texture is (ommCpuBake, ommxBakeDevice, the sharded and multi-device bakes, ommxResolveHits, ommCpuGetTextureDesc, ommCpuSerialize) and
+ * destroyed with ommCpuDestroyTexture.  It is byte for byte the texture ommCpuCreateTexture makes from the decoded texels, summed-area table included.
+ * ommxCreateTextureBC       `data` is HOST memory of any kind, as for ommCpuCreateTexture; pointers and pitches need no alignment beyond what a memcpy
+ *                        needs.  The blocks are uploaded with tight rows into scratch of the baker's device pool and decoded on the null stream.
+ * ommxCreateTextureBCDevice `data` is read IN PLACE from memory the baker's device can read; memory rule and the hipPointerGetAttributes check of the first
+ *                        and last byte of every mip are those of ommxCreateTextureDevice.  The decode runs on `hipStream` (null = the null stream)
+ *                        behind whatever the caller queued there; the stream is synchronised before the call returns, so the blocks may be
+ *                        overwritten or freed then.  `data` and a non-zero pitch must be multiples of 8.
+ *   the source           block (bx, by) of mip m starts at  (const char*)mips[m].data + by * rowPitchInBytes + bx * blockSize , bx < ceil(width / 4),
+ *                        by < ceil(height / 4); texel i = 4 * y + x of a block, x, y in 0..3, is texel (4 * bx + x, 4 * by + y) of the mip.  Multi-byte
+ *                        fields are little-endian.  Only the 8 bytes that hold the alpha are read: the colour half of a BC2 / BC3 block, the
+ *                        unselected channel of BC5, the codes of texels beyond width / height in a partial block and the pitch padding may hold
+ *                        anything.  A DDS file's payload is this layout with a tight pitch, mip after mip.
+ *   the value            BC1  c0 = u16 at bytes 0..1, c1 = u16 at bytes 2..3, code = bits 2i..2i+1 of the u32 at bytes 4..7: byte 0 if c0 <= c1 and
+ *                             code == 3, else byte 255.                                                              -> UNORM8 texture
+ *                        BC2  a = bits 4i..4i+3 of the u64 at bytes 0..7: byte 17 * a.                               -> UNORM8 texture
+ *                        BC3 (bytes 0..7), BC4 (the block), BC5 (bytes 0..7 for channel 0, 8..15 for channel 1)      -> FP32 texture
+ *                             a0 = byte 0, a1 = byte 1, k = bits 3i..3i+2 of the 48-bit integer at bytes 2..7.  The texel is n / D:
+ *                             a0 > a1:  D = 7;  k = 0: n = 7 a0;  k = 1: n = 7 a1;  k = 2..7: n = (8 - k) a0 + (k - 1) a1
+ *                             else:     D = 5;  k = 0: n = 5 a0;  k = 1: n = 5 a1;  k = 2..5: n = (6 - k) a0 + (k - 1) a1;  k = 6: n = 0;  k = 7: n = 5 * 255
+ *                             stored as the fp32  ((float)n / (float)D) * (1.f / 255.f) : one IEEE division, then the multiplication the
+ *                             classification applies to a UNORM8 byte.  Where the code selects an integer alpha a (k = 0, 1, and 6, 7 of the second
+ *                             mode) the texel is bit for bit the value the library gives the UNORM8 byte a, so such a texture bakes exactly like
+ *                             the UNORM8 texture of those bytes; everywhere else it is the interpolated value "as a float", as D3D10+ defines these
+ *                             formats (not rounded to a byte), within 1.5 ulp of the real quotient n / (255 D).
+ *   not covered          the SNORM variants of BC4 / BC5, BC6H and BC7: decode those yourself and use ommxCreateTextureDevice.  The enum leaves
+ *                        room at its end.
+ *   result codes         INVALID_ARGUMENT, each with a log line of its own and judged before the device is touched: a null baker, desc or outTexture;
+ *                        a baker not of CPU type; mips null with mipCount != 0; mipCount 0 or above 17; a width or height of 0 or above 65536; a
+ *                        null data; a format outside the enum; a channel above 1, or non-zero for a format other than BC5; a non-zero pitch below
+ *                        ceil(width / 4) * blockSize; ommxCreateTextureBCDevice only: data or a pitch that is not a multiple of 8.  After that,
+ *                        ommxCreateTextureBCDevice only: a mip whose first or last byte the baker's device cannot read is INVALID_ARGUMENT, before
+ *                        anything is launched.  Without a usable HIP device: FAILURE (no CPU fallback).  *outTexture is written on SUCCESS only. */
+typedef enum ommxBlockFormat {
+    ommxBlockFormat_BC1 = 0,   /*  8-byte blocks; alpha = the punch-through bit                              -> UNORM8 texture */
+    ommxBlockFormat_BC2 = 1,   /* 16-byte blocks; alpha = the explicit 4-bit values of bytes 0..7            -> UNORM8 texture */
+    ommxBlockFormat_BC3 = 2,   /* 16-byte blocks; alpha = the interpolated block of bytes 0..7               -> FP32 texture   */
+    ommxBlockFormat_BC4 = 3,   /*  8-byte blocks; the one UNORM channel                                      -> FP32 texture   */
+    ommxBlockFormat_BC5 = 4,   /* 16-byte blocks; channel 0 (bytes 0..7) or 1 (bytes 8..15), UNORM           -> FP32 texture   */
+    ommxBlockFormat_MAX_NUM = 5
+} ommxBlockFormat;
+typedef struct ommxBlockTextureMipDesc {
+    uint32_t    width, height;      /* TEXELS; need not be multiples of 4 (the last block column / row is partial) */
+    uint32_t    rowPitchInBytes;    /* bytes from one ROW OF BLOCKS to the next; 0 = ceil(width / 4) * block size */
+    const void* data;               /* first block of the mip */
+} ommxBlockTextureMipDesc;
+typedef struct ommxBlockTextureDesc {
+    ommxBlockFormat                format;
+    uint32_t                       channel;      /* BC5: 0 or 1; every other format: must be 0 */
+    ommCpuTextureFlags             flags;
+    const ommxBlockTextureMipDesc* mips;         /* mip 0 first; independent allocations */
+    uint32_t                       mipCount;
+    float                          alphaCutoff;  /* as ommCpuTextureDesc: >= 0 gives the summed-area table */
+} ommxBlockTextureDesc;
+OMM_MI355X_API ommResult ommxCreateTextureBC(ommBaker baker, const ommxBlockTextureDesc* desc, ommCpuTexture* outTexture);
+OMM_MI355X_API ommResult ommxCreateTextureBCDevice(ommBaker baker, const ommxBlockTextureDesc* desc, void* hipStream, ommCpuTexture* outTexture);
+
 #endif

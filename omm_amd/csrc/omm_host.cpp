@@ -13,6 +13,7 @@
 #include "lookup_kernels.h"
 #include "stats_kernels.h"
 #include "texture_kernels.h"
+#include "block_kernels.h"
 
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
@@ -1776,6 +1777,67 @@ ommResult create_texture_device_impl(Baker* b, const ommxDeviceTextureDesc* desc
     }
     return tb.finish(HIP_OK(hipStreamSynchronize(stream)), outTexture);
 }
+
+// ommxCreateTextureBC / ommxCreateTextureBCDevice: the alpha of BC1..BC5 blocks, decoded by block_kernels.hip.  fromDevice: the blocks are read in place on
+// `stream`; otherwise they are host memory, uploaded with tight rows into pooled scratch and decoded on the null stream (`stream` is null then).
+ommResult create_texture_bc_impl(Baker* b, const ommxBlockTextureDesc* desc, bool fromDevice, hipStream_t stream, ommCpuTexture* outTexture)
+{
+    const Logger& L = b->log;
+    // ---- everything that can be judged without a device ----
+    if (desc->mipCount != 0 && desc->mips == nullptr) return L.invalid("[Invalid Arg] - mips is not set");
+    const ommResult checked = check_texture_mips(L, desc->mipCount, (unsigned)desc->format < (unsigned)ommxBlockFormat_MAX_NUM, desc->mips, [](const ommxBlockTextureMipDesc& m) { return m.data; });
+    if (checked != ommResult_SUCCESS) return checked;
+    if (desc->channel > 1u) return L.invalid("[Invalid Arg] - channel must be 0 or 1");
+    if (desc->channel != 0u && desc->format != ommxBlockFormat_BC5) return L.invalid("[Invalid Arg] - channel must be 0 for every format but BC5");
+    const bool small = desc->format == ommxBlockFormat_BC1 || desc->format == ommxBlockFormat_BC4;
+    const uint64_t blockBytes = small ? 8u : 16u, byteOffset = 8u * desc->channel;
+    const int kind = desc->format == ommxBlockFormat_BC1 ? kBlockBC1 : desc->format == ommxBlockFormat_BC2 ? kBlockBC2 : kBlockBC4;
+    auto row_bytes = [&](const ommxBlockTextureMipDesc& md) { return (((uint64_t)md.width + 3u) / 4u) * blockBytes; };
+    for (uint32_t i = 0; i < desc->mipCount; ++i) {
+        const ommxBlockTextureMipDesc& md = desc->mips[i];
+        if (md.rowPitchInBytes != 0 && (uint64_t)md.rowPitchInBytes < row_bytes(md)) return L.invalid("[Invalid Arg] - mips.rowPitchInBytes is smaller than ceil(width / 4) * the size of a block");
+        if (fromDevice && ((uint64_t)md.rowPitchInBytes % 8u != 0 || (uintptr_t)md.data % 8u != 0)) return L.invalid("[Invalid Arg] - mips.rowPitchInBytes and mips.data must be multiples of 8");
+    }
+    // ---- the device ----
+    const int dev = b->bind_device();
+    int deviceCount = 0;
+    if (dev < 0 || !HIP_OK(hipGetDeviceCount(&deviceCount)) || deviceCount < 1) { (void)hipGetLastError(); return L.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)"); }
+    const DeviceScope onBakersDevice(dev);
+    if (fromDevice) for (uint32_t i = 0; i < desc->mipCount; ++i) {   // first and last byte of every mip, before any launch
+        const ommxBlockTextureMipDesc& md = desc->mips[i];
+        const uint64_t pitch = md.rowPitchInBytes ? (uint64_t)md.rowPitchInBytes : row_bytes(md);
+        const uint8_t* first = (const uint8_t*)md.data;
+        if (!device_readable(first, dev) || !device_readable(first + (((uint64_t)md.height + 3u) / 4u - 1u) * pitch + row_bytes(md) - 1, dev))
+            return L.invalid("[Invalid Arg] - mips.data is not memory the baker's device can read (device memory of that device, managed or pinned host memory)");
+    }
+    TextureBuild tb(b, kind == kBlockBC4 ? ommCpuTextureFormat_FP32 : ommCpuTextureFormat_UNORM8, desc->flags, desc->alphaCutoff);
+    if (!tb.t) return ommResult_FAILURE;
+    struct Uploads { DevPool* pool; std::vector<void*> blocks; ~Uploads() { for (void* p : blocks) pool->release(p); } } uploads{ b->devPool.get(), {} };   // (released behind the synchronisation below)
+    std::vector<uint8_t> staging;
+    for (uint32_t mi = 0; mi < desc->mipCount && tb.ok; ++mi) {
+        const ommxBlockTextureMipDesc& md = desc->mips[mi];
+        const uint64_t rowBytes = row_bytes(md), blockRows = ((uint64_t)md.height + 3u) / 4u;
+        uint64_t pitch = md.rowPitchInBytes ? (uint64_t)md.rowPitchInBytes : rowBytes;
+        const void* blocks = md.data;
+        TexMip& m = tb.add_mip(md.width, md.height);
+        if (!fromDevice && tb.ok) {
+            const size_t bytes = (size_t)(rowBytes * blockRows);
+            const uint8_t* src = (const uint8_t*)md.data;
+            if (pitch != rowBytes) {
+                staging.resize(bytes);
+                for (uint64_t j = 0; j < blockRows; ++j) memcpy(staging.data() + rowBytes * j, src + pitch * j, (size_t)rowBytes);
+                src = staging.data();
+            }
+            void* up = b->devPool->acquire(bytes);
+            tb.ok = up != nullptr;
+            if (tb.ok) { uploads.blocks.push_back(up); tb.ok = HIP_OK(hipMemcpy(up, src, bytes, hipMemcpyHostToDevice)); }
+            blocks = up; pitch = rowBytes;
+        }
+        if (tb.ok) { launch_block_decode(blocks, (size_t)pitch, (uint32_t)blockBytes, (uint32_t)byteOffset, kind, m.texels, m.w, m.h, stream); tb.ok = HIP_OK(hipGetLastError()); }
+        tb.build_sat(m, stream);
+    }
+    return tb.finish(fromDevice ? HIP_OK(hipStreamSynchronize(stream)) : HIP_OK(hipDeviceSynchronize()), outTexture);
+}
 } // namespace
 
 OMM_MI355X_API ommResult ommCpuCreateTexture(ommBaker baker, const ommCpuTextureDesc* desc, ommCpuTexture* outTexture)
@@ -1797,6 +1859,25 @@ OMM_MI355X_API ommResult ommxCreateTextureDevice(ommBaker baker, const ommxDevic
     if (tag_of(baker) != kCpuBaker) return b->log.invalid("Baker was not created as the right type");
     if (outTexture == nullptr) return b->log.invalid("[Invalid Arg] - outTexture is not set");
     return guarded(&b->log, [&] { return create_texture_device_impl(b, desc, (hipStream_t)hipStream, outTexture); });
+}
+
+// A texture from the alpha of BC1..BC5 blocks (include/omm_mi355x_ext.h): the decode kernel of block_kernels.hip in front of what ommCpuCreateTexture does.
+static ommResult create_texture_bc(ommBaker baker, const ommxBlockTextureDesc* desc, bool fromDevice, void* hipStream, ommCpuTexture* outTexture)
+{
+    if (baker == 0) return ommResult_INVALID_ARGUMENT;
+    Baker* b = untag<Baker>(baker);
+    if (desc == 0) return b->log.invalid("texture desc was not set");
+    if (tag_of(baker) != kCpuBaker) return b->log.invalid("Baker was not created as the right type");
+    if (outTexture == nullptr) return b->log.invalid("[Invalid Arg] - outTexture is not set");
+    return guarded(&b->log, [&] { return create_texture_bc_impl(b, desc, fromDevice, (hipStream_t)hipStream, outTexture); });
+}
+OMM_MI355X_API ommResult ommxCreateTextureBC(ommBaker baker, const ommxBlockTextureDesc* desc, ommCpuTexture* outTexture)
+{
+    return create_texture_bc(baker, desc, false, nullptr, outTexture);
+}
+OMM_MI355X_API ommResult ommxCreateTextureBCDevice(ommBaker baker, const ommxBlockTextureDesc* desc, void* hipStream, ommCpuTexture* outTexture)
+{
+    return create_texture_bc(baker, desc, true, hipStream, outTexture);
 }
 
 OMM_MI355X_API ommResult ommCpuGetTextureDesc(ommCpuTexture texture, ommCpuTextureDesc* outDesc)
