@@ -360,8 +360,8 @@ OMM_MI355X_API ommResult ommxCreateTextureDevice(ommBaker baker, const ommxDevic
  *                             mode) the texel is bit for bit the value the library gives the UNORM8 byte a, so such a texture bakes exactly like
  *                             the UNORM8 texture of those bytes; everywhere else it is the interpolated value "as a float", as D3D10+ defines these
  *                             formats (not rounded to a byte), within 1.5 ulp of the real quotient n / (255 D).
- *   not covered          the SNORM variants of BC4 / BC5, BC6H and BC7: decode those yourself and use ommxCreateTextureDevice.  The enum leaves
- *                        room at its end.
+ *   not covered          BC7 has a call of its own, ommxCreateTextureBC7 below.  The SNORM variants of BC4 / BC5 and BC6H are not covered: decode
+ *                        those yourself and use ommxCreateTextureDevice.  The enum leaves room at its end.
  *   result codes         INVALID_ARGUMENT, each with a log line of its own and judged before the device is touched: a null baker, desc or outTexture;
  *                        a baker not of CPU type; mips null with mipCount != 0; mipCount 0 or above 17; a width or height of 0 or above 65536; a
  *                        null data; a format outside the enum; a channel above 1, or non-zero for a format other than BC5; a non-zero pitch below
@@ -391,5 +391,65 @@ typedef struct ommxBlockTextureDesc {
 } ommxBlockTextureDesc;
 OMM_MI355X_API ommResult ommxCreateTextureBC(ommBaker baker, const ommxBlockTextureDesc* desc, ommCpuTexture* outTexture);
 OMM_MI355X_API ommResult ommxCreateTextureBCDevice(ommBaker baker, const ommxBlockTextureDesc* desc, void* hipStream, ommCpuTexture* outTexture);
+
+/* ---- an alpha texture straight from BC7 blocks ----
+ * BC7 is the block format for RGBA with a real alpha channel (DXGI_FORMAT_BC7_UNORM, _UNORM_SRGB: sRGB does not touch alpha).  Its decode is defined
+ * exactly, an 8-bit integer per channel on which every conforming decoder agrees, so the result is always an ommCpuTextureFormat_UNORM8 texture: byte for
+ * byte the texture ommCpuCreateTexture makes from the decoded alpha bytes, summed-area table included, and a bake from it is bit-exact with a bake from
+ * those bytes.  It is accepted wherever a texture is (ommCpuBake, ommxBakeDevice, the sharded and multi-device bakes, ommxResolveHits,
+ * ommCpuGetTextureDesc, ommCpuSerialize) and destroyed with ommCpuDestroyTexture.
+ * ommxCreateTextureBC7       the host entry, as ommxCreateTextureBC: `data` is HOST memory of any kind, no alignment needed; the blocks are uploaded
+ *                        with tight rows into scratch of the baker's device pool and decoded on the null stream.
+ * ommxCreateTextureBC7Device the device entry, as ommxCreateTextureBCDevice: `data` is read IN PLACE from memory the baker's device can read (same memory
+ *                        rule, same hipPointerGetAttributes check of the first and last byte of every mip before anything is launched), on `hipStream`
+ *                        (null = the null stream) behind whatever the caller queued there; the stream is synchronised before the call returns.
+ *                        `data` and a non-zero pitch must be multiples of 16: a lane reads its block with one aligned 16-byte load.
+ *   the source           as ommxCreateTextureBC with 16-byte blocks: block (bx, by) of mip m starts at  (const char*)mips[m].data + by * rowPitchInBytes
+ *                        + 16 * bx ; texel i = 4 * y + x of a block is texel (4 * bx + x, 4 * by + y) of the mip.  Only the alpha is decoded: the
+ *                        colour fields are read only when rot != 0, and then only the one channel.  The index bits of texels beyond width / height
+ *                        in a partial block and the pitch padding may hold anything.  A DDS file's payload is this layout with a tight pitch.
+ *   the value            q is the 128-bit little-endian integer of the block; fields are read LSB first.
+ *                        Mode m = the number of trailing zero bits of byte 0; fields start at bit m + 1.  Byte 0 == 0 (reserved): all 16 texels
+ *                        are 0, as D3D defines it.  Modes 0..3: 255 everywhere.
+ *                        Mode 4  rot(2), idxMode(1), R0 R1 G0 G1 B0 B1 (5 bits each), A0 A1 (6 each, at bits 38 and 44); sixteen 2-bit indices from
+ *                                bit 50 (texel 0 has 1 bit: 31 bits), sixteen 3-bit indices from bit 81 (texel 0 has 2 bits: 47 bits).  idxMode == 0:
+ *                                colour uses the 2-bit set and alpha the 3-bit set; idxMode == 1: the other way round.  Endpoints widen to 8 bits by
+ *                                bit replication: 5 -> (v<<3)|(v>>2), 6 -> (v<<2)|(v>>4).
+ *                        Mode 5  rot(2), R0 R1 G0 G1 B0 B1 (7 bits each, widened (v<<1)|(v>>6)), A0 A1 (8 each, at bits 50 and 58); 2-bit colour
+ *                                indices from bit 66, 2-bit alpha indices from bit 97, each set 31 bits (texel 0 has 1 bit).
+ *                        Rotation (modes 4, 5): rot swaps A with R (1), G (2) or B (3) after interpolation.  With rot != 0 the output alpha is that
+ *                                colour channel, interpolated with the colour index set; with rot == 0 it is A with the alpha index set.
+ *                        Mode 6  R0 R1 G0 G1 B0 B1 A0 A1 (7 bits each; A0 at bit 49, A1 at bit 56), P0 (bit 63), P1 (bit 64); alpha endpoint k is
+ *                                (Ak << 1) | Pk; 4-bit indices from bit 65 (texel 0 has 3 bits).
+ *                        Mode 7  part(6, bits 8..13), then R, G, B, A with four 5-bit values each in the order subset 0 endpoint 0, subset 0 endpoint
+ *                                1, subset 1 endpoint 0, subset 1 endpoint 1 (A starts at bit 74), then P[4] in that order at bits 94..97.  An alpha
+ *                                endpoint is v = (A << 1) | P, 6 bits, widened (v<<2)|(v>>4).  2-bit indices from bit 98; texel 0 and texel
+ *                                anchor[part] have 1 bit each (30 bits).  Texel i belongs to subset (mask[part] >> i) & 1.
+ *                        Interpolation  ((64 - w) * e0 + w * e1 + 32) >> 6  with the weights  2-bit: 0 21 43 64;  3-bit: 0 9 18 27 37 46 55 64;
+ *                                4-bit: 0 4 9 13 17 21 26 30 34 38 43 47 51 55 60 64  (= (64 i + 1) / 3, (64 i + 3) / 7, (64 i + 7) / 15 in integer
+ *                                division).
+ *                        mask[64], hexadecimal, bit i is texel i:
+ *                                CCCC 8888 EEEE ECC8 C880 FEEC FEC8 EC80 C800 FFEC FE80 E800 FFE8 FF00 FFF0 F000
+ *                                F710 008E 7100 08CE 008C 7310 3100 8CCE 088C 3110 6666 366C 17E8 0FF0 718E 399C
+ *                                AAAA F0F0 5A5A 33CC 3C3C 55AA 9696 A55A 73CE 13C8 324C 3BDC 6996 C33C 9966 0660
+ *                                0272 04E4 4E40 2720 C936 936C 39C6 639C 9336 9CC6 817E E718 CCF0 0FCC 7744 EE22
+ *                        anchor[64]:
+ *                                15 15 15 15 15 15 15 15  15 15 15 15 15 15 15 15  15  2  8  2  2  8  8 15   2  8  2  2  8  8  2  2
+ *                                15 15  6  8  2  8 15 15   2  8  2  2  2 15 15  6   6  2  6  8 15 15  2  2  15 15 15 15 15  2  2 15
+ *   not covered          the colour channels of BC7 as the alpha source (modes 0..3 have three subsets), BC6H.
+ *   result codes         as ommxCreateTextureBC, without the format and channel checks: INVALID_ARGUMENT, each with a log line of its own and judged
+ *                        before the device is touched: a null baker, desc or outTexture; a baker not of CPU type; mips null with mipCount != 0;
+ *                        mipCount 0 or above 17; a width or height of 0 or above 65536; a null data; a non-zero pitch below ceil(width / 4) * 16;
+ *                        ommxCreateTextureBC7Device only: data or a pitch that is not a multiple of 16.  After that, ommxCreateTextureBC7Device only:
+ *                        a mip whose first or last byte the baker's device cannot read is INVALID_ARGUMENT, before anything is launched.  Without
+ *                        a usable HIP device: FAILURE (no CPU fallback).  *outTexture is written on SUCCESS only. */
+typedef struct ommxBC7TextureDesc {
+    ommCpuTextureFlags             flags;
+    const ommxBlockTextureMipDesc* mips;        /* mip 0 first; independent allocations; 16-byte blocks */
+    uint32_t                       mipCount;
+    float                          alphaCutoff; /* as ommCpuTextureDesc: >= 0 gives the summed-area table */
+} ommxBC7TextureDesc;
+OMM_MI355X_API ommResult ommxCreateTextureBC7(ommBaker baker, const ommxBC7TextureDesc* desc, ommCpuTexture* outTexture);
+OMM_MI355X_API ommResult ommxCreateTextureBC7Device(ommBaker baker, const ommxBC7TextureDesc* desc, void* hipStream, ommCpuTexture* outTexture);
 
 #endif

@@ -14,6 +14,7 @@
 #include "stats_kernels.h"
 #include "texture_kernels.h"
 #include "block_kernels.h"
+#include "bc7_kernels.h"
 
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
@@ -1778,44 +1779,44 @@ ommResult create_texture_device_impl(Baker* b, const ommxDeviceTextureDesc* desc
     return tb.finish(HIP_OK(hipStreamSynchronize(stream)), outTexture);
 }
 
-// ommxCreateTextureBC / ommxCreateTextureBCDevice: the alpha of BC1..BC5 blocks, decoded by block_kernels.hip.  fromDevice: the blocks are read in place on
-// `stream`; otherwise they are host memory, uploaded with tight rows into pooled scratch and decoded on the null stream (`stream` is null then).
-ommResult create_texture_bc_impl(Baker* b, const ommxBlockTextureDesc* desc, bool fromDevice, hipStream_t stream, ommCpuTexture* outTexture)
+// What ommxCreateTextureBC and ommxCreateTextureBC7 share behind their format checks: the pitch (and, on the device entry, alignment) rules, the device,
+// and the one loop over the mips.  fromDevice: the blocks are read in place on `stream`; otherwise they are host memory, uploaded with tight rows into pooled
+// scratch (hipMalloc blocks: 256-byte aligned) and decoded on the null stream (`stream` is null then).  decode(blocks, pitch, mip, stream) launches the kernel.
+struct BlockSource {
+    ommCpuTextureFlags flags; const ommxBlockTextureMipDesc* mips; uint32_t mipCount; float alphaCutoff;
+    uint64_t blockBytes;          // 8 or 16
+    uint64_t align;               // device entry: data and a non-zero pitch are multiples of this (8 or 16: the size of the kernel's one load per block)
+    ommCpuTextureFormat format;   // of the texture made
+};
+template <class Decode>
+ommResult create_texture_blocks_impl(Baker* b, const BlockSource& s, bool fromDevice, hipStream_t stream, Decode decode, ommCpuTexture* outTexture)
 {
     const Logger& L = b->log;
-    // ---- everything that can be judged without a device ----
-    if (desc->mipCount != 0 && desc->mips == nullptr) return L.invalid("[Invalid Arg] - mips is not set");
-    const ommResult checked = check_texture_mips(L, desc->mipCount, (unsigned)desc->format < (unsigned)ommxBlockFormat_MAX_NUM, desc->mips, [](const ommxBlockTextureMipDesc& m) { return m.data; });
-    if (checked != ommResult_SUCCESS) return checked;
-    if (desc->channel > 1u) return L.invalid("[Invalid Arg] - channel must be 0 or 1");
-    if (desc->channel != 0u && desc->format != ommxBlockFormat_BC5) return L.invalid("[Invalid Arg] - channel must be 0 for every format but BC5");
-    const bool small = desc->format == ommxBlockFormat_BC1 || desc->format == ommxBlockFormat_BC4;
-    const uint64_t blockBytes = small ? 8u : 16u, byteOffset = 8u * desc->channel;
-    const int kind = desc->format == ommxBlockFormat_BC1 ? kBlockBC1 : desc->format == ommxBlockFormat_BC2 ? kBlockBC2 : kBlockBC4;
-    auto row_bytes = [&](const ommxBlockTextureMipDesc& md) { return (((uint64_t)md.width + 3u) / 4u) * blockBytes; };
-    for (uint32_t i = 0; i < desc->mipCount; ++i) {
-        const ommxBlockTextureMipDesc& md = desc->mips[i];
+    auto row_bytes = [&](const ommxBlockTextureMipDesc& md) { return (((uint64_t)md.width + 3u) / 4u) * s.blockBytes; };
+    for (uint32_t i = 0; i < s.mipCount; ++i) {
+        const ommxBlockTextureMipDesc& md = s.mips[i];
         if (md.rowPitchInBytes != 0 && (uint64_t)md.rowPitchInBytes < row_bytes(md)) return L.invalid("[Invalid Arg] - mips.rowPitchInBytes is smaller than ceil(width / 4) * the size of a block");
-        if (fromDevice && ((uint64_t)md.rowPitchInBytes % 8u != 0 || (uintptr_t)md.data % 8u != 0)) return L.invalid("[Invalid Arg] - mips.rowPitchInBytes and mips.data must be multiples of 8");
+        if (fromDevice && ((uint64_t)md.rowPitchInBytes % s.align != 0 || (uintptr_t)md.data % s.align != 0))
+            return L.invalid(s.align == 8u ? "[Invalid Arg] - mips.rowPitchInBytes and mips.data must be multiples of 8" : "[Invalid Arg] - mips.rowPitchInBytes and mips.data must be multiples of 16");
     }
     // ---- the device ----
     const int dev = b->bind_device();
     int deviceCount = 0;
     if (dev < 0 || !HIP_OK(hipGetDeviceCount(&deviceCount)) || deviceCount < 1) { (void)hipGetLastError(); return L.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)"); }
     const DeviceScope onBakersDevice(dev);
-    if (fromDevice) for (uint32_t i = 0; i < desc->mipCount; ++i) {   // first and last byte of every mip, before any launch
-        const ommxBlockTextureMipDesc& md = desc->mips[i];
+    if (fromDevice) for (uint32_t i = 0; i < s.mipCount; ++i) {   // first and last byte of every mip, before any launch
+        const ommxBlockTextureMipDesc& md = s.mips[i];
         const uint64_t pitch = md.rowPitchInBytes ? (uint64_t)md.rowPitchInBytes : row_bytes(md);
         const uint8_t* first = (const uint8_t*)md.data;
         if (!device_readable(first, dev) || !device_readable(first + (((uint64_t)md.height + 3u) / 4u - 1u) * pitch + row_bytes(md) - 1, dev))
             return L.invalid("[Invalid Arg] - mips.data is not memory the baker's device can read (device memory of that device, managed or pinned host memory)");
     }
-    TextureBuild tb(b, kind == kBlockBC4 ? ommCpuTextureFormat_FP32 : ommCpuTextureFormat_UNORM8, desc->flags, desc->alphaCutoff);
+    TextureBuild tb(b, s.format, s.flags, s.alphaCutoff);
     if (!tb.t) return ommResult_FAILURE;
     struct Uploads { DevPool* pool; std::vector<void*> blocks; ~Uploads() { for (void* p : blocks) pool->release(p); } } uploads{ b->devPool.get(), {} };   // (released behind the synchronisation below)
     std::vector<uint8_t> staging;
-    for (uint32_t mi = 0; mi < desc->mipCount && tb.ok; ++mi) {
-        const ommxBlockTextureMipDesc& md = desc->mips[mi];
+    for (uint32_t mi = 0; mi < s.mipCount && tb.ok; ++mi) {
+        const ommxBlockTextureMipDesc& md = s.mips[mi];
         const uint64_t rowBytes = row_bytes(md), blockRows = ((uint64_t)md.height + 3u) / 4u;
         uint64_t pitch = md.rowPitchInBytes ? (uint64_t)md.rowPitchInBytes : rowBytes;
         const void* blocks = md.data;
@@ -1833,10 +1834,40 @@ ommResult create_texture_bc_impl(Baker* b, const ommxBlockTextureDesc* desc, boo
             if (tb.ok) { uploads.blocks.push_back(up); tb.ok = HIP_OK(hipMemcpy(up, src, bytes, hipMemcpyHostToDevice)); }
             blocks = up; pitch = rowBytes;
         }
-        if (tb.ok) { launch_block_decode(blocks, (size_t)pitch, (uint32_t)blockBytes, (uint32_t)byteOffset, kind, m.texels, m.w, m.h, stream); tb.ok = HIP_OK(hipGetLastError()); }
+        if (tb.ok) { decode(blocks, (size_t)pitch, m, stream); tb.ok = HIP_OK(hipGetLastError()); }
         tb.build_sat(m, stream);
     }
     return tb.finish(fromDevice ? HIP_OK(hipStreamSynchronize(stream)) : HIP_OK(hipDeviceSynchronize()), outTexture);
+}
+
+// ommxCreateTextureBC / ommxCreateTextureBCDevice: the alpha of BC1..BC5 blocks, decoded by block_kernels.hip.
+ommResult create_texture_bc_impl(Baker* b, const ommxBlockTextureDesc* desc, bool fromDevice, hipStream_t stream, ommCpuTexture* outTexture)
+{
+    const Logger& L = b->log;
+    // ---- everything that can be judged without a device (the pitch and alignment rules follow in create_texture_blocks_impl) ----
+    if (desc->mipCount != 0 && desc->mips == nullptr) return L.invalid("[Invalid Arg] - mips is not set");
+    const ommResult checked = check_texture_mips(L, desc->mipCount, (unsigned)desc->format < (unsigned)ommxBlockFormat_MAX_NUM, desc->mips, [](const ommxBlockTextureMipDesc& m) { return m.data; });
+    if (checked != ommResult_SUCCESS) return checked;
+    if (desc->channel > 1u) return L.invalid("[Invalid Arg] - channel must be 0 or 1");
+    if (desc->channel != 0u && desc->format != ommxBlockFormat_BC5) return L.invalid("[Invalid Arg] - channel must be 0 for every format but BC5");
+    const bool small = desc->format == ommxBlockFormat_BC1 || desc->format == ommxBlockFormat_BC4;
+    const uint32_t blockBytes = small ? 8u : 16u, byteOffset = 8u * desc->channel;
+    const int kind = desc->format == ommxBlockFormat_BC1 ? kBlockBC1 : desc->format == ommxBlockFormat_BC2 ? kBlockBC2 : kBlockBC4;
+    const BlockSource src{ desc->flags, desc->mips, desc->mipCount, desc->alphaCutoff, blockBytes, 8u, kind == kBlockBC4 ? ommCpuTextureFormat_FP32 : ommCpuTextureFormat_UNORM8 };
+    return create_texture_blocks_impl(b, src, fromDevice, stream, [&](const void* blocks, size_t pitch, TexMip& m, hipStream_t st) {
+        launch_block_decode(blocks, pitch, blockBytes, byteOffset, kind, m.texels, m.w, m.h, st); }, outTexture);
+}
+
+// ommxCreateTextureBC7 / ommxCreateTextureBC7Device: the alpha of BC7 blocks, decoded by bc7_kernels.hip; always a UNORM8 texture.
+ommResult create_texture_bc7_impl(Baker* b, const ommxBC7TextureDesc* desc, bool fromDevice, hipStream_t stream, ommCpuTexture* outTexture)
+{
+    const Logger& L = b->log;
+    if (desc->mipCount != 0 && desc->mips == nullptr) return L.invalid("[Invalid Arg] - mips is not set");
+    const ommResult checked = check_texture_mips(L, desc->mipCount, true, desc->mips, [](const ommxBlockTextureMipDesc& m) { return m.data; });
+    if (checked != ommResult_SUCCESS) return checked;
+    const BlockSource src{ desc->flags, desc->mips, desc->mipCount, desc->alphaCutoff, 16u, 16u, ommCpuTextureFormat_UNORM8 };
+    return create_texture_blocks_impl(b, src, fromDevice, stream, [](const void* blocks, size_t pitch, TexMip& m, hipStream_t st) {
+        launch_bc7_decode(blocks, pitch, m.texels, m.w, m.h, st); }, outTexture);
 }
 } // namespace
 
@@ -1861,23 +1892,33 @@ OMM_MI355X_API ommResult ommxCreateTextureDevice(ommBaker baker, const ommxDevic
     return guarded(&b->log, [&] { return create_texture_device_impl(b, desc, (hipStream_t)hipStream, outTexture); });
 }
 
-// A texture from the alpha of BC1..BC5 blocks (include/omm_mi355x_ext.h): the decode kernel of block_kernels.hip in front of what ommCpuCreateTexture does.
-static ommResult create_texture_bc(ommBaker baker, const ommxBlockTextureDesc* desc, bool fromDevice, void* hipStream, ommCpuTexture* outTexture)
+// A texture from the alpha of BC1..BC5 blocks, or of BC7 blocks (include/omm_mi355x_ext.h): the decode kernel of block_kernels.hip / bc7_kernels.hip in front
+// of what ommCpuCreateTexture does.  `impl` is create_texture_bc_impl or create_texture_bc7_impl.
+template <class Desc, class Impl>
+static ommResult create_texture_from_blocks(ommBaker baker, const Desc* desc, bool fromDevice, void* hipStream, ommCpuTexture* outTexture, Impl impl)
 {
     if (baker == 0) return ommResult_INVALID_ARGUMENT;
     Baker* b = untag<Baker>(baker);
     if (desc == 0) return b->log.invalid("texture desc was not set");
     if (tag_of(baker) != kCpuBaker) return b->log.invalid("Baker was not created as the right type");
     if (outTexture == nullptr) return b->log.invalid("[Invalid Arg] - outTexture is not set");
-    return guarded(&b->log, [&] { return create_texture_bc_impl(b, desc, fromDevice, (hipStream_t)hipStream, outTexture); });
+    return guarded(&b->log, [&] { return impl(b, desc, fromDevice, (hipStream_t)hipStream, outTexture); });
 }
 OMM_MI355X_API ommResult ommxCreateTextureBC(ommBaker baker, const ommxBlockTextureDesc* desc, ommCpuTexture* outTexture)
 {
-    return create_texture_bc(baker, desc, false, nullptr, outTexture);
+    return create_texture_from_blocks(baker, desc, false, nullptr, outTexture, create_texture_bc_impl);
 }
 OMM_MI355X_API ommResult ommxCreateTextureBCDevice(ommBaker baker, const ommxBlockTextureDesc* desc, void* hipStream, ommCpuTexture* outTexture)
 {
-    return create_texture_bc(baker, desc, true, hipStream, outTexture);
+    return create_texture_from_blocks(baker, desc, true, hipStream, outTexture, create_texture_bc_impl);
+}
+OMM_MI355X_API ommResult ommxCreateTextureBC7(ommBaker baker, const ommxBC7TextureDesc* desc, ommCpuTexture* outTexture)
+{
+    return create_texture_from_blocks(baker, desc, false, nullptr, outTexture, create_texture_bc7_impl);
+}
+OMM_MI355X_API ommResult ommxCreateTextureBC7Device(ommBaker baker, const ommxBC7TextureDesc* desc, void* hipStream, ommCpuTexture* outTexture)
+{
+    return create_texture_from_blocks(baker, desc, true, hipStream, outTexture, create_texture_bc7_impl);
 }
 
 OMM_MI355X_API ommResult ommCpuGetTextureDesc(ommCpuTexture texture, ommCpuTextureDesc* outDesc)
