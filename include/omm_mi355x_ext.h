@@ -282,6 +282,77 @@ OMM_MI355X_API ommResult ommxDebugGetStatsDevice(ommBaker baker, const ommCpuBak
 OMM_MI355X_API ommResult ommxGetDeviceBakeResultTriangleAreas(ommxDeviceBakeResult result, const float** deviceAreas);
 OMM_MI355X_API ommResult ommxDebugGetStatsDevice2(ommBaker baker, ommxDeviceBakeResult result, ommDebugStats* out);
 
+/* ---- geometry from a micromap: opacity-sorted triangles for hardware without an OMM unit ----
+ * ommxExtractMicroGeometry  cuts every primitive of a device-resident result into the largest sub-triangles of the bird curve whose micro-triangles
+ *                        all go to one output list, so that the known-opaque part of a mesh can go into a geometry without a filter function, the
+ *                        known-transparent part can be left out of the BVH, and only the remainder keeps the alpha test.  `deviceResult` is a HOST
+ *                        struct as for ommxLookupOpacity / ommxDebugGetStatsDevice: the desc of ommxGetDeviceBakeResultDesc, or one the caller filled
+ *                        over device copies of an ommCpuBake result.
+ *   records              a record is (primitiveIndex, node), node = level << 24 | index with level <= 12 and index < 4^level: micro-triangle `index`
+ *                        of subdivision level `level` of that primitive.  The micro-triangles 4j..4j+3 of level l + 1 tile micro-triangle j of level
+ *                        l (the bird curve is hierarchical), so node (l, j) covers the micro-triangles [j * 4^(L-l), (j+1) * 4^(L-l)) of a block of
+ *                        level L, and its vertices are ommx_micro_vertices(j, l) (include/omm_mi355x_lookup.h).
+ *   the block of primitive i   entry e = indexBuffer[i] selects its block by the rule of ommx_opacity_state.  A special index -1..-4 is ONE node
+ *                        (level 0, index 0) of state -(e + 1).  e >= 0 selects descArray[e].  A primitive is SKIPPED, and counted in
+ *                        *outSkippedPrimitives, when e < -4, e >= descArrayCount, the level is above 12, the format is not OC1_2_State (1) /
+ *                        OC1_4_State (2), or the block does not fit inside arrayDataSize: it emits nothing and nothing is read through its descriptor.
+ *                        Blocks may start at any byte offset; unused bits of a one-byte block are ignored.
+ *   classes              let the block have level L and E = min(L, maxEmitLevel).  A node (E, j) covers the micro-triangles
+ *                        [j * 4^(L-E), (j+1) * 4^(L-E)); its class is listOfState[s] when that value is the same for the state s of every covered
+ *                        micro-triangle, and mixedList otherwise.  A node (l < E, j) has class c if and only if its four children (l+1, 4j..4j+3)
+ *                        all have class c; otherwise it has no class.  OMMX_GEOMETRY_DROP is a class like any other, for merging.
+ *   emission and order   every node that has a class is emitted if its parent has none, or if it is the root, into the list its class names
+ *                        (nothing goes anywhere for OMMX_GEOMETRY_DROP).  Within a list, records are ordered by (primitiveIndex, first covered
+ *                        micro-triangle) ascending.  The outputs are a pure function of the inputs: two calls return the same bytes.
+ *   presets              listOfState = { DROP, 0, 1, 1 }: opaque triangles in list 0, alpha-tested ones in list 1, transparent ones gone.
+ *                        maxEmitLevel = 0 with mixedList = 1: the same partition on whole primitives, no new vertices.
+ *                        The "force 2-state" ray flag: map state 2 like state 0 and state 3 like state 1.
+ *   counts and capacity  outCounts[k] <- the number of records of list k, written on SUCCESS and on the capacity failure: where outputs->nodes[k] is
+ *                        not NULL and capacity[k] < outCounts[k] the call returns INSUFFICIENT_SCRATCH_MEMORY with a log line, the counts reported
+ *                        and NOT ONE BYTE of any output array written.  Expected use: call with outputs == NULL, allocate, call again.
+ *   outputs              DEVICE memory, every member optional: nodes[k] (capacity[k] records) and primitiveOffsets[k] (indexCount + 1 entries: the
+ *                        records of primitive i in list k are [off[i], off[i+1])).
+ *   stream, memory       the kernels run on `hipStream` (null = the null stream), which the call synchronises before it returns -- the counts are
+ *                        host values.  Scratch comes from the baker's device pool and is back there when the call returns.
+ *   result codes         judged before the device is touched: a null baker, deviceResult, desc or outCounts, a baker of unknown type, an unknown
+ *                        indexFormat, a listOfState[] / mixedList value that is neither 0..3 nor OMMX_GEOMETRY_DROP, non-zero reserved bytes ->
+ *                        INVALID_ARGUMENT.  indexCount == 0 -> SUCCESS with zero counts and no launch.  Null arrays with non-zero counts ->
+ *                        INVALID_ARGUMENT as in ommxDebugGetStatsDevice.  Without a usable device -> FAILURE.
+ * ommxExpandMicroNodes   records -> vertices, one grid-stride kernel enqueued on `hipStream`; allocates nothing and synchronises nothing, like
+ *                        ommxLookupOpacity.  count == 0 is SUCCESS without a launch.
+ *   outBarycentrics      [count][3][2]: ommx_micro_vertices(node & 0xFFFFFF, node >> 24) of every record -- positive orientation in (u, v), hence
+ *                        the winding of the primitive.  Callers interpolate their other attributes with these.
+ *   outPositions         [count][3][3]: for each vertex (u, v) and component c, w = (1.f - u) - v and P.c = (V0.c * w + V1.c * u) + V2.c * v in fp32,
+ *                        one rounding per operation, V0..V2 in index-buffer order.  A vertex at a corner of the primitive therefore equals that
+ *                        corner and vertices shared by nodes of ONE primitive are bit-identical.  A vertex on an edge between two primitives is
+ *                        computed from different corners on each side, and merged nodes leave T-junctions inside a primitive: the triangles are
+ *                        not watertight.
+ *   malformed records    a record whose node has a level above 12 or an index >= 4^level, or (with `mesh`) a primitiveIndex >= triangleCount, gets
+ *                        0x7FC00000 in every float it owns; the mesh is not read for it.
+ *   result codes         outPositions without mesh, an unknown mesh indexFormat, a stride below 12 or no multiple of 4, null nodes with count > 0,
+ *                        null mesh arrays where they would be read -> INVALID_ARGUMENT. */
+#define OMMX_GEOMETRY_DROP 0xFFu
+typedef struct ommxMicroNode { uint32_t primitiveIndex; uint32_t node; } ommxMicroNode;   /* node = level << 24 | index; level <= 12, index < 4^level */
+typedef struct ommxMicroGeometryDesc {
+    uint8_t  listOfState[4];   /* ommOpacityState 0..3 -> output list 0..3, or OMMX_GEOMETRY_DROP */
+    uint8_t  mixedList;        /* list (or DROP) of a node at maxEmitLevel whose micro-triangles map to different lists */
+    uint8_t  reserved[3];      /* must be 0 */
+    uint32_t maxEmitLevel;     /* no node deeper than this is emitted; >= 12: no limit */
+} ommxMicroGeometryDesc;
+typedef struct ommxMicroGeometryOutputs {     /* DEVICE memory; every member optional */
+    ommxMicroNode* nodes[4];   uint64_t capacity[4];   /* records of list k */
+    uint64_t*      primitiveOffsets[4];                /* [indexCount + 1]: records of primitive i in list k are [off[i], off[i+1]) */
+} ommxMicroGeometryOutputs;
+OMM_MI355X_API ommResult ommxExtractMicroGeometry(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxMicroGeometryDesc* desc,
+                                                  const ommxMicroGeometryOutputs* outputs /* NULL: count only */, uint64_t outCounts[4],
+                                                  uint32_t* outSkippedPrimitives /* or NULL */, void* hipStream);
+typedef struct ommxMicroMeshDesc {         /* the mesh the result was baked from, in DEVICE memory */
+    const void* positions;  uint32_t positionStrideInBytes;   /* 3 floats per vertex; stride >= 12 and a multiple of 4; 0 = 12 */
+    const void* indexBuffer; ommIndexFormat indexFormat; uint32_t triangleCount;
+} ommxMicroMeshDesc;
+OMM_MI355X_API ommResult ommxExpandMicroNodes(const ommxMicroNode* nodes, uint64_t count, const ommxMicroMeshDesc* mesh /* NULL if outPositions is */,
+                                              float* outBarycentrics /* [count][3][2] or NULL */, float* outPositions /* [count][3][3] or NULL */, void* hipStream);
+
 /* ---- an alpha texture from an image that is already in device memory ----
  * ommxCreateTextureDevice  ommCpuCreateTexture for texels that live in HBM: ONE channel of an interleaved (or packed single-channel) image is read where
  *                        it is; nothing is downloaded, restaged or uploaded.  The result is an ordinary ommCpuTexture, byte for byte the texture

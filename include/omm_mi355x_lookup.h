@@ -5,6 +5,7 @@
  * function of their own ray tracer.  This header is that consumer: include it in HIP device code (hipcc) or in plain C++ on the host.
  *
  *   ommx_micro_index(u, v, level)          hit barycentrics -> micro-triangle index on the bird curve, 0 <= index < 4^level
+ *   ommx_micro_vertices(index, level, uv)  the way back: the three barycentric vertices of a micro-triangle (or of a merged node)
  *   ommx_opacity_state(result, prim, u, v) the 4-state value (ommOpacityState, 0..3) the result stores there, or OMMX_OPACITY_INVALID
  *   ommx_force_2state(state)               the "force OMM 2-state" ray flag: UnknownTransparent -> Transparent, UnknownOpaque -> Opaque
  *
@@ -81,6 +82,50 @@ OMMX_LOOKUP_FN uint32_t ommx_micro_index(float u, float v, uint32_t level)
         y ^= digit == 1u ? 1u : 0u;
     }
     return index;
+}
+
+/* helpers of the forward decode: bits 0, 2, 4, ... of x gathered into the low half ... */
+OMMX_LOOKUP_FN uint32_t ommx_even_bits(uint32_t x)
+{
+    x &= 0x55555555u;
+    x = (x | (x >> 1)) & 0x33333333u; x = (x | (x >> 2)) & 0x0f0f0f0fu;
+    x = (x | (x >> 4)) & 0x00ff00ffu; x = (x | (x >> 8)) & 0x0000ffffu;
+    return x;
+}
+/* ... and bit i of the result = the xor of the bits >= i of x */
+OMMX_LOOKUP_FN uint32_t ommx_prefix_xor(uint32_t x)
+{
+    x ^= x >> 1; x ^= x >> 2; x ^= x >> 4; x ^= x >> 8; x ^= x >> 16;
+    return x;
+}
+
+/* The three vertices of micro-triangle `index` at `level` as DXR / Vulkan barycentrics, uv = u0 v0 u1 v1 u2 v2: the bird curve's forward
+ * decode (omm_amd/csrc/classify_device.h, micro_triangle), the inverse of ommx_micro_index.
+ *  - vertex order is the decode's: (u, v), (u + d, v), (u, v + d) with d = +2^-level for an upright micro-triangle and -2^-level for an
+ *    inverted one.  In that order EVERY micro-triangle, upright or inverted, has positive orientation in (u, v) -- the cross product of
+ *    its two edges from vertex 0 is d * d > 0 -- so mapped through (1-u-v) * V0 + u * V1 + v * V2 it has the winding of the triangle it
+ *    came from;
+ *  - every coordinate is k * 2^-level with 0 <= k <= 2^level: exact in fp32;
+ *  - the micro-triangles 4j .. 4j+3 of level N + 1 tile micro-triangle j of level N, so the same function is the vertex rule of a merged
+ *    node of ommxExtractMicroGeometry: node (level l, index j) is ommx_micro_vertices(j, l);
+ *  - levels above 12 are treated as 12 and an index >= 4^level is reduced modulo 4^level, as in ommx_micro_index. */
+OMMX_LOOKUP_FN void ommx_micro_vertices(uint32_t index, uint32_t level, float uv[6])
+{
+    if (level > OMMX_LOOKUP_MAX_LEVEL) level = OMMX_LOOKUP_MAX_LEVEL;
+    if (level == 0u) { uv[0] = 0.f; uv[1] = 0.f; uv[2] = 1.f; uv[3] = 0.f; uv[4] = 0.f; uv[5] = 1.f; return; }
+    index &= (1u << (2u * level)) - 1u;
+    const uint32_t b0 = ommx_even_bits(index), b1 = ommx_even_bits(index >> 1);
+    const uint32_t fx = ommx_prefix_xor(b0), fy = ommx_prefix_xor(b0 & ~b1);
+    const uint32_t t = fy ^ b1, mask = (1u << level) - 1u;
+    uint32_t iu = ((fx & ~t) | (b0 & ~t) | (~b0 & ~fx & t)) & mask;
+    uint32_t iv = (fy ^ b0) & mask;
+    const uint32_t iw = ((~fx & ~t) | (b0 & ~t) | (~b0 & fx & t)) & mask;
+    const bool upright = ((iu ^ iv ^ iw) & 1u) != 0u;
+    if (!upright) { iu += 1u; iv += 1u; }
+    const float s = 1.f / (float)(1u << level);   /* a power of two: every product and sum below is exact */
+    const float d = upright ? s : -s;
+    const float u = (float)iu * s, v = (float)iv * s;
+    uv[0] = u; uv[1] = v; uv[2] = u + d; uv[3] = v; uv[4] = u; uv[5] = v + d;
 }
 
 /* The state the result stores for triangle `prim` at the hit (u, v): 0..3 (ommOpacityState) or OMMX_OPACITY_INVALID.

@@ -12,6 +12,8 @@
 #include "host_expand.h"
 #include "lookup_kernels.h"
 #include "stats_kernels.h"
+#include "geometry_kernels.h"
+#include "geometry_cut.h"
 #include "texture_kernels.h"
 #include "block_kernels.h"
 #include "bc7_kernels.h"
@@ -2923,6 +2925,70 @@ OMM_MI355X_API ommResult ommxDebugGetStatsDevice2(ommBaker baker, ommxDeviceBake
     if (result == 0) return ommResult_INVALID_ARGUMENT;
     const DeviceBakeResult* r = (const DeviceBakeResult*)result;
     return ommxDebugGetStatsDevice(baker, &r->desc, r->R.triArea, nullptr, out, nullptr, nullptr);
+}
+
+// Opacity-sorted nodes of the bird curve from a result whose arrays are device memory (include/omm_mi355x_ext.h; kernels in geometry_kernels.hip): count,
+// judge the caller's capacities on the host, then write -- so that a call that fails for capacity has written nothing.
+namespace {
+ommResult extract_geometry(Baker& b, const ommCpuBakeResultDesc& r, const ommxMicroGeometryDesc& g, const ommxMicroGeometryOutputs* outputs, uint64_t outCounts[4],
+                           uint32_t* outSkipped, hipStream_t stream)
+{
+    if (r.indexFormat != ommIndexFormat_UINT_8 && r.indexFormat != ommIndexFormat_UINT_16 && r.indexFormat != ommIndexFormat_UINT_32)
+        return b.log.invalid("[Invalid Arg] - deviceResult.indexFormat is not an index format");
+    GeoArgs a; memset(&a, 0, sizeof a);
+    for (int s = 0; s < 5; ++s) {
+        const uint8_t v = s < 4 ? g.listOfState[s] : g.mixedList;
+        if (v > 3 && v != OMMX_GEOMETRY_DROP) return b.log.invalid(s < 4 ? "[Invalid Arg] - listOfState must name a list 0..3 or OMMX_GEOMETRY_DROP" : "[Invalid Arg] - mixedList must name a list 0..3 or OMMX_GEOMETRY_DROP");
+        (s < 4 ? a.cls[s] : a.mixed) = v == OMMX_GEOMETRY_DROP ? (uint8_t)kGeoDrop : v;
+    }
+    if (g.reserved[0] || g.reserved[1] || g.reserved[2]) return b.log.invalid("[Invalid Arg] - ommxMicroGeometryDesc.reserved must be 0");
+    a.result = r; a.emitLevel = g.maxEmitLevel < kGeoMaxLevel ? g.maxEmitLevel : kGeoMaxLevel;
+    for (int k = 0; k < 4; ++k) outCounts[k] = 0;
+    if (outSkipped) *outSkipped = 0;
+    if (r.indexCount == 0) return ommResult_SUCCESS;   // nothing to launch
+    if (r.indexBuffer == nullptr || (r.descArrayCount && (r.descArray == nullptr || (r.arrayData == nullptr && r.arrayDataSize))))
+        return b.log.invalid("[Invalid Arg] - deviceResult has a null array with a non-zero count");
+    int deviceCount = 0;
+    if (!HIP_OK(hipGetDeviceCount(&deviceCount)) || deviceCount < 1) { (void)hipGetLastError(); return b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)"); }
+    const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
+    struct PoolBlock { DevPool* pool; void* p; ~PoolBlock() { if (p) pool->release(p); } };
+    PoolBlock head{ b.devPool.get(), b.devPool->acquire(geo_head_bytes(a)) }, tiles{ b.devPool.get(), nullptr };
+    if (!head.p) return b.log.failure("[Failure] - out of device memory for the geometry scratch");
+    // (after a failed launch the scratch goes back only when nothing can still touch it)
+    const auto failed = [&] { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); return b.log.failure("[Failure] - the geometry kernels could not run"); };
+    unsigned long long tileCount = 0;
+    if (geo_count_tiles(a, head.p, &tileCount, stream) != hipSuccess) return failed();
+    if (tileCount) {
+        tiles.p = b.devPool->acquire(geo_tile_bytes(tileCount));
+        if (!tiles.p) return b.log.failure("[Failure] - out of device memory for the geometry scratch");
+    }
+    bool wantNodes = false, wantAny = false;
+    if (outputs) for (int k = 0; k < 4; ++k) { wantNodes = wantNodes || outputs->nodes[k]; wantAny = wantAny || outputs->nodes[k] || outputs->primitiveOffsets[k]; }
+    GeoTotals t;
+    if (geo_count(a, head.p, tiles.p, tileCount, wantNodes, &t, stream) != hipSuccess) return failed();
+    for (int k = 0; k < 4; ++k) outCounts[k] = t.counts[k];
+    if (outSkipped) *outSkipped = t.skipped;
+    if (!wantAny) return ommResult_SUCCESS;
+    for (int k = 0; k < 4; ++k)
+        if (outputs->nodes[k] && outputs->capacity[k] < t.counts[k]) {
+            b.log.msg(ommMessageSeverity_Fatal, "[Failure] - ommxMicroGeometryOutputs.capacity is smaller than the list's record count (see outCounts); nothing was written");
+            return ommResult_INSUFFICIENT_SCRATCH_MEMORY;
+        }
+    if (geo_emit(a, head.p, tiles.p, tileCount, t, *outputs, stream) != hipSuccess) return failed();
+    return ommResult_SUCCESS;
+}
+}
+
+OMM_MI355X_API ommResult ommxExtractMicroGeometry(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxMicroGeometryDesc* desc,
+                                                  const ommxMicroGeometryOutputs* outputs, uint64_t outCounts[4], uint32_t* outSkippedPrimitives, void* hipStream)
+{
+    if (baker == 0) return ommResult_INVALID_ARGUMENT;
+    if (tag_of(baker) != kCpuBaker && tag_of(baker) != kGpuBaker) return ommResult_INVALID_ARGUMENT;
+    Baker* b = untag<Baker>(baker);
+    if (deviceResult == nullptr) return b->log.invalid("[Invalid Arg] - deviceResult was not set");
+    if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxMicroGeometryDesc was not set");
+    if (outCounts == nullptr) return b->log.invalid("[Invalid Arg] - outCounts was not set");
+    return guarded(&b->log, [&] { return extract_geometry(*b, *deviceResult, *desc, outputs, outCounts, outSkippedPrimitives, (hipStream_t)hipStream); });
 }
 
 // Any-hit resolution of hits against a device-resident result (include/omm_mi355x_ext.h; kernels in lookup_kernels.hip).  The desc is checked as

@@ -9,6 +9,7 @@
 #include <rocprim/rocprim.hpp>
 #include "stats_kernels.h"
 #include "stats_count.h"
+#include "wave_search.h"
 
 namespace ommx {
 
@@ -80,24 +81,6 @@ __global__ __launch_bounds__(kStatsBlock) void stats_prepare(ommCpuBakeResultDes
     for (int s = 0; s < 4; ++s) stateCounts[4ull * d + s] = c[s];   // (a caller's array is only 4-byte aligned)
     refs[d] = 0u;
     segments[d] = segs;
-}
-
-// The descriptor that owns segment `seg`: the last d with segStart[d] <= seg (segStart: exclusive scan of the segment counts, segStart[0] = 0, so
-// descriptors without segments are passed over).  Every lane of the wave gets it.  The 64 lanes probe 64 evenly spaced entries at a time: three
-// dependent loads for 2^18 descriptors where a binary search has eighteen.
-__device__ __forceinline__ uint32_t owner_of_segment(const unsigned long long* __restrict__ segStart, uint32_t count, unsigned long long seg)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t lo = 0u, n = count;
-    while (n > 1u) {
-        const uint32_t step = (n + 63u) >> 6;
-        const uint64_t at = (uint64_t)lane * step;
-        const bool le = at < n && segStart[lo + at] <= seg;   // a prefix of the lanes (lane 0 always)
-        const uint32_t k = (uint32_t)__popcll(__ballot(le)) - 1u;
-        lo += k * step;
-        n = n - k * step < step ? n - k * step : step;
-    }
-    return lo;
 }
 
 // One 16 KiB segment of one block per workgroup and turn: 64 bytes per lane as four 16-byte reads, popcounts on the words, the four counts
