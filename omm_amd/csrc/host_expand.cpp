@@ -200,6 +200,26 @@ HostCodecLayout host_codec_layout(uint64_t paddedBytes)
     return c;
 }
 
+CodecSlicePlan plan_codec_slices(const HostCodecLayout& L, const uint32_t* ofs, uint64_t streamBytes)
+{
+    CodecSlicePlan P; P.ok = true;
+    for (uint32_t k = 0; k <= CodecSlicePlan::kSlices; ++k) P.blockCut[k] = L.blocks * k / CodecSlicePlan::kSlices;
+    for (uint32_t k = 0; k < CodecSlicePlan::kSlices; ++k) {
+        const uint64_t b0 = P.blockCut[k], b1 = P.blockCut[k + 1];
+        CodecSlicePlan::Slice& s = P.slice[k];
+        s.c0 = L.offCodes + b0 * 128u; s.c1 = b1 == L.blocks ? L.offRaw : L.offCodes + b1 * 128u;
+        s.r0 = L.offRaw + 16ull * ofs[b0]; s.r1 = L.offRaw + 16ull * ofs[b1];
+        P.ok = P.ok && s.r0 <= s.r1 && s.r1 <= streamBytes;
+    }
+    return P;
+}
+uint32_t last_slice_needed(const CodecSlicePlan& plan, uint64_t s1)
+{
+    uint32_t need = 0;
+    while (need + 1u < CodecSlicePlan::kSlices && plan.blockCut[need + 1u] < s1) ++need;
+    return need;
+}
+
 namespace {
 const uint32_t kPattern[4] = { 0u, 0x55555555u, 0xAAAAAAAAu, 0xFFFFFFFFu };
 // a 4 KiB block of one repeated state (96 % of the blocks of a bake): non-temporal stores as wide as the CPU has them (the destination is 16-byte aligned;

@@ -11,6 +11,7 @@
 #include <mutex>
 #include <thread>
 #include <vector>
+#include "bake_host.h"   // pad256, CarveCursor
 
 namespace ommx {
 
@@ -59,7 +60,41 @@ private:
 struct HostCodecLayout { uint64_t units, blocks, offOfs, offCodes, offRaw; };
 HostCodecLayout host_codec_layout(uint64_t paddedBytes);
 
-// Zeroing ahead (omm_host.cpp: Prefill): while the device bakes, helper threads zero an idle result block of `cap` bytes in pieces of 2 MiB, up to the size of
+// ---- the compressed transfer's integer rules (omm_host.cpp: CodecBlock, deliver_compressed; tests/native/result_delivery_check.cpp) ----
+// a stream that does not shrink below half of the (padded) array is not sent: the array takes the plain copy
+inline uint64_t codec_stream_cap(const HostCodecLayout& L, uint64_t paddedBytes) { return L.offRaw + paddedBytes / 2u + 16u; }
+// The device block that holds the codec stream of `arrayBytes` of arrayData: size word (256 B) | scan scratch | [unit codes | block raw counts] | the stream.
+// Like carve_bake_tables (bake_host.h): from base 0 `bytes` is what to reserve, from the block's base the pointers are the slots.  The stream slot has
+// codec_stream_cap() bytes and ends the block; `withCodes`: a byte per 16-byte unit and a word per codec block (+ 1) for the gather to fill.
+struct CodecBlockCarve { uint32_t* sizeWord; uint8_t *scratch, *unitCodes; uint32_t* blockRawCounts; uint8_t* stream; size_t bytes; };
+inline CodecBlockCarve carve_codec_block(uintptr_t base, uint64_t arrayBytes, size_t scratchBytes, bool withCodes)
+{
+    const uint64_t padded = (arrayBytes + 255u) & ~255ull; const HostCodecLayout L = host_codec_layout(padded);
+    CodecBlockCarve b = CodecBlockCarve(); CarveCursor c{ base };
+    b.sizeWord = c.take<uint32_t>(1); b.scratch = c.take<uint8_t>(scratchBytes);
+    if (withCodes) { b.unitCodes = c.take<uint8_t>((size_t)(padded / 16u)); b.blockRawCounts = c.take<uint32_t>((size_t)L.blocks + 1); }
+    b.stream = c.take<uint8_t>(0);
+    b.bytes = (size_t)(c.at - base) + (size_t)codec_stream_cap(L, padded);
+    return b;
+}
+// The stream crosses the link in kSlices pieces, each the codes of a range of codec blocks and the raw units those blocks point at (both contiguous: `ofs`,
+// the stream's table of blocks + 1 first-raw-unit indices, is a prefix sum).  Slice k: blocks [blockCut[k], blockCut[k + 1]), stream bytes [c0, c1) and
+// [r0, r1); the last slice's codes end at offRaw (the padding of the code section travels with it).  Empty slices are legal.  `ok` is false when a
+// table entry AT A CUT decreases or points beyond streamBytes -- a corrupt table must not turn into a wild copy; entries inside a slice are never read here.
+struct CodecSlicePlan {
+    static constexpr uint32_t kSlices = 12;
+    struct Slice { uint64_t c0, c1, r0, r1; };
+    uint64_t blockCut[kSlices + 1]; Slice slice[kSlices]; bool ok;
+};
+CodecSlicePlan plan_codec_slices(const HostCodecLayout& L, const uint32_t* ofs, uint64_t streamBytes);
+// The expansion runs as tasks of kTaskBlocks codec blocks (2 MiB of the array) in block order: task t expands blocks [t kTaskBlocks, s1), s1 cut at L.blocks
+constexpr uint64_t kTaskBlocks = 512;
+inline uint64_t codec_task_count(const HostCodecLayout& L) { return (L.blocks + kTaskBlocks - 1) / kTaskBlocks; }
+inline void codec_task_range(const HostCodecLayout& L, uint64_t t, uint64_t* s0, uint64_t* s1) { *s0 = t * kTaskBlocks; *s1 = *s0 + kTaskBlocks < L.blocks ? *s0 + kTaskBlocks : L.blocks; }
+// the last slice a task that ends at block s1 reads from: it may start once slices 0 .. that one are on the host
+uint32_t last_slice_needed(const CodecSlicePlan& plan, uint64_t s1);
+
+// Zeroing ahead (omm_host.cpp: ResultArray): while the device bakes, helper threads zero an idle result block of `cap` bytes in pieces of 2 MiB, up to the size of
 // the last compressed result (`last`).  The block may then hold a LARGER result (up to `cap`): the last piece ends at `bytes`, not at its 2 MiB boundary, and
 // what lies beyond `bytes` is whatever the block held before.
 constexpr unsigned kZeroPieceShift = 21;   // 2 MiB pieces

@@ -218,6 +218,20 @@ struct DevPool {
         for (void* p : drop) (void)hipFree(p);
     }
 };
+// One block of a DevPool.  Owns it from acquire() until release() or the destructor hands it back: declare it BEFORE the StreamDrain of the stream
+// that uses it (destructors run in reverse), so that it goes back only when the device is done with it.
+struct PoolBlock {
+    DevPool* pool = nullptr; void* p = nullptr;
+    PoolBlock() = default;
+    PoolBlock(DevPool* from, size_t bytes) { (void)acquire(from, bytes); }
+    PoolBlock(const PoolBlock&) = delete; PoolBlock& operator=(const PoolBlock&) = delete;
+    ~PoolBlock() { release(); }
+    bool acquire(DevPool* from, size_t bytes) { release(); pool = from; p = from->acquire(bytes); return p != nullptr; }
+    void release() { if (p) pool->release(p); p = nullptr; }
+    uint8_t* bytes() const { return (uint8_t*)p; }
+};
+// waits for a stream when the scope is left, whichever way: declared right BEHIND the memory that asynchronous copies on the stream read or write
+struct StreamDrain { hipStream_t s; ~StreamDrain() { (void)hipStreamSynchronize(s); } };
 
 // ---- warm, pinned host memory for the (large) result array -------------------------------------------------
 // A fresh 1.3 GB malloc costs more in page faults (70-100 ms) and munmap (95 ms) than the PCIe copy itself (24 ms at 57 GB/s), so
@@ -432,7 +446,7 @@ struct BakeResult {
     ~BakeResult() { if (pool) pool->release(arrayData); else mem.release(arrayData); mem.release(descs); mem.release(arrayHist); mem.release(indexHist); mem.release(index); mem.release(triArea); }
 };
 // Whatever a host BakeResult still lacks of its arrays: arrayData and descriptors of E OMMs, index buffer, triangle areas, the two histogram lists.
-// (ommCpuBake's main path arrives with all but the histograms: ArrayAlloc places its array, the others are allocated ahead of the copies that fill them.)
+// (ommCpuBake's main path arrives with all but the histograms: ResultArray places its array, the others are allocated ahead of the copies that fill them.)
 ommResult alloc_host_result(Baker& baker, BakeResult* res, uint32_t E, size_t arrayBytes, uint32_t T)
 {
     const Allocator& mem = baker.mem;
@@ -811,7 +825,7 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
             return L.failure("[Failure] - device work-item setup failed");
         if (hc.numPending) {
             std::vector<uint32_t> pend(hc.numPending); std::vector<float> puv((size_t)hc.numPending * 6); std::vector<uint8_t> plv(hc.numPending);
-            struct PoolBlock { DevPool* pool; void* p; ~PoolBlock() { if (p) pool->release(p); } } tmp{ baker.devPool.get(), baker.devPool->acquire((size_t)hc.numPending * 24 + 256) };
+            const PoolBlock tmp(baker.devPool.get(), (size_t)hc.numPending * 24 + 256);
             if (!tmp.p) return L.failure("[Failure] - device work-item setup failed");
             if (!HIP_OK(copy_pending_to_host(tab.scratch, tab.scratchBytes, T, hc.numPending, pend.data(), puv.data(), tmp.p, stream))) return L.failure("[Failure] - device work-item setup failed");
             {   // (tiny triangles under dynamic subdivision are degenerate by the tens of thousands -- configs[4]: 1.5 ms of log2f on one thread; four share it)
@@ -1285,18 +1299,276 @@ CodecBlockLayout codec_block_layout(uint64_t arrayBytes)
 {
     CodecBlockLayout B;
     B.padded = (arrayBytes + 255u) & ~255ull; B.L = host_codec_layout(B.padded);
-    B.cap = B.L.offRaw + B.padded / 2u + 16u;   // a stream that does not shrink below half takes the plain copy
+    B.cap = codec_stream_cap(B.L, B.padded);
     B.scratchBytes = pad256(shard_codec_scratch_bytes(B.padded));
     B.fits = B.L.blocks < 0x7FFFFFFFull;
     return B;
 }
 constexpr uint64_t kCompressedMinBytes = 32ull << 20;   // smaller arrays cross the link as they are (0.6 ms at 57 GB/s)
-// ommCpuBake: host arrays in, host arrays out
+
+// ---- result delivery of ommCpuBake (and of the multi-device bake made of the same parts): one owner per resource ----
+// The device block of ONE codec stream (slots: carve_codec_block, host_expand.h): ommCpuBake's compressed result, a rank's contribution of the multi-device bake.
+// Owns the pool block from reserve() until it is destroyed -- declared BEFORE the StreamDrain of the stream that compresses into it.
+struct CodecBlock : CodecBlockLayout {
+    PoolBlock block; CodecBlockCarve at = CodecBlockCarve(); uint64_t arrayBytes = 0;
+    bool on = false;   // (ommCpuBake: the stream of the finished array has been queued)
+    bool reserved() const { return block.p != nullptr; }
+    bool has_codes() const { return at.unitCodes != nullptr; }   // the gather fills (has filled) the codes of the units and the raw counts of the blocks
+    bool reserve(DevPool* pool, uint64_t bytes, bool withCodes) {
+        static_cast<CodecBlockLayout&>(*this) = codec_block_layout(bytes); arrayBytes = bytes;
+        if (!block.acquire(pool, carve_codec_block(0, bytes, scratchBytes, withCodes).bytes) || !fits) return false;
+        at = carve_codec_block((uintptr_t)block.p, bytes, scratchBytes, withCodes);
+        return true;
+    }
+    // in front of the gather that fills them: the units of the padding behind the array count as zeros, the counts start at zero
+    bool prepare_codes(hipStream_t stream) {
+        const uint64_t units = arrayBytes / 16u, paddedUnits = padded / 16u;
+        bool ok = HIP_OK(hipMemsetAsync(at.blockRawCounts, 0, ((size_t)L.blocks + 1) * 4, stream));
+        if (ok && paddedUnits > units) ok = HIP_OK(hipMemsetAsync(at.unitCodes + units, 0, (size_t)(paddedUnits - units), stream));
+        if (!ok) { at.unitCodes = nullptr; at.blockRawCounts = nullptr; }
+        return ok;
+    }
+    // the codec stream of dArray[0 .. padded) into at.stream (with the gather's codes the array is read for its raw units only)
+    bool compress(const uint8_t* dArray, hipStream_t stream) const {
+        return HIP_OK(has_codes() ? run_shard_compress_coded(dArray, padded, at.unitCodes, at.blockRawCounts, at.stream, cap, at.sizeWord, at.scratch, scratchBytes, stream)
+                                  : run_shard_compress(dArray, padded, at.stream, cap, at.sizeWord, at.scratch, scratchBytes, stream));
+    }
+};
+// A host BakeResult until release() hands it to the caller.  Let go of earlier -- an error, an exception -- it is destroyed only after the session's streams are
+// idle (the comm stream, which may have been opened after the guard was made, then the bake's): nothing may still be copying into the result's arrays when they
+// are freed.  Without a session (the multi-device bake) the caller's own StreamDrain stands behind the guard.
+struct HostResultGuard {
+    Baker& b; BakeResult* r; const BakeSession* drain;
+    ~HostResultGuard() {
+        if (!r) return;
+        if (drain) { if (drain->commStream) (void)hipStreamSynchronize(drain->commStream); (void)hipStreamSynchronize(drain->stream); }
+        b.mem.destroy(r);
+    }
+    BakeResult* release() { BakeResult* p = r; r = nullptr; return p; }
+};
+// HIP events without timing, destroyed with the scope: declared in the scope that holds the last wait on them
+struct GpuEvents {
+    hipEvent_t ev[CodecSlicePlan::kSlices]; uint32_t n = 0;
+    bool create(uint32_t count) { while (n < count && n < CodecSlicePlan::kSlices && HIP_OK(hipEventCreateWithFlags(&ev[n], hipEventDisableTiming))) ++n; return n == count; }
+    ~GpuEvents() { for (uint32_t k = 0; k < n; ++k) (void)hipEventDestroy(ev[k]); }
+};
+struct ActiveBake { std::atomic<uint32_t>& n; explicit ActiveBake(std::atomic<uint32_t>& c) : n(c) { n.fetch_add(1); } ~ActiveBake() { n.fetch_sub(1); } };   // Baker::activeBakes
+
+// The host arrayData of an ommCpuBake result, and the block that is zeroed ahead for it.
+// Zeroing ahead (round 6, compressed transfer).  The expansion of the result is bound by what twelve threads can store (1.27 GB in 3.6 ms), and a quarter of
+// the metric configuration's 4-KiB codec blocks repeat state 0 = zeros.  While the device bakes the host is idle: the baker's helper threads zero an IDLE block
+// of the result pool (what the previous bake left; never a fresh allocation, never a user allocator's memory) in pieces of 2 MiB, up to the size of the last
+// compressed result; if the block then fits this bake's result it becomes the result, and the expansion leaves zero blocks of complete pieces alone.
+// Owns that block and the helper threads' run on it: the threads are stopped before anybody else writes the block and before it is released, and the block
+// is either made the result's array by get() or goes back to the pool (get(), the destructor) -- whatever happens: another transfer, a larger result, an error.
+// The array that get() has placed belongs to the BakeResult: freed with it, on an error path by the HostResultGuard this object is declared BEHIND (after the
+// streams are drained -- it is never freed while a copy can land in it).
+struct ResultArray {
+    Baker& b; BakeResult* res;
+    uint64_t cap = 0; bool pinned = false;   // of res->arrayData
+    bool fromPrefill = false;                // res->arrayData is the block zeroed ahead, and nothing but the zeroing has written into it
+    std::shared_ptr<WorkerPool> workers; std::shared_ptr<HostPool> host; uint8_t* block = nullptr; size_t blockCap = 0; bool blockPinned = false, started = false;
+    ZeroPlan plan{ 0, 0, 0 };   // (host_expand.h: the pieces, and the extent the expansion may trust -- a larger result's bytes beyond it are stale)
+    std::unique_ptr<std::atomic<uint8_t>[]> done; std::atomic<bool> cancel{ false };
+    ResultArray(Baker& baker, BakeResult* r) : b(baker), res(r) {}
+    ~ResultArray() { stop(); if (block) host->release(block); }
+    void stop() { if (started) { cancel.store(true); workers->wait(); started = false; } }   // (pieces not begun stay unmarked: the expansion writes them like any other)
+    // takes an idle pool block of the last compressed result's size, if there is one, and starts zeroing it
+    void zero_ahead(unsigned expandThreads) {
+        const uint64_t last = b.lastCompressedArrayBytes.load();
+        if (last < kCompressedMinBytes || (block = (uint8_t*)b.hostPool->acquire_idle((size_t)last, &blockCap, &blockPinned)) == nullptr) return;
+        host = b.hostPool; workers = b.worker_pool(expandThreads);
+        plan = zero_plan(blockCap, (size_t)last);
+        done.reset(new (std::nothrow) std::atomic<uint8_t>[plan.pieces]);
+        if (!done || ((uintptr_t)block & 4095u) != 0u) return;
+        for (size_t j = 0; j < plan.pieces; ++j) done[j].store(0);
+        if (b.knob(ommxBakerKnob_HelperAffinity) == 0) (void)workers->bind_near(block);
+        started = workers->start((uint32_t)plan.pieces, [this](uint32_t j) {
+            if (cancel.load(std::memory_order_relaxed)) return;
+            size_t lo, hi; zero_piece_range(plan, j, &lo, &hi);
+            fill_zero_nt(block, lo, hi);
+            done[j].store(1, std::memory_order_release);
+        });
+    }
+    // res->arrayData with room for `bytes`, from: the array it has if that is large enough | the block zeroed ahead | the baker's host pool | the allocator
+    uint8_t* get(uint64_t bytes, bool* outPinned) {
+        if (outPinned) *outPinned = false;
+        if (res->arrayData && cap >= bytes) { if (outPinned) *outPinned = pinned; return (uint8_t*)res->arrayData; }
+        if (!res->arrayData && block) {   // the block that was zeroed ahead, if it holds this result (its threads have stopped before anybody writes into it)
+            stop();
+            if (blockCap >= bytes) {
+                res->arrayData = block; res->pool = host; pinned = blockPinned; cap = bytes; fromPrefill = true; block = nullptr;
+                if (outPinned) *outPinned = pinned;
+                return (uint8_t*)res->arrayData;
+            }
+            host->release(block); block = nullptr;
+        }
+        if (res->arrayData) { if (res->pool) { res->pool->release(res->arrayData); res->pool.reset(); } else b.mem.release(res->arrayData); res->arrayData = nullptr; cap = 0; }
+        // (small results are pooled -- pinned -- only while this is the baker's one bake in flight: sixteen callers copying into pinned blocks at once take
+        //  turns on the copy engines -- measured on configs[1]: 2 278 -> 1 190 bakes/s at 16 threads --, while one caller gains 0.28 ms per bake)
+        if (b.mem.alloc == default_alloc && ((size_t)bytes >= HostPool::kMinBytes || (b.activeBakes.load() <= 1u && b.hostPool->wants((size_t)bytes)))) {
+            res->arrayData = b.hostPool->acquire((size_t)bytes, &pinned);
+            if (res->arrayData) res->pool = b.hostPool;
+        }
+        if (!res->arrayData) { res->arrayData = b.mem.allocate((size_t)bytes, 64); pinned = false; }
+        cap = res->arrayData ? bytes : 0;
+        if (outPinned) *outPinned = pinned;
+        return (uint8_t*)res->arrayData;
+    }
+    // StreamOut::alloc: a block the streamed placement writes into is no longer only zeroed -- if the stream is discarded, the compressed transfer that follows
+    // must write every byte
+    static uint8_t* get_for_stream(void* self, uint64_t bytes, bool* outPinned) { ResultArray& a = *(ResultArray*)self; uint8_t* p = a.get(bytes, outPinned); a.fromPrefill = false; return p; }
+    ZeroedPieces zeroed() const { return zeroed_pieces(plan, done.get()); }
+    bool trust_zeroed() const { return fromPrefill && done; }   // the expansion may leave zeros inside zeroed() alone
+};
+
+// the caller's raw triangle data into its device block (raw_input_layout, bake_host.h); a null stream: blocking copies.  All null: no block / a copy failed
+DeviceInputs upload_raw_inputs(const RawInputLayout& raw, const ommCpuBakeInputDesc& d, uint8_t* dRaw, hipStream_t stream)
+{
+    const auto put = [&](size_t at, const void* src, size_t bytes) {
+        return !bytes || HIP_OK(stream ? hipMemcpyAsync(dRaw + at, src, bytes, hipMemcpyHostToDevice, stream) : hipMemcpy(dRaw + at, src, bytes, hipMemcpyHostToDevice));
+    };
+    if (!dRaw || !put(raw.offUv, d.texCoords, raw.uvBytes) || !put(raw.offIdx, d.indexBuffer, raw.idxBytes) || !put(raw.offLvl, d.subdivisionLevels, raw.lvlBytes))
+        return DeviceInputs{ nullptr, nullptr, nullptr };
+    return DeviceInputs{ dRaw + raw.offUv, dRaw + raw.offIdx, raw.lvlBytes ? dRaw + raw.offLvl : nullptr };
+}
+// descriptors, index buffer and triangle areas of a device result into the host result's arrays (8.6 MB at the metric configuration, into the caller's pageable
+// arrays: each copy holds its thread until it is done)
+bool copy_small_arrays(BakeResult* res, const ommCpuOpacityMicromapDesc* descs, const void* index, const float* triArea, uint32_t E, uint32_t T, size_t indexBytes, hipStream_t s)
+{
+    bool k = true;
+    if (E) k = HIP_OK(hipMemcpyAsync(res->descs, descs, sizeof(ommCpuOpacityMicromapDesc) * (size_t)E, hipMemcpyDeviceToHost, s));
+    if (k && T) k = HIP_OK(hipMemcpyAsync(res->index, index, indexBytes * T, hipMemcpyDeviceToHost, s));
+    if (k && T) k = HIP_OK(hipMemcpyAsync(res->triArea, triArea, sizeof(float) * (size_t)T, hipMemcpyDeviceToHost, s));
+    return k;
+}
+// With a compressed result the small arrays cross the link on the second stream WHILE the helper threads expand the array: that stream waits for the device
+// result (an event behind everything on the bake's stream).  False: no second stream / no event -- the small arrays go in front of the wait, on the bake's stream.
+bool defer_small_arrays(BakeSession& ses, GpuEvents& resultEvent)
+{
+    if (!ses.open_comm() || !resultEvent.create(1)) return false;
+    return HIP_OK(hipEventRecord(resultEvent.ev[0], ses.stream)) && HIP_OK(hipStreamWaitEvent(ses.commStream, resultEvent.ev[0], 0));
+}
+// result of the serial host tail -> host result (ommCpuBake with the opt-in lossy reducers): the host twin of upload_host_tail; the triangle areas come from the device
+ommResult host_result_from_tail(Baker& baker, const BakeSession& ses, const HostTailResult& hres, ommIndexFormat ifmt, uint32_t T, const float* dTriArea, BakeResult** out)
+{
+    HostResultGuard guard{ baker, baker.mem.make<BakeResult>(), &ses };
+    BakeResult* const res = guard.r;
+    if (!res) return ommResult_FAILURE;
+    res->mem = baker.mem;
+    const uint32_t E = (uint32_t)hres.descs.size();
+    if (alloc_host_result(baker, res, E, hres.arrayData.size(), T) != ommResult_SUCCESS) return ommResult_FAILURE;
+    if (T && (!HIP_OK(hipMemcpyAsync(res->triArea, dTriArea, sizeof(float) * (size_t)T, hipMemcpyDeviceToHost, ses.stream)) || !HIP_OK(hipStreamSynchronize(ses.stream))))
+        return baker.log.failure("[Failure] - device to host transfer of the bake result failed");
+    if (E) { memcpy(res->arrayData, hres.arrayData.data(), hres.arrayData.size()); memcpy(res->descs, hres.descs.data(), sizeof(ommCpuOpacityMicromapDesc) * (size_t)E); }
+    memcpy(res->index, hres.index.data(), sizeof(int32_t) * (size_t)T);
+    memcpy(res->arrayHist, hres.arrayHist.data(), sizeof(ommCpuOpacityMicromapUsageCount) * clamp_hist_count(hres.arrayHist.size()));
+    memcpy(res->indexHist, hres.indexHist.data(), sizeof(ommCpuOpacityMicromapUsageCount) * clamp_hist_count(hres.indexHist.size()));
+    fill_result_desc(&res->desc, res->arrayData, hres.arrayData.size(), res->descs, E, res->index, T, ifmt, res->arrayHist, hres.arrayHist.size(), res->indexHist, hres.indexHist.size());
+    *out = guard.release();
+    return ommResult_SUCCESS;
+}
+
+// Which slices of a codec stream are on the host.  A task whose slice is not there yet polls the slices' events in order -- whichever thread gets there first
+// moves the `arrived` mark -- so the threads never meet at a barrier between slices (12 runs, one per slice, cost ~0.5 ms of joins and idle tails).
+struct SliceArrivals {
+    const hipEvent_t* evs; std::atomic<uint32_t> arrived{ 0 }; std::atomic<bool> failed{ false };
+    // false: a slice's event failed (here or on another thread).  A few polls back to back -- a slice is ~0.1 ms of PCIe time --, then short sleeps: up to twelve
+    // threads spinning on hipEventQuery burn the process's CPU quota for nothing, and a throttled process expands slower
+    bool wait_for(uint32_t need) {
+        uint32_t polls = 0;
+        for (uint32_t a; (a = arrived.load(std::memory_order_acquire)) <= need && !failed.load(std::memory_order_relaxed); ) {
+            const hipError_t q = hipEventQuery(evs[a]);
+            if (q == hipSuccess) { uint32_t expect = a; arrived.compare_exchange_strong(expect, a + 1u, std::memory_order_acq_rel); polls = 0; }
+            else if (q != hipErrorNotReady) { (void)hipGetLastError(); failed.store(true); }
+            else { (void)hipGetLastError(); if (++polls < 32u) std::this_thread::yield(); else std::this_thread::sleep_for(std::chrono::microseconds(20)); }
+        }
+        return !failed.load(std::memory_order_relaxed);
+    }
+};
+// ommCpuBake's compressed delivery, once the bake's stream is idle and the head of the codec stream (its length, the per-block offsets of the raw units) is in
+// `head`: the rest of the stream lands in the working set's pinned block slice by slice (plan_codec_slices, host_expand.h) and the helper threads expand slice k
+// into res->arrayData while slice k + 1 is on the link; with `deferSmall` one of the tasks issues the small arrays on the second stream.  Noise-like states (the
+// stream would not be below half of the array): the array itself crosses the link.  Returns whether the result is complete; fills the transfer's timings.
+bool deliver_compressed(Baker& baker, BakeSession& ses, const CodecBlock& codec, const std::vector<uint8_t>& head, const DeviceResult& R, BakeResult* res, uint32_t T,
+                        const ResultArray& array, bool deferSmall, unsigned expandThreads, double c0, ommxBakeTimings& tm)
+{
+    constexpr uint32_t kSlices = CodecSlicePlan::kSlices;
+    hipStream_t stream = ses.stream;
+    const uint32_t E = R.numDescs; const size_t outIdx = index_bytes(R.indexFormat);
+    const double c1 = now_ms();
+    bool ok = true;
+    uint64_t streamBytes = 0; memcpy(&streamBytes, head.data(), 8);   // (shard_codec_finish: the length the stream has, or would have had)
+    const bool fits = streamBytes <= codec.cap && streamBytes >= codec.L.offRaw && ses.set->pinned.reserve((size_t)streamBytes + 4096);   // (pinned staging of the stream's size)
+    if (!fits) {
+        ok = HIP_OK(hipMemcpyAsync(res->arrayData, R.arrayData, (size_t)R.arrayDataSize, hipMemcpyDeviceToHost, stream))
+          && (!deferSmall || copy_small_arrays(res, R.descs, R.index, R.triAreaScratch, E, T, outIdx, stream)) && HIP_OK(hipStreamSynchronize(stream));
+        tm.resultTransfer = ommxResultTransfer_Plain;
+    } else {
+        uint8_t* hStream = ses.set->pinned.base; const uint8_t* dComp = codec.at.stream;
+        memcpy(hStream, head.data(), head.size());
+        const HostCodecLayout L = codec.L;
+        const CodecSlicePlan plan = plan_codec_slices(L, (const uint32_t*)(hStream + L.offOfs), streamBytes);
+        GpuEvents evs;   // one per slice: on the host
+        ok = evs.create(kSlices) && plan.ok;
+        for (uint32_t k = 0; ok && k < kSlices; ++k) {
+            const CodecSlicePlan::Slice& s = plan.slice[k];
+            if (s.c1 > s.c0) ok = HIP_OK(hipMemcpyAsync(hStream + s.c0, dComp + s.c0, (size_t)(s.c1 - s.c0), hipMemcpyDeviceToHost, stream));
+            if (ok && s.r1 > s.r0) ok = HIP_OK(hipMemcpyAsync(hStream + s.r0, dComp + s.r0, (size_t)(s.r1 - s.r0), hipMemcpyDeviceToHost, stream));
+            ok = ok && HIP_OK(hipEventRecord(evs.ev[k], stream));
+        }
+        if (ok) {
+            const std::shared_ptr<WorkerPool> poolRef = baker.worker_pool(expandThreads); WorkerPool& pool = *poolRef;
+            // the helper threads next to the memory they fill: on the two-socket host of the GPU box a process whose threads happened to run on the other socket
+            // expanded at half the rate (five process pairs on one lease: 17.0 - 25.0 ms per call without, 17.0 - 19.8 with the binding)
+            if (baker.knob(ommxBakerKnob_HelperAffinity) == 0) (void)pool.bind_near(res->arrayData);
+            uint8_t* dst = (uint8_t*)res->arrayData; const uint64_t dstBytes = R.arrayDataSize;
+            SliceArrivals arrivals{ evs.ev };
+            // (the result array is the block that was zeroed ahead: blocks and lines of zeros inside its zeroed extent, in complete pieces, are left alone)
+            std::atomic<uint64_t> skippedBytes{ 0 };
+            const ZeroedPieces zeroedPieces = array.zeroed();
+            const ZeroedPieces* const zeroedPtr = array.trust_zeroed() ? &zeroedPieces : nullptr;
+            ok = HIP_OK(hipEventSynchronize(evs.ev[0]));
+            if (ok) arrivals.arrived.store(1);
+            const int dev = baker.bind_device();
+            const uint32_t extra = deferSmall ? 1u : 0u;   // task 0: the small arrays, on the second stream
+            // ONE run over all tasks (2 MiB of the array each, in slice order)
+            if (ok) pool.run((uint32_t)codec_task_count(L) + extra, [&](uint32_t t0) {
+                if (extra && t0 == 0u) {
+                    const DeviceScope onDev(dev);
+                    if (!copy_small_arrays(res, R.descs, R.index, R.triAreaScratch, E, T, outIdx, ses.commStream) || !HIP_OK(hipStreamSynchronize(ses.commStream))) arrivals.failed.store(true);
+                    return;
+                }
+                uint64_t s0, s1; codec_task_range(L, t0 - extra, &s0, &s1);
+                if (!arrivals.wait_for(last_slice_needed(plan, s1))) return;
+                uint64_t skippedHere = 0;
+                codec_expand_blocks(dst, dstBytes, hStream, L, s0, s1, zeroedPtr, &skippedHere);
+                if (skippedHere) skippedBytes.fetch_add(skippedHere, std::memory_order_relaxed);
+            });
+            ok = ok && !arrivals.failed.load();
+            tm.expandThreads = pool.workers() + 1u;
+            tm.expandSkippedBytes = skippedBytes.load(); tm.prefilledBytes = zeroedPtr ? zeroed_bytes(zeroedPieces) : 0;
+        }
+        if (!ok) (void)hipStreamSynchronize(stream);   // (nothing may still be landing in the pinned block when the session hands it back)
+        tm.resultTransfer = ommxResultTransfer_Compressed; tm.compressedBytes = streamBytes;
+        if (ok) baker.lastCompressedArrayBytes.store(R.arrayDataSize);   // (what the next bake of this baker zeroes ahead)
+    }
+    tm.compressMs = (float)(c1 - c0); tm.expandMs = (float)(now_ms() - c1);
+    return ok;
+}
+
+// ommCpuBake: host arrays in, host arrays out.
+// What is let go of in which order (whichever way the function is left) is the reverse of the order of the named objects below:
+//   the result event (after the last wait on it) -> StreamOut (its DMA copies have landed) -> ResultArray (zeroing stopped, then its block back to the pool)
+//   -> HostResultGuard (comm stream, then the bake's stream drained, then an undelivered result destroyed) -> StreamDrain (the bake's stream idle)
+//   -> CodecBlock, DeviceResult, the raw upload (pooled device blocks go back) -> EventTimer -> BakeSession (working set back to its pool).
+// Top to bottom: fences | session | upload | host-tail bakes leave early | choice of the transfer | zeroing ahead | bake_core | compress | allocate | deliver
+// (plain, the rest of a streamed result, or compressed) | descriptor and timings.
 ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult* out)
 {
     const Logger& L = baker.log;
     const double t0 = now_ms();
-    struct Active { std::atomic<uint32_t>& n; explicit Active(std::atomic<uint32_t>& c) : n(c) { n.fetch_add(1); } ~Active() { n.fetch_sub(1); } } activeGuard(baker.activeBakes);
+    const ActiveBake activeGuard(baker.activeBakes);
     const ommResult fr = scope_fences(baker, d, true);
     if (fr != ommResult_SUCCESS) return fr;
     const uint32_t T = d.indexCount / 3u;
@@ -1311,22 +1583,17 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
 
     // ---- upload the caller's triangle data (the C ABI gives no vertex count: it is max(index)+1, as serialize_impl.cpp:60-79) ----
     const RawInputLayout raw = raw_input_layout(d, T, max_index(d.indexBuffer, d.indexFormat, 3ull * T));
-    uint8_t* dRaw = (uint8_t*)baker.devPool->acquire(raw.total);
-    if (!dRaw) return L.failure("[Failure] - out of device memory for the triangle data");
-    struct RawGuard { DevPool* pool; uint8_t* p; ~RawGuard() { pool->release(p); } } rawGuard{ baker.devPool.get(), dRaw };
+    const PoolBlock dRaw(baker.devPool.get(), raw.total);
+    if (!dRaw.p) return L.failure("[Failure] - out of device memory for the triangle data");
     EventTimer et(stream);
     const int u0 = et.mark();
-    DeviceInputs din; din.texCoords = dRaw + raw.offUv; din.indices = dRaw + raw.offIdx; din.perTriLevels = raw.lvlBytes ? dRaw + raw.offLvl : nullptr;
-    bool ok = true;
-    if (raw.uvBytes) ok = ok && HIP_OK(hipMemcpyAsync(dRaw + raw.offUv, d.texCoords, raw.uvBytes, hipMemcpyHostToDevice, stream));
-    if (raw.idxBytes) ok = ok && HIP_OK(hipMemcpyAsync(dRaw + raw.offIdx, d.indexBuffer, raw.idxBytes, hipMemcpyHostToDevice, stream));
-    if (raw.lvlBytes) ok = ok && HIP_OK(hipMemcpyAsync(dRaw + raw.offLvl, d.subdivisionLevels, raw.lvlBytes, hipMemcpyHostToDevice, stream));
-    if (!ok) return L.failure("[Failure] - host to device transfer failed");
+    const DeviceInputs din = upload_raw_inputs(raw, d, dRaw.bytes(), stream);
+    if (!din.texCoords) return L.failure("[Failure] - host to device transfer failed");
     const int u1 = et.mark();
 
     DeviceResult R; ommxBakeTimings tm; memset(&tm, 0, sizeof tm);
-    // declared after R and the upload guard, so destroyed first: pooled blocks are only handed back once the stream is idle (error paths too)
-    struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } syncOnExit{ stream };
+    CodecBlock codec;   // (compressed transfer: the device block of the codec stream)
+    const StreamDrain idleBeforeBlocksGoBack{ stream };
     if (wants_host_tail(d)) {
         // near-duplicate merge / size budget: device classification, then the reference's serial tail on the host (host_tail.cpp)
         HostTailRequest ht;
@@ -1334,73 +1601,22 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
         if (hr != ommResult_SUCCESS) return hr;
         HostTailResult hres; ommIndexFormat ifmt = ommIndexFormat_UINT_32;
         if (run_host_tail_for(d, T, ht.items, hres, ifmt) != ommResult_SUCCESS) return ommResult_FAILURE;
-        BakeResult* res = baker.mem.make<BakeResult>();
-        if (!res) return ommResult_FAILURE;
-        res->mem = baker.mem;
-        const uint32_t E = (uint32_t)hres.descs.size();
-        if (alloc_host_result(baker, res, E, hres.arrayData.size(), T) != ommResult_SUCCESS) { baker.mem.destroy(res); return ommResult_FAILURE; }
-        if (T && (!HIP_OK(hipMemcpyAsync(res->triArea, R.triAreaScratch, sizeof(float) * (size_t)T, hipMemcpyDeviceToHost, stream)) || !HIP_OK(hipStreamSynchronize(stream))))
-            { baker.mem.destroy(res); return L.failure("[Failure] - device to host transfer of the bake result failed"); }
-        if (E) { memcpy(res->arrayData, hres.arrayData.data(), hres.arrayData.size()); memcpy(res->descs, hres.descs.data(), sizeof(ommCpuOpacityMicromapDesc) * (size_t)E); }
-        memcpy(res->index, hres.index.data(), sizeof(int32_t) * (size_t)T);
-        memcpy(res->arrayHist, hres.arrayHist.data(), sizeof(ommCpuOpacityMicromapUsageCount) * clamp_hist_count(hres.arrayHist.size()));
-        memcpy(res->indexHist, hres.indexHist.data(), sizeof(ommCpuOpacityMicromapUsageCount) * clamp_hist_count(hres.indexHist.size()));
-        fill_result_desc(&res->desc, res->arrayData, hres.arrayData.size(), res->descs, E, res->index, T, ifmt, res->arrayHist, hres.arrayHist.size(), res->indexHist, hres.indexHist.size());
+        BakeResult* tailRes = nullptr;
+        const ommResult rr = host_result_from_tail(baker, ses, hres, ifmt, T, R.triAreaScratch, &tailRes);
+        if (rr != ommResult_SUCCESS) return rr;
         tm.totalMs = (float)(now_ms() - t0);
         store_timings(baker, tm);
-        *out = (ommCpuBakeResult)res;
+        *out = (ommCpuBakeResult)tailRes;
         return ommResult_SUCCESS;
     }
     // the finished blocks travel to their final place in the result array while the classification is still running (StreamOut): the array is allocated
     // when the first block is about to leave, from an upper bound of its size (every active work item a block)
-    BakeResult* res = baker.mem.make<BakeResult>();
+    HostResultGuard resGuard{ baker, baker.mem.make<BakeResult>(), &ses };
+    BakeResult* const res = resGuard.r;
     if (!res) return ommResult_FAILURE;
     res->mem = baker.mem;
-    // (error paths: nothing may still be copying into the result array when it is freed)
-    struct ResGuard { Baker& b; BakeResult*& r; BakeSession& s; ~ResGuard() { if (r) { if (s.commStream) (void)hipStreamSynchronize(s.commStream); (void)hipStreamSynchronize(s.stream); b.mem.destroy(r); } } } resGuard{ baker, res, ses };
-    // Zeroing ahead (round 6, compressed transfer).  The expansion of the result is bound by what twelve threads can store (1.27 GB in 3.6 ms), and a quarter of
-    // the metric configuration's 4-KiB codec blocks repeat state 0 = zeros.  While the device bakes the host is idle: the baker's helper threads zero an IDLE block
-    // of the result pool (what the previous bake left; never a fresh allocation, never a user allocator's memory) in pieces of 2 MiB, up to the size of the last
-    // compressed result; if the block then fits this bake's result it becomes the result, and the expansion leaves zero blocks of complete pieces alone.
-    // Whatever happens -- another transfer, a larger result, an error -- the block is either handed out after the threads have stopped, or goes back to the pool.
-    struct Prefill {
-        std::shared_ptr<WorkerPool> pool; std::shared_ptr<HostPool> host; uint8_t* block = nullptr; size_t cap = 0; bool pinned = false, started = false;
-        ZeroPlan plan{ 0, 0, 0 };   // (host_expand.h: the pieces, and the extent the expansion may trust -- a larger result's bytes beyond it are stale)
-        std::unique_ptr<std::atomic<uint8_t>[]> done; std::atomic<bool> cancel{ false };
-        void stop() { if (started) { cancel.store(true); pool->wait(); started = false; } }   // (pieces not begun stay unmarked: the expansion writes them like any other)
-        ~Prefill() { stop(); if (block) host->release(block); }
-    } prefill;
-    struct ArrayAlloc {
-        Baker* b; BakeResult* res; uint64_t cap; bool pinned; Prefill* pre; bool fromPrefill;
-        static uint8_t* get(void* u, uint64_t bytes, bool* pinned) {
-            ArrayAlloc& a = *(ArrayAlloc*)u;
-            if (pinned) *pinned = false;
-            if (a.res->arrayData && a.cap >= bytes) { if (pinned) *pinned = a.pinned; return (uint8_t*)a.res->arrayData; }
-            if (!a.res->arrayData && a.pre && a.pre->block) {   // the block that was zeroed ahead, if it holds this result (its threads have stopped before anybody writes into it)
-                a.pre->stop();
-                if (a.pre->cap >= bytes) {
-                    a.res->arrayData = a.pre->block; a.res->pool = a.pre->host; a.pinned = a.pre->pinned; a.cap = bytes; a.fromPrefill = true; a.pre->block = nullptr;
-                    if (pinned) *pinned = a.pinned;
-                    return (uint8_t*)a.res->arrayData;
-                }
-                a.pre->host->release(a.pre->block); a.pre->block = nullptr;
-            }
-            if (a.res->arrayData) { if (a.res->pool) { a.res->pool->release(a.res->arrayData); a.res->pool.reset(); } else a.b->mem.release(a.res->arrayData); a.res->arrayData = nullptr; a.cap = 0; }
-            // (small results are pooled -- pinned -- only while this is the baker's one bake in flight: sixteen callers copying into pinned blocks at once take
-            //  turns on the copy engines -- measured on configs[1]: 2 278 -> 1 190 bakes/s at 16 threads --, while one caller gains 0.28 ms per bake)
-            if (a.b->mem.alloc == default_alloc && ((size_t)bytes >= HostPool::kMinBytes || (a.b->activeBakes.load() <= 1u && a.b->hostPool->wants((size_t)bytes)))) {
-                a.res->arrayData = a.b->hostPool->acquire((size_t)bytes, &a.pinned);
-                if (a.res->arrayData) a.res->pool = a.b->hostPool;
-            }
-            if (!a.res->arrayData) { a.res->arrayData = a.b->mem.allocate((size_t)bytes, 64); a.pinned = false; }
-            a.cap = a.res->arrayData ? bytes : 0;
-            if (pinned) *pinned = a.pinned;
-            return (uint8_t*)a.res->arrayData;
-        }
-    } arrayAlloc{ &baker, res, 0, false, &prefill, false };
-    StreamOut so; so.set = ses.set.get(); so.allocUser = &arrayAlloc;
-    // (a block the streamed placement writes into is no longer only zeroed: if the stream is discarded, the compressed transfer that follows must write every byte)
-    so.alloc = [](void* u, uint64_t bytes, bool* pinned) -> uint8_t* { uint8_t* p = ArrayAlloc::get(u, bytes, pinned); ((ArrayAlloc*)u)->fromPrefill = false; return p; };
+    ResultArray array(baker, res);
+    StreamOut so; so.set = ses.set.get(); so.allocUser = &array; so.alloc = &ResultArray::get_for_stream;
     if (const uint64_t k = baker.knob(ommxBakerKnob_StreamChunks)) { so.chunksWanted = (uint32_t)k; so.forced = true; }
     // How a large arrayData reaches the caller (ommxBakerKnob_ResultTransfer).  COMPRESSED (round 5): the bake finishes on the device, the array crosses PCIe as
     // a codec stream (tail_kernels.hip: 6 % of its bytes at the metric configuration) and host threads expand it into the caller's array -- 190 - 250 GB/s with
@@ -1416,48 +1632,12 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
     so.compressedAvailable = wantCompressed && transferKnob == ommxResultTransfer_Auto;
     const bool canStream = (!wantCompressed || so.compressedAvailable) && transferKnob != ommxResultTransfer_Plain && ses.open_comm() && ses.open_place();
     so.copyStream = ses.commStream; so.placeStream = ses.placeStream; so.device = baker.bind_device();
-    struct CodecOut : CodecBlockLayout { uint8_t* dBlock = nullptr; DevPool* pool = nullptr; uint8_t* dComp = nullptr; uint32_t* dSize = nullptr; bool on = false;
-                      uint8_t* unitCodes = nullptr; uint32_t* blockRawCounts = nullptr;   // (set when the gather produces the codes)
-                      ~CodecOut() { if (dBlock) pool->release(dBlock); } } co;
-    auto codec_block = [&](uint64_t arrayDataSize, bool withCodes) -> bool {
-        static_cast<CodecBlockLayout&>(co) = codec_block_layout(arrayDataSize);
-        const size_t codeBytes = withCodes ? pad256((size_t)(co.padded / 16u)) : 0, countBytes = withCodes ? pad256(((size_t)co.L.blocks + 1) * 4) : 0;
-        co.pool = baker.devPool.get(); co.dBlock = (uint8_t*)baker.devPool->acquire(256 + co.scratchBytes + codeBytes + countBytes + (size_t)co.cap);
-        if (!co.dBlock || !co.fits) return false;
-        co.dSize = (uint32_t*)co.dBlock; co.dComp = co.dBlock + 256 + co.scratchBytes + codeBytes + countBytes;
-        if (withCodes) { co.unitCodes = co.dBlock + 256 + co.scratchBytes; co.blockRawCounts = (uint32_t*)(co.unitCodes + codeBytes); }
-        return true;
-    };
-    if (wantCompressed) R.gatherCodes = [&](uint64_t arrayDataSize, uint8_t** unitCodes, uint32_t** blockRawCounts) -> bool {
-        if (arrayDataSize < kCompressedMinBytes || (arrayDataSize & 15u) != 0 || !codec_block(arrayDataSize, true)) return false;
-        // (the units of the padding behind the array count as zeros; the counts start at zero)
-        const uint64_t units = arrayDataSize / 16u, paddedUnits = co.padded / 16u;
-        bool okm = HIP_OK(hipMemsetAsync(co.blockRawCounts, 0, ((size_t)co.L.blocks + 1) * 4, stream));
-        if (okm && paddedUnits > units) okm = HIP_OK(hipMemsetAsync(co.unitCodes + units, 0, (size_t)(paddedUnits - units), stream));
-        if (!okm) { co.unitCodes = nullptr; co.blockRawCounts = nullptr; return false; }
-        *unitCodes = co.unitCodes; *blockRawCounts = co.blockRawCounts;
-        return true;
-    };
+    // (asked by bake_core right before the gather: from 32 MiB, every OMM a multiple of 16 bytes -- the gather then leaves the codec's codes next to the array)
+    if (wantCompressed) R.gatherCodes = [&](uint64_t bytes, uint8_t** unitCodes, uint32_t** blockRawCounts) {
+        const bool k = bytes >= kCompressedMinBytes && (bytes & 15u) == 0 && codec.reserve(baker.devPool.get(), bytes, true) && codec.prepare_codes(stream);
+        *unitCodes = k ? codec.at.unitCodes : nullptr; *blockRawCounts = k ? codec.at.blockRawCounts : nullptr; return k; };
     // zeroing ahead: only with the default allocator, the compressed transfer on offer, helper threads, and an idle pool block of the last compressed result's size
-    if (wantCompressed && baker.mem.alloc == default_alloc && baker.knob(ommxBakerKnob_RetainMemory) == 0 && baker.knob(ommxBakerKnob_ZeroAhead) == 0) {
-        const uint64_t last = baker.lastCompressedArrayBytes.load();
-        if (last >= kCompressedMinBytes && (prefill.block = (uint8_t*)baker.hostPool->acquire_idle((size_t)last, &prefill.cap, &prefill.pinned)) != nullptr) {
-            prefill.host = baker.hostPool; prefill.pool = baker.worker_pool(expandThreads);
-            prefill.plan = zero_plan(prefill.cap, (size_t)last);
-            prefill.done.reset(new (std::nothrow) std::atomic<uint8_t>[prefill.plan.pieces]);
-            if (prefill.done && ((uintptr_t)prefill.block & 4095u) == 0u) {
-                for (size_t j = 0; j < prefill.plan.pieces; ++j) prefill.done[j].store(0);
-                if (baker.knob(ommxBakerKnob_HelperAffinity) == 0) (void)prefill.pool->bind_near(prefill.block);
-                Prefill* pf = &prefill;
-                prefill.started = prefill.pool->start((uint32_t)prefill.plan.pieces, [pf](uint32_t j) {
-                    if (pf->cancel.load(std::memory_order_relaxed)) return;
-                    size_t lo, hi; zero_piece_range(pf->plan, j, &lo, &hi);
-                    fill_zero_nt(pf->block, lo, hi);
-                    pf->done[j].store(1, std::memory_order_release);
-                });
-            }
-        }
-    }
+    if (wantCompressed && baker.mem.alloc == default_alloc && baker.knob(ommxBakerKnob_RetainMemory) == 0 && baker.knob(ommxBakerKnob_ZeroAhead) == 0) array.zero_ahead(expandThreads);
     const ommResult br = bake_core(baker, d, din, &d, ses.arena, ses.states, stream, et, R, tm, nullptr, nullptr, canStream ? &so : nullptr);
     R.gatherCodes = nullptr;
     if (br != ommResult_SUCCESS) return br;
@@ -1470,127 +1650,32 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
     const double c0 = now_ms();
     if (E && wantCompressed && !so.used && R.arrayDataSize >= kCompressedMinBytes) {
         // (the device array was taken from the result pool, whose blocks are multiples of 4096 bytes: the codec may read the padding, the host never writes it)
-        if (co.unitCodes)   // the gather has left the codes of the units and the raw counts of the blocks: the array is read for its raw units only
-            co.on = HIP_OK(run_shard_compress_coded(R.arrayData, co.padded, co.unitCodes, co.blockRawCounts, co.dComp, co.cap, co.dSize, co.dBlock + 256, co.scratchBytes, stream));
-        else if (!co.dBlock && codec_block(R.arrayDataSize, false))
-            co.on = HIP_OK(run_shard_compress(R.arrayData, co.padded, co.dComp, co.cap, co.dSize, co.dBlock + 256, co.scratchBytes, stream));
+        if (codec.has_codes() || (!codec.reserved() && codec.reserve(baker.devPool.get(), R.arrayDataSize, false))) codec.on = codec.compress(R.arrayData, stream);
         (void)hipGetLastError();
     }
+    bool ok = true;
     if (E) {
-        ok = ArrayAlloc::get(&arrayAlloc, R.arrayDataSize, nullptr) != nullptr;   // (a streamed bake has it already; every other path asks for the exact size)
+        ok = array.get(R.arrayDataSize, nullptr) != nullptr;   // (a streamed bake has it already; every other path asks for the exact size)
         res->descs = (ommCpuOpacityMicromapDesc*)baker.mem.allocate(sizeof(ommCpuOpacityMicromapDesc) * (size_t)E, 16);
         ok = ok && res->descs;
-        if (co.on) {   // the stream's header (its length) and the per-block offsets of the raw units: the first piece of the stream, needed before the others can be cut
-            codecHead.resize((size_t)co.L.offCodes);
-            ok = ok && HIP_OK(hipMemcpyAsync(codecHead.data(), co.dComp, (size_t)co.L.offCodes, hipMemcpyDeviceToHost, stream));
+        if (codec.on) {   // the stream's header (its length) and the per-block offsets of the raw units: the first piece of the stream, needed before the others can be cut
+            codecHead.resize((size_t)codec.L.offCodes);
+            ok = ok && HIP_OK(hipMemcpyAsync(codecHead.data(), codec.at.stream, (size_t)codec.L.offCodes, hipMemcpyDeviceToHost, stream));
         } else if (!so.used) ok = ok && HIP_OK(hipMemcpyAsync(res->arrayData, R.arrayData, (size_t)R.arrayDataSize, hipMemcpyDeviceToHost, stream));
     }
     res->index = (int32_t*)baker.mem.allocate(sizeof(int32_t) * (size_t)(T ? T : 1), 16);
     res->triArea = (float*)baker.mem.allocate(sizeof(float) * (size_t)(T ? T : 1), 16);
     ok = ok && res->index != nullptr && res->triArea != nullptr;
     const size_t outIdx = index_bytes(R.indexFormat);
-    // descriptors, index buffer and triangle areas (8.6 MB at the metric configuration, into the caller's pageable arrays: each copy holds its thread until it is done).
-    // With a compressed result they cross the link on the second stream WHILE the helper threads expand the array (one of the expansion's tasks issues them);
-    // otherwise here, in front of the wait.
-    auto small_copies = [&](hipStream_t s) -> bool {
-        bool k = true;
-        if (E) k = HIP_OK(hipMemcpyAsync(res->descs, R.descs, sizeof(ommCpuOpacityMicromapDesc) * (size_t)E, hipMemcpyDeviceToHost, s));
-        if (k && T) k = HIP_OK(hipMemcpyAsync(res->index, R.index, outIdx * T, hipMemcpyDeviceToHost, s));
-        if (k && T) k = HIP_OK(hipMemcpyAsync(res->triArea, R.triAreaScratch, sizeof(float) * (size_t)T, hipMemcpyDeviceToHost, s));
-        return k;
-    };
-    hipEvent_t evResult = nullptr;   // the device result is complete (everything in front of it on the bake's stream)
-    bool deferSmall = ok && co.on && ses.open_comm() && HIP_OK(hipEventCreateWithFlags(&evResult, hipEventDisableTiming));
-    if (deferSmall) deferSmall = HIP_OK(hipEventRecord(evResult, stream)) && HIP_OK(hipStreamWaitEvent(ses.commStream, evResult, 0));
-    struct EvGuard { hipEvent_t& e; ~EvGuard() { if (e) (void)hipEventDestroy(e); } } evGuard{ evResult };
-    if (ok && !deferSmall) ok = small_copies(stream);
+    // the small arrays: behind the expansion's back on the second stream with a compressed result (defer_small_arrays), otherwise here, in front of the wait
+    GpuEvents resultEvent;   // the device result is complete (everything in front of it on the bake's stream)
+    const bool deferSmall = ok && codec.on && defer_small_arrays(ses, resultEvent);
+    if (ok && !deferSmall) ok = copy_small_arrays(res, R.descs, R.index, R.triAreaScratch, E, T, outIdx, stream);
     const int d1 = et.mark();
     ok = ok && HIP_OK(hipStreamSynchronize(stream));
     if (so.chunks) { ok = so.finish() && ok; if (so.used) tm.streamTailMs = (float)(so.lastByteMs - so.classifyEndMs); }   // (the last streamed bytes arrive while the small arrays above are read back)
-    if (ok && co.on) {
-        const double c1 = now_ms();
-        uint64_t streamBytes = 0; memcpy(&streamBytes, codecHead.data(), 8);   // (shard_codec_finish: the length the stream has, or would have had)
-        const bool fits = streamBytes <= co.cap && streamBytes >= co.L.offRaw && ses.set->pinned.reserve((size_t)streamBytes + 4096);   // (pinned staging of the stream's size)
-        uint8_t* hStream = ses.set->pinned.base;
-        if (fits) memcpy(hStream, codecHead.data(), codecHead.size());
-        if (!fits) {   // noise-like states (the stream would not be below half of the array): the array itself crosses the link
-            ok = HIP_OK(hipMemcpyAsync(res->arrayData, R.arrayData, (size_t)R.arrayDataSize, hipMemcpyDeviceToHost, stream)) && (!deferSmall || small_copies(stream)) && HIP_OK(hipStreamSynchronize(stream));
-            tm.resultTransfer = ommxResultTransfer_Plain;
-        } else {
-            // The rest of the stream lands in the working set's pinned block slice by slice -- the codes of a range of codec blocks and the raw units those blocks
-            // point at (both contiguous: the offsets are a prefix sum) -- and the helper threads expand slice k while slice k + 1 is on the link.
-            constexpr uint32_t kSlices = 12;
-            const uint32_t* ofs = (const uint32_t*)(hStream + co.L.offOfs);
-            hipEvent_t evs[kSlices]; uint32_t nev = 0;
-            for (; nev < kSlices; ++nev) if (!HIP_OK(hipEventCreateWithFlags(&evs[nev], hipEventDisableTiming))) break;
-            ok = nev == kSlices;
-            uint64_t blockCut[kSlices + 1];
-            for (uint32_t k = 0; k <= kSlices; ++k) blockCut[k] = co.L.blocks * k / kSlices;
-            for (uint32_t k = 0; ok && k < kSlices; ++k) {
-                const uint64_t b0 = blockCut[k], b1 = blockCut[k + 1];
-                const uint64_t c0b = co.L.offCodes + b0 * 128u, c1b = b1 == co.L.blocks ? co.L.offRaw : co.L.offCodes + b1 * 128u;
-                const uint64_t r0b = co.L.offRaw + 16ull * ofs[b0], r1b = co.L.offRaw + 16ull * ofs[b1];
-                ok = r0b <= r1b && r1b <= streamBytes;   // (a corrupt offset table must not turn into a wild copy)
-                if (ok && c1b > c0b) ok = HIP_OK(hipMemcpyAsync(hStream + c0b, co.dComp + c0b, (size_t)(c1b - c0b), hipMemcpyDeviceToHost, stream));
-                if (ok && r1b > r0b) ok = HIP_OK(hipMemcpyAsync(hStream + r0b, co.dComp + r0b, (size_t)(r1b - r0b), hipMemcpyDeviceToHost, stream));
-                ok = ok && HIP_OK(hipEventRecord(evs[k], stream));
-            }
-            if (ok) {
-                const std::shared_ptr<WorkerPool> poolRef = baker.worker_pool(expandThreads); WorkerPool& pool = *poolRef;
-                // the helper threads next to the memory they fill: on the two-socket host of the GPU box a process whose threads happened to run on the other socket
-                // expanded at half the rate (five process pairs on one lease: 17.0 - 25.0 ms per call without, 17.0 - 19.8 with the binding)
-                if (baker.knob(ommxBakerKnob_HelperAffinity) == 0) (void)pool.bind_near(res->arrayData);
-                uint8_t* dst = (uint8_t*)res->arrayData; const uint64_t dstBytes = R.arrayDataSize; const HostCodecLayout L = co.L;
-                // ONE run over all tasks (2 MiB of the array each, in slice order): a task whose slice is not on the host yet polls the slices' events in order --
-                // whichever thread gets there first moves the `arrived` mark -- so the threads never meet at a barrier between slices (12 runs, one per slice,
-                // cost ~0.5 ms of joins and idle tails)
-                constexpr uint64_t kTaskBlocks = 512;
-                const uint64_t numTasks = (co.L.blocks + kTaskBlocks - 1) / kTaskBlocks;
-                std::atomic<uint32_t> arrived{ 0 }; std::atomic<bool> failed{ false };
-                // (the result array is the block that was zeroed ahead: blocks and lines of zeros inside its zeroed extent, in complete pieces, are left alone)
-                std::atomic<uint64_t> skippedBytes{ 0 };
-                const ZeroedPieces zeroedPieces = zeroed_pieces(prefill.plan, prefill.done.get());
-                const ZeroedPieces* const zeroedPtr = arrayAlloc.fromPrefill && prefill.done ? &zeroedPieces : nullptr;
-                ok = HIP_OK(hipEventSynchronize(evs[0]));
-                if (ok) arrived.store(1);
-                const int dev = baker.bind_device();
-                const uint32_t extra = deferSmall ? 1u : 0u;   // task 0: the small arrays, on the second stream
-                if (ok) pool.run((uint32_t)numTasks + extra, [&](uint32_t t0) {
-                    if (extra && t0 == 0u) {
-                        const DeviceScope onDev(dev);
-                        if (!small_copies(ses.commStream) || !HIP_OK(hipStreamSynchronize(ses.commStream))) failed.store(true);
-                        return;
-                    }
-                    const uint32_t t = t0 - extra;
-                    const uint64_t s0 = (uint64_t)t * kTaskBlocks, s1 = s0 + kTaskBlocks < L.blocks ? s0 + kTaskBlocks : L.blocks;
-                    uint32_t need = 0; while (need + 1u < kSlices && blockCut[need + 1u] < s1) ++need;   // the last slice this task reads from
-                    // (a few polls back to back -- a slice is ~0.1 ms of PCIe time --, then short sleeps: up to twelve threads spinning on hipEventQuery burn the
-                    //  process's CPU quota for nothing, and a throttled process expands slower)
-                    uint32_t polls = 0;
-                    for (uint32_t a; (a = arrived.load(std::memory_order_acquire)) <= need && !failed.load(std::memory_order_relaxed); ) {
-                        const hipError_t q = hipEventQuery(evs[a]);
-                        if (q == hipSuccess) { uint32_t expect = a; arrived.compare_exchange_strong(expect, a + 1u, std::memory_order_acq_rel); polls = 0; }
-                        else if (q != hipErrorNotReady) { (void)hipGetLastError(); failed.store(true); }
-                        else { (void)hipGetLastError(); if (++polls < 32u) std::this_thread::yield(); else std::this_thread::sleep_for(std::chrono::microseconds(20)); }
-                    }
-                    if (!failed.load(std::memory_order_relaxed)) {
-                        uint64_t skippedHere = 0;
-                        codec_expand_blocks(dst, dstBytes, hStream, L, s0, s1, zeroedPtr, &skippedHere);
-                        if (skippedHere) skippedBytes.fetch_add(skippedHere, std::memory_order_relaxed);
-                    }
-                });
-                ok = ok && !failed.load();
-                tm.expandThreads = pool.workers() + 1u;
-                tm.expandSkippedBytes = skippedBytes.load(); tm.prefilledBytes = zeroedPtr ? zeroed_bytes(zeroedPieces) : 0;
-            }
-            if (!ok) (void)hipStreamSynchronize(stream);   // (nothing may still be landing in the pinned block when the session hands it back)
-            for (uint32_t k = 0; k < nev; ++k) (void)hipEventDestroy(evs[k]);
-            tm.resultTransfer = ommxResultTransfer_Compressed; tm.compressedBytes = streamBytes;
-            if (ok && fits) baker.lastCompressedArrayBytes.store(R.arrayDataSize);   // (what the next bake of this baker zeroes ahead)
-        }
-        tm.compressMs = (float)(c1 - c0); tm.expandMs = (float)(now_ms() - c1);
-    } else if (so.used) tm.resultTransfer = ommxResultTransfer_Streamed;
-    else tm.resultTransfer = ommxResultTransfer_Plain;
+    if (ok && codec.on) ok = deliver_compressed(baker, ses, codec, codecHead, R, res, T, array, deferSmall, expandThreads, c0, tm);
+    else tm.resultTransfer = so.used ? ommxResultTransfer_Streamed : ommxResultTransfer_Plain;
     if (!ok) { return L.failure("[Failure] - device to host transfer of the bake result failed"); }
 
     // histograms: format {2-state, 4-state} x level ascending, non-zero entries only (:1833-1850); one global format here
@@ -1600,8 +1685,7 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
     fill_result_desc(&res->desc, res->arrayData, R.arrayDataSize, res->descs, E, res->index, T, R.indexFormat, res->arrayHist, nAH, res->indexHist, nIH);
     tm.uploadMs = et.ms(u0, u1); tm.downloadMs = et.ms(d0, d1); tm.totalMs = (float)(now_ms() - t0);
     store_timings(baker, tm);
-    *out = (ommCpuBakeResult)res;
-    res = nullptr;   // (handed over: the guard lets go)
+    *out = (ommCpuBakeResult)resGuard.release();   // (handed over: the guard lets go)
     return ommResult_SUCCESS;
 }
 
@@ -2456,8 +2540,10 @@ ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBake
     Texture* tex0 = untag<Texture>(d.texture);
     // ---- per rank: device, baker, texture (made before the threads start: replicas and shadow bakers are created once and kept) ----
     struct Rank {
-        int dev = 0; Baker* baker = nullptr; Texture* tex = nullptr; ShardedBake* sb = nullptr; uint8_t* dRaw = nullptr; uint8_t* dCodec = nullptr;
+        int dev = 0; Baker* baker = nullptr; Texture* tex = nullptr; ShardedBake* sb = nullptr; PoolBlock dRaw; CodecBlock codec;
         std::vector<uint32_t> meta; const uint8_t* hStream = nullptr; bool raw = false; ommResult status = ommResult_SUCCESS;
+        // on the rank's device: the sharded bake first (its session drains the rank's streams), then the pooled blocks those streams used
+        ~Rank() { const DeviceScope onDev(dev); if (sb) baker->mem.destroy(sb); dRaw.release(); codec.block.release(); }
     };
     std::vector<Rank> ranks(N);
     for (uint32_t r = 0; r < N; ++r) {
@@ -2476,15 +2562,12 @@ ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBake
         Rank& R = ranks[r];
         const DeviceScope onDev(R.dev);
         Baker& sub = *R.baker;
-        bool ok = true;
-        R.dRaw = (uint8_t*)sub.devPool->acquire(raw.total);
-        ok = R.dRaw != nullptr;
-        if (ok && raw.uvBytes) ok = HIP_OK(hipMemcpy(R.dRaw + raw.offUv, d.texCoords, raw.uvBytes, hipMemcpyHostToDevice));
-        if (ok && raw.idxBytes) ok = HIP_OK(hipMemcpy(R.dRaw + raw.offIdx, d.indexBuffer, raw.idxBytes, hipMemcpyHostToDevice));
-        if (ok && raw.lvlBytes) ok = HIP_OK(hipMemcpy(R.dRaw + raw.offLvl, d.subdivisionLevels, raw.lvlBytes, hipMemcpyHostToDevice));
+        (void)R.dRaw.acquire(sub.devPool.get(), raw.total);
+        const DeviceInputs din = upload_raw_inputs(raw, d, R.dRaw.bytes(), nullptr);
+        bool ok = din.texCoords != nullptr;
         ommCpuBakeInputDesc dd = d;
         dd.texture = (ommCpuTexture)((uintptr_t)R.tex | kTexture);
-        dd.texCoords = R.dRaw + raw.offUv; dd.indexBuffer = R.dRaw + raw.offIdx; dd.subdivisionLevels = raw.lvlBytes ? R.dRaw + raw.offLvl : nullptr;
+        dd.texCoords = din.texCoords; dd.indexBuffer = din.indices; dd.subdivisionLevels = din.perTriLevels;
         if (ok) { R.status = sharded_begin(&sub, &dd, r, N, false, &R.sb); ok = R.status == ommResult_SUCCESS; if (!ok) R.sb = nullptr; }
         else R.status = ommResult_FAILURE;
         if (!team.barrier(ok)) return;
@@ -2502,12 +2585,12 @@ ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBake
         // ---- replicated tail, layout, this rank's blocks packed into its contribution ----
         if (ok) { R.status = sharded_tail(R.sb); ok = R.status == ommResult_SUCCESS; }
         // ---- the contribution as a codec stream, over this device's own link ----
-        const CodecBlockLayout cb = codec_block_layout(c.strideBytes);   // (a multiple of 256 already: cb.padded is the stride)
-        if (ok) { R.dCodec = (uint8_t*)sub.devPool->acquire(256 + cb.scratchBytes + (size_t)cb.cap); ok = R.dCodec != nullptr && cb.fits; }
+        const CodecBlock& cb = R.codec;
+        if (ok) ok = R.codec.reserve(sub.devPool.get(), c.strideBytes, false);   // (a multiple of 256 already: cb.padded is the stride)
         uint64_t streamBytes = 0;
         if (ok) {
-            uint8_t* dComp = R.dCodec + 256 + cb.scratchBytes;
-            ok = HIP_OK(run_shard_compress(c.dContrib, cb.padded, dComp, cb.cap, (uint32_t*)R.dCodec, R.dCodec + 256, cb.scratchBytes, stream))
+            uint8_t* dComp = cb.at.stream;
+            ok = cb.compress(c.dContrib, stream)
               && HIP_OK(hipMemcpyAsync(&streamBytes, dComp, 8, hipMemcpyDeviceToHost, stream)) && HIP_OK(hipStreamSynchronize(stream));
             R.raw = ok && (streamBytes > cb.cap || streamBytes < cb.L.offRaw);
             const uint64_t take = R.raw ? c.totals[r] : streamBytes;
@@ -2527,12 +2610,10 @@ ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBake
     if (!spawned) {
         team.abort();   // (threads that did start wait in the first barrier for ranks that never come)
         for (auto& t : threads) t.join();
-        for (Rank& R : ranks) { const DeviceScope onDev(R.dev); if (R.sb) R.baker->mem.destroy(R.sb); if (R.dRaw) R.baker->devPool->release(R.dRaw); if (R.dCodec) R.baker->devPool->release(R.dCodec); }
         return L.failure("[Failure] - multi-device bake: could not start a thread per device");
     }
     guardedBody(0);
     for (auto& t : threads) t.join();
-    struct Cleanup { std::vector<Rank>& ranks; ~Cleanup() { for (Rank& R : ranks) { const DeviceScope onDev(R.dev); if (R.sb) R.baker->mem.destroy(R.sb); if (R.dRaw) R.baker->devPool->release(R.dRaw); if (R.dCodec) R.baker->devPool->release(R.dCodec); } } } cleanup{ ranks };
     for (const Rank& R : ranks) if (R.status != ommResult_SUCCESS) return R.status;
     for (const Rank& R : ranks) if (!R.sb || !R.hStream) return L.failure("[Failure] - multi-device bake: a device failed");
     const double tA = now_ms();
@@ -2546,8 +2627,7 @@ ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBake
     // Asynchronous copies into the vectors above (and, further down, into the result's arrays) are queued on stream0: whatever way this function is left --
     // a failed copy half way down a chain, an exception of a host container or of the thread pool -- the stream is drained BEFORE their memory is released
     // (destructors run in reverse order of declaration: each guard is declared right behind the memory it protects).
-    struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } };
-    const SyncOnExit drainBeforeVectors{ stream0 };
+    const StreamDrain drainBeforeVectors{ stream0 };
     bool ok = true;
     if (E) ok = HIP_OK(hipMemcpyAsync(hOrder.data(), c0.to.order, (size_t)E * 4, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(hDstOfs.data(), c0.to.dstOfs, (size_t)E * 4, hipMemcpyDeviceToHost, stream0))
               && HIP_OK(hipMemcpyAsync(hSizes.data(), c0.to.sizes, (size_t)E * 4, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(hCofs.data(), c0.tab.cofs, (size_t)E * 8, hipMemcpyDeviceToHost, stream0));
@@ -2560,16 +2640,14 @@ ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBake
     struct DresGuard { Baker& b; DeviceBakeResult* p; ~DresGuard() { b.mem.destroy(p); } } dresGuard{ baker, dr };
     DeviceResult& DR = dr->R;
 
-    BakeResult* res = baker.mem.make<BakeResult>();
+    HostResultGuard resGuard{ baker, baker.mem.make<BakeResult>(), nullptr };
+    BakeResult* const res = resGuard.r;
     if (!res) return ommResult_FAILURE;
     res->mem = baker.mem;
-    struct ResGuard { Baker& b; BakeResult*& r; ~ResGuard() { if (r) b.mem.destroy(r); } } resGuard{ baker, res };
-    const SyncOnExit drainBeforeResult{ stream0 };
+    const StreamDrain drainBeforeResult{ stream0 };
     if (E && baker.mem.alloc == default_alloc && baker.hostPool->wants((size_t)DR.arrayDataSize)) { res->arrayData = baker.hostPool->acquire((size_t)DR.arrayDataSize); if (res->arrayData) res->pool = baker.hostPool; }
     if (alloc_host_result(baker, res, E, (size_t)DR.arrayDataSize, T) != ommResult_SUCCESS) return ommResult_FAILURE;
-    const size_t outIdx = index_bytes(DR.indexFormat);
-    if (E) ok = HIP_OK(hipMemcpyAsync(res->descs, DR.descs, sizeof(ommCpuOpacityMicromapDesc) * (size_t)E, hipMemcpyDeviceToHost, stream0));
-    if (ok && T) ok = HIP_OK(hipMemcpyAsync(res->index, DR.index, outIdx * T, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(res->triArea, c0.tab.triArea, sizeof(float) * (size_t)T, hipMemcpyDeviceToHost, stream0));
+    ok = copy_small_arrays(res, DR.descs, DR.index, c0.tab.triArea, E, T, index_bytes(DR.indexFormat), stream0);
     // the blocks: OMM ranges of ~2 MiB each to the helper threads, while the small arrays above are on their way
     uint32_t threadsUsed = 1;
     if (ok && E) {
@@ -2597,8 +2675,7 @@ ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBake
         baker.timings.devices = N; baker.timings.resultTransfer = ommxResultTransfer_Compressed; baker.timings.compressedBytes = wire; baker.timings.expandThreads = threadsUsed;
         baker.timings.expandMs = (float)(now_ms() - tA); baker.timings.totalMs = (float)(now_ms() - t0); baker.timings.contributionBytes = strideBytes;
     }
-    *out = (ommCpuBakeResult)res;
-    res = nullptr;
+    *out = (ommCpuBakeResult)resGuard.release();
     return ommResult_SUCCESS;
 }
 } // namespace
@@ -2895,7 +2972,7 @@ ommResult stats_device(Baker& b, const ommCpuBakeResultDesc& r, const float* are
     a.stateCounts = outputs ? outputs->stateCounts : nullptr; a.referenceCounts = outputs ? outputs->referenceCounts : nullptr;
     a.knownFraction = outputs ? outputs->knownFraction : nullptr;
     const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
-    struct PoolBlock { DevPool* pool; void* p; ~PoolBlock() { if (p) pool->release(p); } } scratch{ b.devPool.get(), b.devPool->acquire(stats_scratch_bytes(a)) };
+    const PoolBlock scratch(b.devPool.get(), stats_scratch_bytes(a));
     if (!scratch.p) return b.log.failure("[Failure] - out of device memory for the statistics scratch");
     StatsTotals t;
     if (launch_stats(a, scratch.p, &t, stream) != hipSuccess) {
@@ -2951,16 +3028,14 @@ ommResult extract_geometry(Baker& b, const ommCpuBakeResultDesc& r, const ommxMi
     int deviceCount = 0;
     if (!HIP_OK(hipGetDeviceCount(&deviceCount)) || deviceCount < 1) { (void)hipGetLastError(); return b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)"); }
     const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
-    struct PoolBlock { DevPool* pool; void* p; ~PoolBlock() { if (p) pool->release(p); } };
-    PoolBlock head{ b.devPool.get(), b.devPool->acquire(geo_head_bytes(a)) }, tiles{ b.devPool.get(), nullptr };
+    PoolBlock head(b.devPool.get(), geo_head_bytes(a)), tiles;
     if (!head.p) return b.log.failure("[Failure] - out of device memory for the geometry scratch");
     // (after a failed launch the scratch goes back only when nothing can still touch it)
     const auto failed = [&] { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); return b.log.failure("[Failure] - the geometry kernels could not run"); };
     unsigned long long tileCount = 0;
     if (geo_count_tiles(a, head.p, &tileCount, stream) != hipSuccess) return failed();
     if (tileCount) {
-        tiles.p = b.devPool->acquire(geo_tile_bytes(tileCount));
-        if (!tiles.p) return b.log.failure("[Failure] - out of device memory for the geometry scratch");
+        if (!tiles.acquire(b.devPool.get(), geo_tile_bytes(tileCount))) return b.log.failure("[Failure] - out of device memory for the geometry scratch");
     }
     bool wantNodes = false, wantAny = false;
     if (outputs) for (int k = 0; k < 4; ++k) { wantNodes = wantNodes || outputs->nodes[k]; wantAny = wantAny || outputs->nodes[k] || outputs->primitiveOffsets[k]; }

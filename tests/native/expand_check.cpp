@@ -1,7 +1,7 @@
 // expand_check.cpp -- host side of ommCpuBake's compressed result (omm_amd/csrc/host_expand.cpp) against a scalar model of the device codec
 // (tail_kernels.hip: codec_code / shard_codec_write): random arrays with long constant runs, every size class incl. tails that are not a multiple of 16,
 // unaligned destinations, worker pools of 0 .. 7 threads.  Prints "ok <cases>" or the first mismatch.   (CPU only; built and run by tests/test_host_expand.py)
-#include "../../omm_amd/csrc/host_expand.h"
+#include "codec_model.h"   // encode(): the scalar model of the device codec
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -10,23 +10,6 @@
 using namespace ommx;
 static uint64_t s = 0x9E3779B97F4A7C15ull;
 static uint64_t rnd() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return s; }
-// the codec stream of src[0 .. padded) (scalar model of tail_kernels.hip: codec_code / shard_codec_write)
-static std::vector<uint8_t> encode(const std::vector<uint8_t>& src, const HostCodecLayout& L)
-{
-    std::vector<uint8_t> stream(L.offRaw + 16 * L.units + 64, 0xEE);
-    uint32_t* ofs = (uint32_t*)(stream.data() + L.offOfs); uint32_t nraw = 0;
-    for (uint64_t u = 0; u < L.units; ++u) {
-        if (u % 256 == 0) ofs[u / 256] = nraw;
-        uint32_t w[4]; memcpy(w, &src[u * 16], 16);
-        const bool same = w[0] == w[1] && w[0] == w[2] && w[0] == w[3];
-        const uint32_t code = !same ? 4u : (w[0] == 0u ? 0u : (w[0] == 0x55555555u ? 1u : (w[0] == 0xAAAAAAAAu ? 2u : (w[0] == 0xFFFFFFFFu ? 3u : 4u))));
-        uint8_t& c = stream[L.offCodes + u / 2];
-        c = (uint8_t)((u & 1) ? ((c & 0x0F) | (code << 4)) : code);
-        if (code == 4u) { memcpy(&stream[L.offRaw + 16ull * nraw], w, 16); ++nraw; }
-    }
-    ofs[L.blocks] = nraw;
-    return stream;
-}
 int main()
 {
     int cases = 0;
@@ -106,7 +89,7 @@ int main()
         if (skipped.load() == 0) { printf("ZERO-AHEAD skipped nothing variant=%d\n", variant); return 1; }
         ++zeroCases;
     }
-    // ---- zeroing ahead of a block that then holds ANOTHER size of result (omm_host.cpp: Prefill, ArrayAlloc): the pool block has `cap` bytes, the helper
+    // ---- zeroing ahead of a block that then holds ANOTHER size of result (omm_host.cpp: ResultArray): the pool block has `cap` bytes, the helper
     //      threads zero it up to `last` (the previous compressed result) by the plan, and the result -- smaller, equal, or larger up to cap -- is expanded over
     //      it.  The block holds stale non-zero bytes of an earlier bake everywhere; the expansion may leave alone only what zeroed_range() vouches for ----
     int planCases = 0; uint64_t planSkipped = 0;
