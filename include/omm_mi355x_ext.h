@@ -353,6 +353,78 @@ typedef struct ommxMicroMeshDesc {         /* the mesh the result was baked from
 OMM_MI355X_API ommResult ommxExpandMicroNodes(const ommxMicroNode* nodes, uint64_t count, const ommxMicroMeshDesc* mesh /* NULL if outPositions is */,
                                               float* outBarycentrics /* [count][3][2] or NULL */, float* outPositions /* [count][3][3] or NULL */, void* hipStream);
 
+/* ---- a coarser micromap from a finer one: cap a device-resident result's subdivision level ----
+ * ommxCoarsenMicromap    makes a new device-resident result in which no block is finer than maxSubdivisionLevel, from the bits of the source alone:
+ *                        no texture, no UVs, no classification.  For a lower level of detail (distant instances, a cheaper BLAS) or a memory budget
+ *                        tighter than the bake's answer.  `deviceResult` is a HOST struct over DEVICE arrays as for ommxLookupOpacity /
+ *                        ommxDebugGetStatsDevice / ommxExtractMicroGeometry; the source is not modified.  The output is an ordinary
+ *                        ommxDeviceBakeResult: ommxGetDeviceBakeResultDesc reads it, the lookup, resolve, stats and geometry entries accept it,
+ *                        ommxDestroyDeviceBakeResult destroys it; its memory comes from the baker's device pool.  It carries no triangle areas
+ *                        (ommxGetDeviceBakeResultTriangleAreas gives NULL, as for sharded results).  The outputs are a pure function of the
+ *                        inputs: two calls return the same bytes.
+ *   source blocks        entry e = indexBuffer[i] selects the block of primitive i by the rule of ommx_opacity_state.  A special index -1..-4
+ *                        passes through unchanged under every flag.  A primitive is SKIPPED when e < -4, e >= descArrayCount, the level is above
+ *                        12, the format is not OC1_2_State (1) / OC1_4_State (2), or the block does not fit inside arrayDataSize: nothing is read
+ *                        through its descriptor, its output entry is -4 (FullyUnknownOpaque), and it is counted in skippedPrimitives.  Descriptors
+ *                        that no primitive selects are dropped.  Blocks may start at any byte offset; unused bits of a one-byte block are ignored
+ *                        on input and are zero on output.
+ *   the level            a block of level L becomes a block of level T = min(L, maxSubdivisionLevel) of the same format.  The micro-triangles
+ *                        4j..4j+3 of level l + 1 tile micro-triangle j of level l (the bird curve is hierarchical), so output micro-triangle j
+ *                        covers the source micro-triangles [j * 4^(L-T), (j+1) * 4^(L-T)).
+ *   the state, 4-state   with side = s & 1 and unknown = s >> 1 of every covered state s: if the covered states differ in side, the output state is
+ *                        mixedState; otherwise it is side | (any unknown ? 2 : 0).  So {T} -> T, {O} -> O, {T, UT} -> UT, {O, UO} -> UO, anything
+ *                        that holds both sides -> mixedState.  A region is known only if all of it was known: the result is conservative.  The
+ *                        rule is associative: applied level by level it gives the same answer.
+ *   the state, 2-state   all covered states 0 -> 0, all 1 -> 1, otherwise mixedState & 1 (the format cannot express "unknown"; the bake maps
+ *                        unknown states the same way).
+ *   uniform blocks       an output block whose states all equal s is uniform.  Without DisableSpecialIndices it is not emitted and its primitives
+ *                        get the entry -(s + 1); this holds for blocks with L <= T too.
+ *   duplicates           without DisableDuplicateDetection two output blocks are one when level, format and every byte are equal (a 64-bit
+ *                        digest finds the candidates, the bytes confirm).  The representative of a class is its member with the lowest SOURCE
+ *                        descriptor index.  A source descriptor selected by several primitives is always reduced once and yields one block,
+ *                        with or without the flag.
+ *   order, offsets       output descriptors are ordered by block size in bytes descending, then by representative source index ascending; a
+ *                        block's size is max(1, 4^T * bits / 8).  Blocks are packed without gaps from offset 0; sizes are powers of two in
+ *                        descending order, so every block is naturally aligned.  An output larger than a 32-bit descriptor offset can express
+ *                        (possible only with detection disabled and overlapping source descriptors) is FAILURE with a log line.
+ *   index buffer         indexCount entries in the source's indexFormat (8, 16 and 32 bits are accepted, as in the lookup): the special index of
+ *                        a source special, a skipped primitive or a promoted block, otherwise the output descriptor of the block's
+ *                        representative.  The output never has more descriptors than the source, so the entries fit.
+ *   histograms           descArrayHistogram counts output descriptors per (level, format); indexHistogram counts primitives with an entry >= 0
+ *                        per (level, format) of the selected block.  Zero counts are omitted.
+ *   info                 see ommxCoarsenInfo.  With default flags referencedBlocks == descArrayCount + uniformBlocks + duplicateBlocks.  With
+ *                        outResult == NULL the same numbers are computed and no output arrays are allocated or written -- for a budget search:
+ *                        ask for a few levels, then build one.
+ *   stream, memory       the kernels run on `hipStream` (null = the null stream), which the call synchronises before it returns.  Scratch comes
+ *                        from the baker's device pool and is back there when the call returns.  *outResult is written on SUCCESS only.
+ *   result codes         judged before the device is touched, each INVALID_ARGUMENT with a log line of its own: a null baker, deviceResult or
+ *                        desc, outResult and outInfo both null, a baker of unknown type, an unknown indexFormat, a mixedState other than 2 or 3,
+ *                        unknown flag bits, non-zero reserved bytes, null arrays with non-zero counts as in ommxDebugGetStatsDevice.
+ *                        indexCount == 0 -> SUCCESS without a launch: the info is all zeros and *outResult is an empty result that can be
+ *                        destroyed.  Without a usable device, or when device memory runs out -> FAILURE with a log line. */
+typedef enum ommxCoarsenFlags {
+    ommxCoarsenFlags_None                      = 0,
+    ommxCoarsenFlags_DisableSpecialIndices     = 1,  /* uniform blocks stay blocks */
+    ommxCoarsenFlags_DisableDuplicateDetection = 2   /* equal blocks are not merged */
+} ommxCoarsenFlags;
+typedef struct ommxCoarsenDesc {
+    uint32_t maxSubdivisionLevel;  /* no block of the output is finer than this; >= 12: no limit */
+    uint8_t  mixedState;           /* 2 (UnknownTransparent) or 3 (UnknownOpaque): see "the state" */
+    uint8_t  reserved[3];          /* must be 0 */
+    uint32_t flags;                /* ommxCoarsenFlags */
+} ommxCoarsenDesc;
+typedef struct ommxCoarsenInfo {
+    uint64_t arrayDataSize;        /* of the output */
+    uint32_t descArrayCount;       /* of the output */
+    uint32_t referencedBlocks;     /* valid source descriptors that at least one primitive selects */
+    uint32_t coarsenedBlocks;      /* of those: level > maxSubdivisionLevel */
+    uint32_t uniformBlocks;        /* of those: every output state equal (promoted to a special index unless disabled) */
+    uint32_t duplicateBlocks;      /* of those: merged into another block's output */
+    uint32_t skippedPrimitives;
+} ommxCoarsenInfo;
+OMM_MI355X_API ommResult ommxCoarsenMicromap(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxCoarsenDesc* desc,
+                                             ommxDeviceBakeResult* outResult /* NULL: info only */, ommxCoarsenInfo* outInfo /* or NULL */, void* hipStream);
+
 /* ---- an alpha texture from an image that is already in device memory ----
  * ommxCreateTextureDevice  ommCpuCreateTexture for texels that live in HBM: ONE channel of an interleaved (or packed single-channel) image is read where
  *                        it is; nothing is downloaded, restaged or uploaded.  The result is an ordinary ommCpuTexture, byte for byte the texture

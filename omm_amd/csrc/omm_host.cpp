@@ -14,6 +14,7 @@
 #include "stats_kernels.h"
 #include "geometry_kernels.h"
 #include "geometry_cut.h"
+#include "coarsen_kernels.h"
 #include "texture_kernels.h"
 #include "block_kernels.h"
 #include "bc7_kernels.h"
@@ -3064,6 +3065,86 @@ OMM_MI355X_API ommResult ommxExtractMicroGeometry(ommBaker baker, const ommCpuBa
     if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxMicroGeometryDesc was not set");
     if (outCounts == nullptr) return b->log.invalid("[Invalid Arg] - outCounts was not set");
     return guarded(&b->log, [&] { return extract_geometry(*b, *deviceResult, *desc, outputs, outCounts, outSkippedPrimitives, (hipStream_t)hipStream); });
+}
+
+// A device-resident result capped at a subdivision level (include/omm_mi355x_ext.h; kernels in coarsen_kernels.hip): read the index buffer, size the
+// staging arena, reduce and compare, judge the output's size on the host, then allocate the new result's arrays and fill them.
+namespace {
+ommResult coarsen_device(Baker& b, const ommCpuBakeResultDesc& r, const ommxCoarsenDesc& c, ommxDeviceBakeResult* outResult, ommxCoarsenInfo* outInfo, hipStream_t stream)
+{
+    if (r.indexFormat != ommIndexFormat_UINT_8 && r.indexFormat != ommIndexFormat_UINT_16 && r.indexFormat != ommIndexFormat_UINT_32)
+        return b.log.invalid("[Invalid Arg] - deviceResult.indexFormat is not an index format");
+    if (c.mixedState != 2 && c.mixedState != 3) return b.log.invalid("[Invalid Arg] - ommxCoarsenDesc.mixedState must be 2 (UnknownTransparent) or 3 (UnknownOpaque)");
+    if ((c.flags & ~(uint32_t)(ommxCoarsenFlags_DisableSpecialIndices | ommxCoarsenFlags_DisableDuplicateDetection)) != 0) return b.log.invalid("[Invalid Arg] - ommxCoarsenDesc.flags has unknown bits");
+    if (c.reserved[0] || c.reserved[1] || c.reserved[2]) return b.log.invalid("[Invalid Arg] - ommxCoarsenDesc.reserved must be 0");
+    if (r.indexCount && (r.indexBuffer == nullptr || (r.descArrayCount && (r.descArray == nullptr || (r.arrayData == nullptr && r.arrayDataSize)))))
+        return b.log.invalid("[Invalid Arg] - deviceResult has a null array with a non-zero count");
+    ommxCoarsenInfo info; memset(&info, 0, sizeof info);
+    DeviceBakeResult* res = nullptr;
+    if (outResult) {
+        res = b.mem.make<DeviceBakeResult>();
+        if (!res) return b.log.failure("[Failure] - the memory allocator returned null for the coarsened result");
+        res->mem = b.mem; memset(&res->desc, 0, sizeof res->desc);
+        res->R.pool = b.devPool; res->R.numTris = r.indexCount; res->R.indexFormat = r.indexFormat;
+    }
+    // (pooled blocks of a result that is given up go back only when the stream is idle)
+    const auto give_up = [&](ommResult code) { if (res) { (void)hipStreamSynchronize(stream); b.mem.destroy(res); } return code; };
+    uint32_t hist[2 * 2 * kCoarsenLevels]; memset(hist, 0, sizeof hist);
+    if (r.indexCount) {
+        int deviceCount = 0;
+        if (!HIP_OK(hipGetDeviceCount(&deviceCount)) || deviceCount < 1) { (void)hipGetLastError(); return give_up(b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)")); }
+        const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
+        CoarsenArgs a; a.result = r; a.maxLevel = c.maxSubdivisionLevel < kCoarsenLevels - 1u ? c.maxSubdivisionLevel : kCoarsenLevels - 1u; a.mixedState = c.mixedState; a.flags = c.flags;
+        PoolBlock head(b.devPool.get(), coarsen_head_bytes(a)), staging;
+        if (!head.p) return give_up(b.log.failure("[Failure] - out of device memory for the coarsening scratch"));
+        // (after a failed launch the scratch goes back only when nothing can still touch it)
+        const auto failed = [&] { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); return give_up(b.log.failure("[Failure] - the coarsening kernels could not run")); };
+        CoarsenPlan plan;
+        if (coarsen_plan(a, head.p, &plan, stream) != hipSuccess) return failed();
+        if (plan.stagingBytes && !staging.acquire(b.devPool.get(), (size_t)plan.stagingBytes)) return give_up(b.log.failure("[Failure] - out of device memory for the coarsening scratch"));
+        CoarsenCounts n;
+        if (coarsen_reduce(a, head.p, staging.p, plan, &n, stream) != hipSuccess) return failed();
+        if (n.arrayBytes > 0xFFFFFFFFull) return give_up(b.log.failure("[Failure] - the coarsened arrayData would exceed what a 32-bit descriptor offset can express"));
+        info.arrayDataSize = n.arrayBytes; info.descArrayCount = n.descCount; info.referencedBlocks = n.referenced; info.coarsenedBlocks = n.coarsened;
+        info.uniformBlocks = n.uniform; info.duplicateBlocks = n.duplicate; info.skippedPrimitives = plan.skipped;
+        if (res) {
+            DeviceResult& R = res->R;
+            R.numDescs = n.descCount; R.arrayDataSize = n.arrayBytes;
+            if (n.descCount) { R.arrayData = (uint8_t*)R.dev_alloc((size_t)n.arrayBytes); R.descs = (ommCpuOpacityMicromapDesc*)R.dev_alloc(sizeof(ommCpuOpacityMicromapDesc) * (size_t)n.descCount); }
+            R.index = R.dev_alloc((size_t)r.indexCount * (r.indexFormat == ommIndexFormat_UINT_8 ? 1u : r.indexFormat == ommIndexFormat_UINT_16 ? 2u : 4u));
+            if (!R.index || (n.descCount && (!R.arrayData || !R.descs))) return give_up(b.log.failure("[Failure] - out of device memory for the coarsened result"));
+            CoarsenOutputs o; o.arrayData = R.arrayData; o.descs = R.descs; o.index = R.index; o.hist = hist;
+            if (coarsen_emit(a, head.p, staging.p, n, o, stream) != hipSuccess) return failed();
+        }
+    }
+    if (res) {
+        // the histogram lists are built here, not by finish_device_result: a caller's source may hold both formats
+        uint32_t nAH = 0, nIH = 0;
+        for (uint32_t l = 0; l < kCoarsenLevels; ++l)
+            for (uint32_t f = 0; f < 2; ++f) {
+                const uint32_t ah = hist[2 * l + f], ih = hist[2 * kCoarsenLevels + 2 * l + f];
+                if (ah) res->arrayHist[nAH++] = ommCpuOpacityMicromapUsageCount{ ah, (uint16_t)l, (uint16_t)(f + 1) };
+                if (ih) res->indexHist[nIH++] = ommCpuOpacityMicromapUsageCount{ ih, (uint16_t)l, (uint16_t)(f + 1) };
+            }
+        const DeviceResult& R = res->R;
+        fill_result_desc(&res->desc, R.arrayData, R.arrayDataSize, R.descs, R.numDescs, R.index, R.numTris, R.indexFormat, res->arrayHist, nAH, res->indexHist, nIH);
+        *outResult = (ommxDeviceBakeResult)res;
+    }
+    if (outInfo) *outInfo = info;
+    return ommResult_SUCCESS;
+}
+}
+
+OMM_MI355X_API ommResult ommxCoarsenMicromap(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxCoarsenDesc* desc,
+                                             ommxDeviceBakeResult* outResult, ommxCoarsenInfo* outInfo, void* hipStream)
+{
+    if (baker == 0) return ommResult_INVALID_ARGUMENT;
+    if (tag_of(baker) != kCpuBaker && tag_of(baker) != kGpuBaker) return ommResult_INVALID_ARGUMENT;
+    Baker* b = untag<Baker>(baker);
+    if (deviceResult == nullptr) return b->log.invalid("[Invalid Arg] - deviceResult was not set");
+    if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxCoarsenDesc was not set");
+    if (outResult == nullptr && outInfo == nullptr) return b->log.invalid("[Invalid Arg] - neither outResult nor outInfo was set");
+    return guarded(&b->log, [&] { return coarsen_device(*b, *deviceResult, *desc, outResult, outInfo, (hipStream_t)hipStream); });
 }
 
 // Any-hit resolution of hits against a device-resident result (include/omm_mi355x_ext.h; kernels in lookup_kernels.hip).  The desc is checked as
