@@ -425,6 +425,71 @@ typedef struct ommxCoarsenInfo {
 OMM_MI355X_API ommResult ommxCoarsenMicromap(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxCoarsenDesc* desc,
                                              ommxDeviceBakeResult* outResult /* NULL: info only */, ommxCoarsenInfo* outInfo /* or NULL */, void* hipStream);
 
+/* ---- one conservative micromap from several results over the same primitives ----
+ * ommxCombineMicromaps   makes a new device-resident result that is safe wherever EVERY source is: a micro-triangle is known only where all sources
+ *                        know it and agree.  For a BLAS that is built once and used under several alpha tests: the bakes at the lowest and the highest
+ *                        cut-off of an animated alphaCutoff (alpha against a cut-off is monotonic, so what both ends agree on holds in between),
+ *                        bakes of several mips, flipbook frames or material variants on the same triangles, or bakes of the same mesh at different
+ *                        subdivision levels ("level 9 where the texture needs it, the level-7 answer elsewhere").  Nothing is downloaded: it is a
+ *                        streaming pass over bits that are already in device memory.
+ *   sources              resultCount is 1..OMMX_COMBINE_MAX_SOURCES.  Each element of deviceResults is a HOST struct over DEVICE arrays as for
+ *                        ommxCoarsenMicromap.  All sources have the same indexCount: they describe the same primitives, and primitive i is the same
+ *                        triangle in each.  Index formats (8, 16 and 32 bits) may differ between sources.  The same source may be given more than
+ *                        once.  No source is modified.
+ *   tuple of primitive i (e_0 .. e_{K-1}) with e_k = source k's index entry.  An entry -1..-4 is the uniform state -(e + 1) at level 0.  An entry
+ *                        >= 0 selects a block by the bounds rule of omm_mi355x_lookup.h.  If any e_k fails that rule -- an entry below -4, an entry at
+ *                        or beyond descArrayCount, a level above 12, a format other than 1 or 2, a block outside arrayDataSize -- the primitive is
+ *                        SKIPPED: nothing is read through any of its descriptors, its output entry is -4, and it counts once in skippedPrimitives.
+ *   the level            T is the maximum level over the blocks of the tuple.  Output micro-triangle j of level T reads micro-triangle
+ *                        j >> 2(T - L_k) of a source block of level L_k (the bird curve is hierarchical), and the one state of a special entry.
+ *   the state            source states are 0..3; a 2-state block gives 0 or 1.  With side = s & 1 over the K states: if the sides differ,
+ *                        r = mixedState; otherwise r = side | (any s >> 1 ? 2 : 0).  An output of format 2 stores r; an output of format 1 stores
+ *                        r & 1, which is ommx_force_2state(r).  The rule is symmetric and associative (the join of ommxCoarsenMicromap's rule).
+ *   only special entries no block is made: the output entry is -(r + 1) for format 2 and -((r & 1) + 1) for format 1.
+ *   uniform blocks       an output block whose states all equal s is always promoted: it is not emitted and its primitives get the entry -(s + 1).
+ *   duplicates           two output blocks are one when their level and every byte are equal (a 64-bit digest finds the candidates, the bytes
+ *                        confirm; two blocks that collide in the digest without being equal are both kept -- a loss of compression, never a wrong
+ *                        state).  The representative of a class is the member whose lowest primitive index is lowest.
+ *   order, offsets       output descriptors are ordered by block size in bytes descending, then by the representative's lowest primitive index
+ *                        ascending.  Blocks are packed from offset 0 without gaps; a block's size is max(1, 4^T * bits / 8), and the unused bits of a
+ *                        one-byte block are zero.  An arrayDataSize above what a 32-bit descriptor offset can express is FAILURE with a log line.
+ *   index buffer         indexCount entries, always ommIndexFormat_UINT_32: the output can have more descriptors than any one source.
+ *   histograms           as in ommxCoarsenMicromap: descArrayHistogram counts output descriptors per (level, format), indexHistogram counts
+ *                        primitives with an entry >= 0 per (level, format) of the selected block.  Zero counts are omitted.
+ *   purity               the output is a pure function of the inputs: two calls return the same bytes, and any permutation of the sources returns
+ *                        the same bytes.
+ *   outResult            an ordinary ommxDeviceBakeResult from the baker's device pool.  It carries no triangle areas and is accepted by the
+ *                        lookup, resolve, stats, geometry and coarsen entries and by ommxCombineMicromaps itself.
+ *   info                 see ommxCombineInfo.  With outResult == NULL the same info is computed and no output arrays are allocated.
+ *                        combinedTuples == descArrayCount + uniformBlocks + duplicateBlocks.
+ *   stream, memory       the kernels run on `hipStream` (null = the null stream), which the call synchronises before it returns.  Scratch comes
+ *                        from the baker's device pool and is back there when the call returns.  *outResult is written on SUCCESS only.
+ *   result codes         judged before the device is touched, each INVALID_ARGUMENT with a log line of its own: a null baker, a baker of unknown
+ *                        type, null deviceResults, null desc, resultCount 0 or above 16, a null element of deviceResults, outResult and outInfo
+ *                        both null, a format other than 1 or 2, a mixedState other than 2 or 3, non-zero flags, non-zero reserved bytes, an unknown
+ *                        indexFormat in any source, indexCount values that differ between sources, null arrays with non-zero counts as in
+ *                        ommxCoarsenMicromap.  indexCount == 0 -> SUCCESS without a launch: the info is all zeros and *outResult is an empty result
+ *                        that can be destroyed.  Without a usable device, or when device memory runs out -> FAILURE with a log line. */
+#define OMMX_COMBINE_MAX_SOURCES 16
+typedef struct ommxCombineDesc {
+    uint32_t format;        /* ommFormat_OC1_2_State (1) or ommFormat_OC1_4_State (2): the format of EVERY output block */
+    uint8_t  mixedState;    /* 2 (UnknownTransparent) or 3 (UnknownOpaque), as ommxCoarsenDesc::mixedState */
+    uint8_t  reserved[3];   /* must be 0 */
+    uint32_t flags;         /* must be 0 (room to grow) */
+} ommxCombineDesc;
+typedef struct ommxCombineInfo {
+    uint64_t arrayDataSize;      /* of the output */
+    uint32_t descArrayCount;     /* of the output */
+    uint32_t combinedTuples;     /* distinct tuples of source entries with at least one block among them (each is joined once) */
+    uint32_t refinedTuples;      /* of those: at least one source block is coarser than the output block */
+    uint32_t uniformBlocks;      /* of those: every output state equal -> special index */
+    uint32_t duplicateBlocks;    /* of those: merged into another tuple's output */
+    uint32_t skippedPrimitives;
+} ommxCombineInfo;
+OMM_MI355X_API ommResult ommxCombineMicromaps(ommBaker baker, const ommCpuBakeResultDesc* const* deviceResults, uint32_t resultCount,
+                                              const ommxCombineDesc* desc, ommxDeviceBakeResult* outResult /* NULL: info only */,
+                                              ommxCombineInfo* outInfo /* or NULL */, void* hipStream);
+
 /* ---- an alpha texture from an image that is already in device memory ----
  * ommxCreateTextureDevice  ommCpuCreateTexture for texels that live in HBM: ONE channel of an interleaved (or packed single-channel) image is read where
  *                        it is; nothing is downloaded, restaged or uploaded.  The result is an ordinary ommCpuTexture, byte for byte the texture

@@ -15,6 +15,7 @@
 #include "geometry_kernels.h"
 #include "geometry_cut.h"
 #include "coarsen_kernels.h"
+#include "combine_kernels.h"
 #include "texture_kernels.h"
 #include "block_kernels.h"
 #include "bc7_kernels.h"
@@ -3145,6 +3146,112 @@ OMM_MI355X_API ommResult ommxCoarsenMicromap(ommBaker baker, const ommCpuBakeRes
     if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxCoarsenDesc was not set");
     if (outResult == nullptr && outInfo == nullptr) return b->log.invalid("[Invalid Arg] - neither outResult nor outInfo was set");
     return guarded(&b->log, [&] { return coarsen_device(*b, *deviceResult, *desc, outResult, outInfo, (hipStream_t)hipStream); });
+}
+
+// One conservative result from several device-resident results over the same primitives (include/omm_mi355x_ext.h; kernels in combine_kernels.hip): find
+// the distinct tuples of entries, size the per-tuple scratch and the staging arena, join and compare, judge the output's size on the host, then allocate
+// the new result's arrays and fill them.
+namespace {
+ommResult combine_device(Baker& b, const ommCpuBakeResultDesc* const* results, uint32_t count, const ommxCombineDesc& c, ommxDeviceBakeResult* outResult,
+                         ommxCombineInfo* outInfo, hipStream_t stream)
+{
+    if (c.format != (uint32_t)ommFormat_OC1_2_State && c.format != (uint32_t)ommFormat_OC1_4_State) return b.log.invalid("[Invalid Arg] - ommxCombineDesc.format must be OC1_2_State (1) or OC1_4_State (2)");
+    if (c.mixedState != 2 && c.mixedState != 3) return b.log.invalid("[Invalid Arg] - ommxCombineDesc.mixedState must be 2 (UnknownTransparent) or 3 (UnknownOpaque)");
+    if (c.flags != 0) return b.log.invalid("[Invalid Arg] - ommxCombineDesc.flags must be 0");
+    if (c.reserved[0] || c.reserved[1] || c.reserved[2]) return b.log.invalid("[Invalid Arg] - ommxCombineDesc.reserved must be 0");
+    for (uint32_t k = 0; k < count; ++k)
+        if (results[k]->indexFormat != ommIndexFormat_UINT_8 && results[k]->indexFormat != ommIndexFormat_UINT_16 && results[k]->indexFormat != ommIndexFormat_UINT_32)
+            return b.log.invalid("[Invalid Arg] - a source's indexFormat is not an index format");
+    const uint32_t indexCount = results[0]->indexCount;
+    for (uint32_t k = 1; k < count; ++k)
+        if (results[k]->indexCount != indexCount) return b.log.invalid("[Invalid Arg] - the sources' indexCount values differ: they must describe the same primitives");
+    for (uint32_t k = 0; k < count; ++k) {
+        const ommCpuBakeResultDesc& r = *results[k];
+        if (r.indexCount && (r.indexBuffer == nullptr || (r.descArrayCount && (r.descArray == nullptr || (r.arrayData == nullptr && r.arrayDataSize)))))
+            return b.log.invalid("[Invalid Arg] - a source has a null array with a non-zero count");
+    }
+    ommxCombineInfo info; memset(&info, 0, sizeof info);
+    DeviceBakeResult* res = nullptr;
+    if (outResult) {
+        res = b.mem.make<DeviceBakeResult>();
+        if (!res) return b.log.failure("[Failure] - the memory allocator returned null for the combined result");
+        res->mem = b.mem; memset(&res->desc, 0, sizeof res->desc);
+        res->R.pool = b.devPool; res->R.numTris = indexCount; res->R.indexFormat = ommIndexFormat_UINT_32;
+    }
+    // (pooled blocks of a result that is given up go back only when the stream is idle)
+    const auto give_up = [&](ommResult code) { if (res) { (void)hipStreamSynchronize(stream); b.mem.destroy(res); } return code; };
+    uint32_t hist[2 * 2 * kCoarsenLevels]; memset(hist, 0, sizeof hist);
+    if (indexCount) {
+        int deviceCount = 0;
+        if (!HIP_OK(hipGetDeviceCount(&deviceCount)) || deviceCount < 1) { (void)hipGetLastError(); return give_up(b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)")); }
+        const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
+        CombineArgs a; memset(&a, 0, sizeof a);
+        for (uint32_t k = 0; k < count; ++k) {
+            const ommCpuBakeResultDesc& r = *results[k];
+            CombineSource& s = a.source[k];
+            s.arrayData = (const uint8_t*)r.arrayData; s.descs = r.descArray; s.index = r.indexBuffer;
+            s.arrayDataSize = r.arrayDataSize; s.descCount = r.descArrayCount; s.indexFormat = (int32_t)r.indexFormat;
+        }
+        a.sourceCount = count; a.indexCount = indexCount; a.format = c.format; a.mixedState = c.mixedState;
+        const auto no_memory = [&] { return give_up(b.log.failure("[Failure] - out of device memory for the combine scratch")); };
+        PoolBlock head(b.devPool.get(), combine_head_bytes(a)), perTuple, staging;
+        if (!head.p) return no_memory();
+        // (after a failed launch the scratch goes back only when nothing can still touch it)
+        const auto failed = [&] { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); return give_up(b.log.failure("[Failure] - the combine kernels could not run")); };
+        CombineTuples t;
+        if (combine_tuples(a, head.p, &t, stream) != hipSuccess) return failed();
+        info.combinedTuples = t.tuples; info.skippedPrimitives = t.skipped;
+        CombineCounts n; memset(&n, 0, sizeof n);
+        if (t.tuples) {
+            if (!perTuple.acquire(b.devPool.get(), combine_tuple_bytes(a, t.tuples))) return no_memory();
+            CombinePlan plan;
+            if (combine_plan(a, head.p, perTuple.p, t, &plan, stream) != hipSuccess) return failed();
+            if (!staging.acquire(b.devPool.get(), (size_t)plan.stagingBytes)) return no_memory();
+            if (combine_join(a, head.p, perTuple.p, staging.p, t, plan, &n, stream) != hipSuccess) return failed();
+            if (n.arrayBytes > 0xFFFFFFFFull) return give_up(b.log.failure("[Failure] - the combined arrayData would exceed what a 32-bit descriptor offset can express"));
+            info.refinedTuples = plan.refined; info.uniformBlocks = n.uniform; info.duplicateBlocks = n.duplicate;
+        }
+        info.arrayDataSize = n.arrayBytes; info.descArrayCount = n.descCount;
+        if (res) {
+            DeviceResult& R = res->R;
+            R.numDescs = n.descCount; R.arrayDataSize = n.arrayBytes;
+            if (n.descCount) { R.arrayData = (uint8_t*)R.dev_alloc((size_t)n.arrayBytes); R.descs = (ommCpuOpacityMicromapDesc*)R.dev_alloc(sizeof(ommCpuOpacityMicromapDesc) * (size_t)n.descCount); }
+            R.index = R.dev_alloc(4u * (size_t)indexCount);
+            if (!R.index || (n.descCount && (!R.arrayData || !R.descs))) return give_up(b.log.failure("[Failure] - out of device memory for the combined result"));
+            CombineOutputs o; o.arrayData = R.arrayData; o.descs = R.descs; o.index = (int32_t*)R.index; o.hist = hist;
+            if (combine_emit(a, head.p, perTuple.p, staging.p, t, n, o, stream) != hipSuccess) return failed();
+        }
+    }
+    if (res) {
+        uint32_t nAH = 0, nIH = 0;
+        for (uint32_t l = 0; l < kCoarsenLevels; ++l)
+            for (uint32_t f = 0; f < 2; ++f) {
+                const uint32_t ah = hist[2 * l + f], ih = hist[2 * kCoarsenLevels + 2 * l + f];
+                if (ah) res->arrayHist[nAH++] = ommCpuOpacityMicromapUsageCount{ ah, (uint16_t)l, (uint16_t)(f + 1) };
+                if (ih) res->indexHist[nIH++] = ommCpuOpacityMicromapUsageCount{ ih, (uint16_t)l, (uint16_t)(f + 1) };
+            }
+        const DeviceResult& R = res->R;
+        fill_result_desc(&res->desc, R.arrayData, R.arrayDataSize, R.descs, R.numDescs, R.index, R.numTris, R.indexFormat, res->arrayHist, nAH, res->indexHist, nIH);
+        *outResult = (ommxDeviceBakeResult)res;
+    }
+    if (outInfo) *outInfo = info;
+    return ommResult_SUCCESS;
+}
+}
+
+OMM_MI355X_API ommResult ommxCombineMicromaps(ommBaker baker, const ommCpuBakeResultDesc* const* deviceResults, uint32_t resultCount, const ommxCombineDesc* desc,
+                                              ommxDeviceBakeResult* outResult, ommxCombineInfo* outInfo, void* hipStream)
+{
+    if (baker == 0) return ommResult_INVALID_ARGUMENT;
+    if (tag_of(baker) != kCpuBaker && tag_of(baker) != kGpuBaker) return ommResult_INVALID_ARGUMENT;
+    Baker* b = untag<Baker>(baker);
+    if (deviceResults == nullptr) return b->log.invalid("[Invalid Arg] - deviceResults was not set");
+    if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxCombineDesc was not set");
+    if (resultCount == 0 || resultCount > OMMX_COMBINE_MAX_SOURCES) return b->log.invalid("[Invalid Arg] - resultCount must be 1..OMMX_COMBINE_MAX_SOURCES (16)");
+    for (uint32_t k = 0; k < resultCount; ++k)
+        if (deviceResults[k] == nullptr) return b->log.invalid("[Invalid Arg] - an element of deviceResults was not set");
+    if (outResult == nullptr && outInfo == nullptr) return b->log.invalid("[Invalid Arg] - neither outResult nor outInfo was set");
+    return guarded(&b->log, [&] { return combine_device(*b, deviceResults, resultCount, *desc, outResult, outInfo, (hipStream_t)hipStream); });
 }
 
 // Any-hit resolution of hits against a device-resident result (include/omm_mi355x_ext.h; kernels in lookup_kernels.hip).  The desc is checked as
