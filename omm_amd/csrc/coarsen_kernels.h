@@ -4,11 +4,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/omm_mi355x_ext.h"
+#include "rebuild_kernels.h"
 
 namespace ommx {
-
-constexpr uint32_t kCoarsenLevels = 13u;        // 0..12
-constexpr uint32_t kCoarsenSizeClasses = 23u;   // log2 of a block's size in bytes: 1 byte .. 4 MiB
 
 struct CoarsenArgs {
     ommCpuBakeResultDesc result;   // host struct, arrays in device memory; indexFormat already checked
@@ -19,13 +17,9 @@ struct CoarsenArgs {
 struct CoarsenPlan {               // after the index buffer has been read
     uint64_t stagingBytes;         // the arena the reduced blocks are written to before their order is known
     uint32_t skipped, deepBlocks;  // skipped primitives; blocks that need a second reduction pass
+    uint32_t referenced, coarsened;   // selected blocks; those above maxLevel
 };
-struct CoarsenCounts {             // after reduction and duplicate search
-    uint32_t referenced, coarsened, uniform, duplicate;
-    uint32_t classCount[kCoarsenSizeClasses];   // output blocks per size class
-    uint32_t descCount; uint64_t arrayBytes;    // of the output (sums over the classes)
-};
-struct CoarsenOutputs {            // device memory of the new result; hist: host memory, [2][kCoarsenLevels][2] = array | index, level, format - 1
+struct CoarsenOutputs {            // device memory of the new result; hist: host memory, [2][kRebuildLevels][2] = array | index, level, format - 1
     uint8_t* arrayData; ommCpuOpacityMicromapDesc* descs; void* index;
     uint32_t* hist;
 };
@@ -33,7 +27,7 @@ struct CoarsenOutputs {            // device memory of the new result; hist: hos
 size_t coarsen_head_bytes(const CoarsenArgs& a);
 // each: every launch on `stream`, the answer copied to the host, the stream synchronised.  indexCount must be > 0.
 hipError_t coarsen_plan(const CoarsenArgs& a, void* head, CoarsenPlan* out, hipStream_t stream);
-hipError_t coarsen_reduce(const CoarsenArgs& a, void* head, void* staging, const CoarsenPlan& plan, CoarsenCounts* out, hipStream_t stream);
-hipError_t coarsen_emit(const CoarsenArgs& a, void* head, const void* staging, const CoarsenCounts& counts, const CoarsenOutputs& o, hipStream_t stream);
+hipError_t coarsen_reduce(const CoarsenArgs& a, void* head, void* staging, const CoarsenPlan& plan, RebuildCounts* out, hipStream_t stream);
+hipError_t coarsen_emit(const CoarsenArgs& a, void* head, const void* staging, const RebuildCounts& counts, const CoarsenOutputs& o, hipStream_t stream);
 
 } // namespace ommx

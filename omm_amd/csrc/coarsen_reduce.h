@@ -10,6 +10,7 @@
 // The rule is associative, so any split of a deep reduction into steps of one to three levels gives the same bits.
 #pragma once
 #include <stdint.h>
+#include "result_block.h"
 
 #ifdef __HIPCC__
 #define OMMX_COARSEN_FN __host__ __device__ __forceinline__
@@ -18,8 +19,6 @@
 #endif
 
 namespace ommx {
-
-constexpr uint32_t kCoarsenMaxLevel = 12u;   // what the bounds rule of include/omm_mi355x_lookup.h admits
 
 struct CoarsenPlanes { uint64_t lo, hi; };   // field f is bit f of both
 
@@ -117,8 +116,5 @@ OMMX_COARSEN_FN uint32_t coarsen_word_uniform(uint64_t w, uint32_t validBits, ui
     const uint64_t lo = 0x5555555555555555ull, hi = 0xaaaaaaaaaaaaaaaaull;
     return (((w & valid) == 0ull) ? 1u : 0u) | ((((w ^ lo) & valid) == 0ull) ? 2u : 0u) | ((((w ^ hi) & valid) == 0ull) ? 4u : 0u) | (((~w & valid) == 0ull) ? 8u : 0u);
 }
-
-// bytes a block of `level` <= 12 and fieldBits 1 or 2 occupies
-OMMX_COARSEN_FN uint64_t coarsen_block_bytes(uint32_t level, uint32_t fieldBits) { return (((uint64_t)fieldBits << (2u * level)) + 7u) >> 3; }
 
 } // namespace ommx

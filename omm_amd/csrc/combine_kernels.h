@@ -4,7 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/omm_mi355x_ext.h"
-#include "coarsen_kernels.h"
+#include "rebuild_kernels.h"
 
 namespace ommx {
 
@@ -27,12 +27,7 @@ struct CombinePlan {               // after the tuples have been listed
     uint64_t units;                // work units of the streaming pass
     uint32_t refined;              // tuples with a block coarser than their output
 };
-struct CombineCounts {             // after the join and the duplicate search
-    uint32_t uniform, duplicate;
-    uint32_t classCount[kCoarsenSizeClasses];   // output blocks per size class
-    uint32_t descCount; uint64_t arrayBytes;    // of the output (sums over the classes)
-};
-struct CombineOutputs {            // device memory of the new result; hist: host memory, [2][kCoarsenLevels][2] = array | index, level, format - 1
+struct CombineOutputs {            // device memory of the new result; hist: host memory, [2][kRebuildLevels][2] = array | index, level, format - 1
     uint8_t* arrayData; ommCpuOpacityMicromapDesc* descs; int32_t* index;
     uint32_t* hist;
 };
@@ -42,10 +37,9 @@ size_t combine_tuple_bytes(const CombineArgs& a, uint32_t tuples);   // scratch 
 // each: every launch on `stream`, the answer copied to the host, the stream synchronised
 hipError_t combine_tuples(const CombineArgs& a, void* head, CombineTuples* out, hipStream_t stream);
 hipError_t combine_plan(const CombineArgs& a, void* head, void* perTuple, const CombineTuples& t, CombinePlan* out, hipStream_t stream);
-hipError_t combine_join(const CombineArgs& a, void* head, void* perTuple, void* staging, const CombineTuples& t, const CombinePlan& plan, CombineCounts* out,
-                        hipStream_t stream);
+hipError_t combine_join(const CombineArgs& a, void* perTuple, void* staging, const CombineTuples& t, const CombinePlan& plan, RebuildCounts* out, hipStream_t stream);
 // perTuple and staging may be null when t.tuples == 0
-hipError_t combine_emit(const CombineArgs& a, void* head, void* perTuple, const void* staging, const CombineTuples& t, const CombineCounts& counts,
+hipError_t combine_emit(const CombineArgs& a, void* head, void* perTuple, const void* staging, const CombineTuples& t, const RebuildCounts& counts,
                         const CombineOutputs& o, hipStream_t stream);
 
 } // namespace ommx

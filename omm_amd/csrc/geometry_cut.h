@@ -9,6 +9,7 @@
 // and the words of tile summaries above that.
 #pragma once
 #include <stdint.h>
+#include "result_block.h"
 
 #ifdef __HIPCC__
 #define OMMX_GEO_FN __host__ __device__ __forceinline__
@@ -20,7 +21,6 @@
 
 namespace ommx {
 
-constexpr uint32_t kGeoMaxLevel = 12u;    // what the bounds rule of include/omm_mi355x_lookup.h admits
 constexpr uint32_t kGeoDrop = 4u;        // the class of OMMX_GEOMETRY_DROP (classes 0..3 are the output lists)
 constexpr uint32_t kGeoNoClass = 0xFFu;  // a node whose children differ
 

@@ -9,6 +9,8 @@
 #include <rocprim/rocprim.hpp>
 #include "geometry_kernels.h"
 #include "geometry_cut.h"
+#include "result_read.h"
+#include "bake_host.h"   // pad256
 #include "wave_search.h"
 #include "../../include/omm_mi355x_lookup.h"
 
@@ -21,17 +23,8 @@ constexpr uint32_t kGeoRun = 4;                  // consecutive tiles per wave a
 constexpr uint32_t kGeoTileLevels = 6;           // a tile is 4^6 micro-triangles: 64 lanes x 64
 constexpr uint32_t kGeoAncestor = 0x80000000u;   // tileAnc: this bit | list << 28 | node
 
-static inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 typedef uint32_t GeoVec __attribute__((vector_size(16), may_alias));
 typedef uint64_t GeoWord __attribute__((may_alias));
-
-__device__ __forceinline__ int32_t geo_index_entry(const void* index, int format, uint64_t i)
-{
-    if (format == ommIndexFormat_UINT_8) return ((const int8_t*)index)[i];
-    if (format == ommIndexFormat_UINT_16) return ((const int16_t*)index)[i];
-    return ((const int32_t*)index)[i];
-}
 
 __device__ __forceinline__ unsigned long long shfl_up_ull(unsigned long long v, uint32_t d)
 {
@@ -133,10 +126,8 @@ __global__ __launch_bounds__(kGeoBlock) void geo_prepare(ommCpuBakeResultDesc r,
     unsigned long long tiles = 0ull;
     if (d < r.descArrayCount) {
         const ommCpuOpacityMicromapDesc desc = r.descArray[d];
-        const uint32_t level = desc.subdivisionLevel, bits = desc.format;
-        if (level <= OMMX_LOOKUP_MAX_LEVEL && (bits == 1u || bits == 2u) &&
-            (uint64_t)desc.offset + ((((uint64_t)bits << (2u * level)) + 7u) >> 3) <= (uint64_t)r.arrayDataSize)
-            tiles = level > kGeoTileLevels ? 1ull << (2u * (level - kGeoTileLevels)) : 1ull;
+        const uint32_t level = desc.subdivisionLevel;
+        if (desc_ok(desc, r.arrayDataSize)) tiles = level > kGeoTileLevels ? 1ull << (2u * (level - kGeoTileLevels)) : 1ull;
     }
     tileStart[d] = tiles;
 }
@@ -249,7 +240,7 @@ __global__ __launch_bounds__(kGeoBlock) void geo_primitives(GeoArgs P, const uns
     unsigned long long tiles = 0ull;
     bool skipped = false;
     if (i < T) {
-        const int32_t e = geo_index_entry(P.result.indexBuffer, (int)P.result.indexFormat, i);
+        const int32_t e = index_entry(P.result.indexBuffer, (int)P.result.indexFormat, i);
         if (e < 0) {
             if (e >= -4) {
                 const uint32_t cl = class_of_state(P, (uint32_t)(-(e + 1)));
@@ -289,7 +280,7 @@ __global__ __launch_bounds__(kGeoBlock) void geo_emit_specials(GeoArgs P, const 
 {
     const uint64_t T = P.result.indexCount, stride = (uint64_t)gridDim.x * kGeoBlock;
     for (uint64_t i = (uint64_t)blockIdx.x * kGeoBlock + threadIdx.x; i < T; i += stride) {
-        const int32_t e = geo_index_entry(P.result.indexBuffer, (int)P.result.indexFormat, i);
+        const int32_t e = index_entry(P.result.indexBuffer, (int)P.result.indexFormat, i);
         if (e >= 0 || e < -4) continue;
         const uint32_t cl = class_of_state(P, (uint32_t)(-(e + 1)));
         #pragma unroll
@@ -312,7 +303,7 @@ __global__ __launch_bounds__(kGeoBlock) void geo_emit_tiles(GeoArgs P, const uns
     for (unsigned long long w = w0, end = 0ull, first = 0ull, firstTile = 0ull; w < w0 + kGeoRun && w < total; ++w) {
         if (w >= end) {
             prim = owner_of_segment(primTileStart, (uint32_t)T, w); first = primTileStart[prim]; end = primTileStart[prim + 1];
-            d = (uint32_t)geo_index_entry(P.result.indexBuffer, (int)P.result.indexFormat, prim);   // (has tiles: a block that passed the bounds rule)
+            d = (uint32_t)index_entry(P.result.indexBuffer, (int)P.result.indexFormat, prim);   // (has tiles: a block that passed the bounds rule)
             firstTile = tileStart[d];
         }
         const uint32_t tib = (uint32_t)(w - first);

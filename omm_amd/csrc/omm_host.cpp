@@ -1228,6 +1228,64 @@ void finish_device_result(DeviceBakeResult* res)
     fill_result_desc(&res->desc, R.arrayData, R.arrayDataSize, R.descs, R.numDescs, R.index, R.numTris, R.indexFormat, res->arrayHist, nAH, res->indexHist, nIH);
 }
 
+// ---- the entries that take device-resident results: what a caller's result must be; and, for ommxCoarsenMicromap and ommxCombineMicromaps, the new handle ----
+bool is_index_format(ommIndexFormat f) { return f == ommIndexFormat_UINT_8 || f == ommIndexFormat_UINT_16 || f == ommIndexFormat_UINT_32; }
+bool has_null_array(const ommCpuBakeResultDesc& r)
+{
+    return r.indexCount && (r.indexBuffer == nullptr || (r.descArrayCount && (r.descArray == nullptr || (r.arrayData == nullptr && r.arrayDataSize))));
+}
+bool usable_device()
+{
+    int deviceCount = 0;
+    if (HIP_OK(hipGetDeviceCount(&deviceCount)) && deviceCount >= 1) return true;
+    (void)hipGetLastError();
+    return false;
+}
+struct DerivedResult {
+    Baker& b; hipStream_t stream; const char* noun;   // noun: the new result in a message ("coarsened", "combined")
+    DeviceBakeResult* res = nullptr;                  // stays null when the caller wants the info only
+    uint32_t hist[2 * kRebuildHist];                  // array | index by (level, format - 1): the operation's last stage fills it
+    DerivedResult(Baker& b_, hipStream_t stream_, const char* noun_) : b(b_), stream(stream_), noun(noun_) { memset(hist, 0, sizeof hist); }
+    ommResult failure(const char* format) { char buf[160]; snprintf(buf, sizeof buf, format, noun); return b.log.failure(buf); }
+    ommResult create(uint32_t numTris, ommIndexFormat indexFormat)
+    {
+        res = b.mem.make<DeviceBakeResult>();
+        if (!res) return failure("[Failure] - the memory allocator returned null for the %s result");
+        res->mem = b.mem; memset(&res->desc, 0, sizeof res->desc);
+        res->R.pool = b.devPool; res->R.numTris = numTris; res->R.indexFormat = indexFormat;
+        return ommResult_SUCCESS;
+    }
+    // (pooled blocks of a result that is given up go back only when the stream is idle)
+    ommResult give_up(ommResult code) { if (res) { (void)hipStreamSynchronize(stream); b.mem.destroy(res); res = nullptr; } return code; }
+    // judges the output's size; with a handle, allocates its three arrays
+    ommResult allocate(const RebuildCounts& n)
+    {
+        if (n.arrayBytes > 0xFFFFFFFFull) return give_up(failure("[Failure] - the %s arrayData would exceed what a 32-bit descriptor offset can express"));
+        if (!res) return ommResult_SUCCESS;
+        DeviceResult& R = res->R;
+        R.numDescs = n.descCount; R.arrayDataSize = n.arrayBytes;
+        if (n.descCount) { R.arrayData = (uint8_t*)R.dev_alloc((size_t)n.arrayBytes); R.descs = (ommCpuOpacityMicromapDesc*)R.dev_alloc(sizeof(ommCpuOpacityMicromapDesc) * (size_t)n.descCount); }
+        R.index = R.dev_alloc((size_t)R.numTris * (R.indexFormat == ommIndexFormat_UINT_8 ? 1u : R.indexFormat == ommIndexFormat_UINT_16 ? 2u : 4u));
+        if (!R.index || (n.descCount && (!R.arrayData || !R.descs))) return give_up(failure("[Failure] - out of device memory for the %s result"));
+        return ommResult_SUCCESS;
+    }
+    // the histogram lists are built here, not by finish_device_result: a caller's source may hold both formats
+    void finish(ommxDeviceBakeResult* outResult)
+    {
+        if (!res) return;
+        uint32_t nAH = 0, nIH = 0;
+        for (uint32_t l = 0; l < kRebuildLevels; ++l)
+            for (uint32_t f = 0; f < 2; ++f) {
+                const uint32_t ah = hist[2 * l + f], ih = hist[kRebuildHist + 2 * l + f];
+                if (ah) res->arrayHist[nAH++] = ommCpuOpacityMicromapUsageCount{ ah, (uint16_t)l, (uint16_t)(f + 1) };
+                if (ih) res->indexHist[nIH++] = ommCpuOpacityMicromapUsageCount{ ih, (uint16_t)l, (uint16_t)(f + 1) };
+            }
+        const DeviceResult& R = res->R;
+        fill_result_desc(&res->desc, R.arrayData, R.arrayDataSize, R.descs, R.numDescs, R.index, R.numTris, R.indexFormat, res->arrayHist, nAH, res->indexHist, nIH);
+        *outResult = (ommxDeviceBakeResult)res;
+    }
+};
+
 // result of the serial host tail -> device-resident result (ommxBakeDevice / ommxShardedBakeRccl with the opt-in lossy reducers)
 ommResult upload_host_tail(Baker& b, const HostTailResult& hres, ommIndexFormat ifmt, uint32_t T, int bits, hipStream_t stream, DeviceBakeResult* res)
 {
@@ -2962,14 +3020,14 @@ namespace {
 ommResult stats_device(Baker& b, const ommCpuBakeResultDesc& r, const float* areas, const ommxDeviceStatsOutputs* outputs, ommDebugStats* out,
                        uint32_t* outSkipped, hipStream_t stream)
 {
-    if (r.indexFormat != ommIndexFormat_UINT_8 && r.indexFormat != ommIndexFormat_UINT_16 && r.indexFormat != ommIndexFormat_UINT_32) return ommResult_INVALID_ARGUMENT;
+    if (!is_index_format(r.indexFormat)) return ommResult_INVALID_ARGUMENT;
     ommDebugStats st; memset(&st, 0, sizeof st);
     if (r.indexCount == 0) {   // nothing to launch; the host's 0 / 0 where areas were handed in
         if (areas) { const float zero = 0.f; st.knownAreaMetric = zero / zero; }
         *out = st; if (outSkipped) *outSkipped = 0;
         return ommResult_SUCCESS;
     }
-    if (r.indexBuffer == nullptr || (r.descArrayCount && (r.descArray == nullptr || (r.arrayData == nullptr && r.arrayDataSize)))) return ommResult_INVALID_ARGUMENT;
+    if (has_null_array(r)) return ommResult_INVALID_ARGUMENT;
     StatsArgs a; a.result = r; a.areas = areas;
     a.stateCounts = outputs ? outputs->stateCounts : nullptr; a.referenceCounts = outputs ? outputs->referenceCounts : nullptr;
     a.knownFraction = outputs ? outputs->knownFraction : nullptr;
@@ -3012,8 +3070,7 @@ namespace {
 ommResult extract_geometry(Baker& b, const ommCpuBakeResultDesc& r, const ommxMicroGeometryDesc& g, const ommxMicroGeometryOutputs* outputs, uint64_t outCounts[4],
                            uint32_t* outSkipped, hipStream_t stream)
 {
-    if (r.indexFormat != ommIndexFormat_UINT_8 && r.indexFormat != ommIndexFormat_UINT_16 && r.indexFormat != ommIndexFormat_UINT_32)
-        return b.log.invalid("[Invalid Arg] - deviceResult.indexFormat is not an index format");
+    if (!is_index_format(r.indexFormat)) return b.log.invalid("[Invalid Arg] - deviceResult.indexFormat is not an index format");
     GeoArgs a; memset(&a, 0, sizeof a);
     for (int s = 0; s < 5; ++s) {
         const uint8_t v = s < 4 ? g.listOfState[s] : g.mixedList;
@@ -3021,14 +3078,12 @@ ommResult extract_geometry(Baker& b, const ommCpuBakeResultDesc& r, const ommxMi
         (s < 4 ? a.cls[s] : a.mixed) = v == OMMX_GEOMETRY_DROP ? (uint8_t)kGeoDrop : v;
     }
     if (g.reserved[0] || g.reserved[1] || g.reserved[2]) return b.log.invalid("[Invalid Arg] - ommxMicroGeometryDesc.reserved must be 0");
-    a.result = r; a.emitLevel = g.maxEmitLevel < kGeoMaxLevel ? g.maxEmitLevel : kGeoMaxLevel;
+    a.result = r; a.emitLevel = g.maxEmitLevel < kResultMaxLevel ? g.maxEmitLevel : kResultMaxLevel;
     for (int k = 0; k < 4; ++k) outCounts[k] = 0;
     if (outSkipped) *outSkipped = 0;
     if (r.indexCount == 0) return ommResult_SUCCESS;   // nothing to launch
-    if (r.indexBuffer == nullptr || (r.descArrayCount && (r.descArray == nullptr || (r.arrayData == nullptr && r.arrayDataSize))))
-        return b.log.invalid("[Invalid Arg] - deviceResult has a null array with a non-zero count");
-    int deviceCount = 0;
-    if (!HIP_OK(hipGetDeviceCount(&deviceCount)) || deviceCount < 1) { (void)hipGetLastError(); return b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)"); }
+    if (has_null_array(r)) return b.log.invalid("[Invalid Arg] - deviceResult has a null array with a non-zero count");
+    if (!usable_device()) return b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)");
     const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
     PoolBlock head(b.devPool.get(), geo_head_bytes(a)), tiles;
     if (!head.p) return b.log.failure("[Failure] - out of device memory for the geometry scratch");
@@ -3073,64 +3128,39 @@ OMM_MI355X_API ommResult ommxExtractMicroGeometry(ommBaker baker, const ommCpuBa
 namespace {
 ommResult coarsen_device(Baker& b, const ommCpuBakeResultDesc& r, const ommxCoarsenDesc& c, ommxDeviceBakeResult* outResult, ommxCoarsenInfo* outInfo, hipStream_t stream)
 {
-    if (r.indexFormat != ommIndexFormat_UINT_8 && r.indexFormat != ommIndexFormat_UINT_16 && r.indexFormat != ommIndexFormat_UINT_32)
-        return b.log.invalid("[Invalid Arg] - deviceResult.indexFormat is not an index format");
+    if (!is_index_format(r.indexFormat)) return b.log.invalid("[Invalid Arg] - deviceResult.indexFormat is not an index format");
     if (c.mixedState != 2 && c.mixedState != 3) return b.log.invalid("[Invalid Arg] - ommxCoarsenDesc.mixedState must be 2 (UnknownTransparent) or 3 (UnknownOpaque)");
     if ((c.flags & ~(uint32_t)(ommxCoarsenFlags_DisableSpecialIndices | ommxCoarsenFlags_DisableDuplicateDetection)) != 0) return b.log.invalid("[Invalid Arg] - ommxCoarsenDesc.flags has unknown bits");
     if (c.reserved[0] || c.reserved[1] || c.reserved[2]) return b.log.invalid("[Invalid Arg] - ommxCoarsenDesc.reserved must be 0");
-    if (r.indexCount && (r.indexBuffer == nullptr || (r.descArrayCount && (r.descArray == nullptr || (r.arrayData == nullptr && r.arrayDataSize)))))
-        return b.log.invalid("[Invalid Arg] - deviceResult has a null array with a non-zero count");
+    if (has_null_array(r)) return b.log.invalid("[Invalid Arg] - deviceResult has a null array with a non-zero count");
     ommxCoarsenInfo info; memset(&info, 0, sizeof info);
-    DeviceBakeResult* res = nullptr;
-    if (outResult) {
-        res = b.mem.make<DeviceBakeResult>();
-        if (!res) return b.log.failure("[Failure] - the memory allocator returned null for the coarsened result");
-        res->mem = b.mem; memset(&res->desc, 0, sizeof res->desc);
-        res->R.pool = b.devPool; res->R.numTris = r.indexCount; res->R.indexFormat = r.indexFormat;
-    }
-    // (pooled blocks of a result that is given up go back only when the stream is idle)
-    const auto give_up = [&](ommResult code) { if (res) { (void)hipStreamSynchronize(stream); b.mem.destroy(res); } return code; };
-    uint32_t hist[2 * 2 * kCoarsenLevels]; memset(hist, 0, sizeof hist);
+    DerivedResult out(b, stream, "coarsened");
+    const ommResult made = outResult ? out.create(r.indexCount, r.indexFormat) : ommResult_SUCCESS;
+    if (made != ommResult_SUCCESS) return made;
     if (r.indexCount) {
-        int deviceCount = 0;
-        if (!HIP_OK(hipGetDeviceCount(&deviceCount)) || deviceCount < 1) { (void)hipGetLastError(); return give_up(b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)")); }
+        if (!usable_device()) return out.give_up(b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)"));
         const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
-        CoarsenArgs a; a.result = r; a.maxLevel = c.maxSubdivisionLevel < kCoarsenLevels - 1u ? c.maxSubdivisionLevel : kCoarsenLevels - 1u; a.mixedState = c.mixedState; a.flags = c.flags;
+        CoarsenArgs a; a.result = r; a.maxLevel = c.maxSubdivisionLevel < kRebuildLevels - 1u ? c.maxSubdivisionLevel : kRebuildLevels - 1u; a.mixedState = c.mixedState; a.flags = c.flags;
         PoolBlock head(b.devPool.get(), coarsen_head_bytes(a)), staging;
-        if (!head.p) return give_up(b.log.failure("[Failure] - out of device memory for the coarsening scratch"));
+        if (!head.p) return out.give_up(b.log.failure("[Failure] - out of device memory for the coarsening scratch"));
         // (after a failed launch the scratch goes back only when nothing can still touch it)
-        const auto failed = [&] { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); return give_up(b.log.failure("[Failure] - the coarsening kernels could not run")); };
+        const auto failed = [&] { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); return out.give_up(b.log.failure("[Failure] - the coarsening kernels could not run")); };
         CoarsenPlan plan;
         if (coarsen_plan(a, head.p, &plan, stream) != hipSuccess) return failed();
-        if (plan.stagingBytes && !staging.acquire(b.devPool.get(), (size_t)plan.stagingBytes)) return give_up(b.log.failure("[Failure] - out of device memory for the coarsening scratch"));
-        CoarsenCounts n;
+        if (plan.stagingBytes && !staging.acquire(b.devPool.get(), (size_t)plan.stagingBytes)) return out.give_up(b.log.failure("[Failure] - out of device memory for the coarsening scratch"));
+        RebuildCounts n;
         if (coarsen_reduce(a, head.p, staging.p, plan, &n, stream) != hipSuccess) return failed();
-        if (n.arrayBytes > 0xFFFFFFFFull) return give_up(b.log.failure("[Failure] - the coarsened arrayData would exceed what a 32-bit descriptor offset can express"));
-        info.arrayDataSize = n.arrayBytes; info.descArrayCount = n.descCount; info.referencedBlocks = n.referenced; info.coarsenedBlocks = n.coarsened;
+        const ommResult sized = out.allocate(n);
+        if (sized != ommResult_SUCCESS) return sized;
+        info.arrayDataSize = n.arrayBytes; info.descArrayCount = n.descCount; info.referencedBlocks = plan.referenced; info.coarsenedBlocks = plan.coarsened;
         info.uniformBlocks = n.uniform; info.duplicateBlocks = n.duplicate; info.skippedPrimitives = plan.skipped;
-        if (res) {
-            DeviceResult& R = res->R;
-            R.numDescs = n.descCount; R.arrayDataSize = n.arrayBytes;
-            if (n.descCount) { R.arrayData = (uint8_t*)R.dev_alloc((size_t)n.arrayBytes); R.descs = (ommCpuOpacityMicromapDesc*)R.dev_alloc(sizeof(ommCpuOpacityMicromapDesc) * (size_t)n.descCount); }
-            R.index = R.dev_alloc((size_t)r.indexCount * (r.indexFormat == ommIndexFormat_UINT_8 ? 1u : r.indexFormat == ommIndexFormat_UINT_16 ? 2u : 4u));
-            if (!R.index || (n.descCount && (!R.arrayData || !R.descs))) return give_up(b.log.failure("[Failure] - out of device memory for the coarsened result"));
-            CoarsenOutputs o; o.arrayData = R.arrayData; o.descs = R.descs; o.index = R.index; o.hist = hist;
+        if (out.res) {
+            const DeviceResult& R = out.res->R;
+            CoarsenOutputs o; o.arrayData = R.arrayData; o.descs = R.descs; o.index = R.index; o.hist = out.hist;
             if (coarsen_emit(a, head.p, staging.p, n, o, stream) != hipSuccess) return failed();
         }
     }
-    if (res) {
-        // the histogram lists are built here, not by finish_device_result: a caller's source may hold both formats
-        uint32_t nAH = 0, nIH = 0;
-        for (uint32_t l = 0; l < kCoarsenLevels; ++l)
-            for (uint32_t f = 0; f < 2; ++f) {
-                const uint32_t ah = hist[2 * l + f], ih = hist[2 * kCoarsenLevels + 2 * l + f];
-                if (ah) res->arrayHist[nAH++] = ommCpuOpacityMicromapUsageCount{ ah, (uint16_t)l, (uint16_t)(f + 1) };
-                if (ih) res->indexHist[nIH++] = ommCpuOpacityMicromapUsageCount{ ih, (uint16_t)l, (uint16_t)(f + 1) };
-            }
-        const DeviceResult& R = res->R;
-        fill_result_desc(&res->desc, R.arrayData, R.arrayDataSize, R.descs, R.numDescs, R.index, R.numTris, R.indexFormat, res->arrayHist, nAH, res->indexHist, nIH);
-        *outResult = (ommxDeviceBakeResult)res;
-    }
+    out.finish(outResult);
     if (outInfo) *outInfo = info;
     return ommResult_SUCCESS;
 }
@@ -3160,30 +3190,18 @@ ommResult combine_device(Baker& b, const ommCpuBakeResultDesc* const* results, u
     if (c.flags != 0) return b.log.invalid("[Invalid Arg] - ommxCombineDesc.flags must be 0");
     if (c.reserved[0] || c.reserved[1] || c.reserved[2]) return b.log.invalid("[Invalid Arg] - ommxCombineDesc.reserved must be 0");
     for (uint32_t k = 0; k < count; ++k)
-        if (results[k]->indexFormat != ommIndexFormat_UINT_8 && results[k]->indexFormat != ommIndexFormat_UINT_16 && results[k]->indexFormat != ommIndexFormat_UINT_32)
-            return b.log.invalid("[Invalid Arg] - a source's indexFormat is not an index format");
+        if (!is_index_format(results[k]->indexFormat)) return b.log.invalid("[Invalid Arg] - a source's indexFormat is not an index format");
     const uint32_t indexCount = results[0]->indexCount;
     for (uint32_t k = 1; k < count; ++k)
         if (results[k]->indexCount != indexCount) return b.log.invalid("[Invalid Arg] - the sources' indexCount values differ: they must describe the same primitives");
-    for (uint32_t k = 0; k < count; ++k) {
-        const ommCpuBakeResultDesc& r = *results[k];
-        if (r.indexCount && (r.indexBuffer == nullptr || (r.descArrayCount && (r.descArray == nullptr || (r.arrayData == nullptr && r.arrayDataSize)))))
-            return b.log.invalid("[Invalid Arg] - a source has a null array with a non-zero count");
-    }
+    for (uint32_t k = 0; k < count; ++k)
+        if (has_null_array(*results[k])) return b.log.invalid("[Invalid Arg] - a source has a null array with a non-zero count");
     ommxCombineInfo info; memset(&info, 0, sizeof info);
-    DeviceBakeResult* res = nullptr;
-    if (outResult) {
-        res = b.mem.make<DeviceBakeResult>();
-        if (!res) return b.log.failure("[Failure] - the memory allocator returned null for the combined result");
-        res->mem = b.mem; memset(&res->desc, 0, sizeof res->desc);
-        res->R.pool = b.devPool; res->R.numTris = indexCount; res->R.indexFormat = ommIndexFormat_UINT_32;
-    }
-    // (pooled blocks of a result that is given up go back only when the stream is idle)
-    const auto give_up = [&](ommResult code) { if (res) { (void)hipStreamSynchronize(stream); b.mem.destroy(res); } return code; };
-    uint32_t hist[2 * 2 * kCoarsenLevels]; memset(hist, 0, sizeof hist);
+    DerivedResult out(b, stream, "combined");
+    const ommResult made = outResult ? out.create(indexCount, ommIndexFormat_UINT_32) : ommResult_SUCCESS;
+    if (made != ommResult_SUCCESS) return made;
     if (indexCount) {
-        int deviceCount = 0;
-        if (!HIP_OK(hipGetDeviceCount(&deviceCount)) || deviceCount < 1) { (void)hipGetLastError(); return give_up(b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)")); }
+        if (!usable_device()) return out.give_up(b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)"));
         const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
         CombineArgs a; memset(&a, 0, sizeof a);
         for (uint32_t k = 0; k < count; ++k) {
@@ -3193,47 +3211,33 @@ ommResult combine_device(Baker& b, const ommCpuBakeResultDesc* const* results, u
             s.arrayDataSize = r.arrayDataSize; s.descCount = r.descArrayCount; s.indexFormat = (int32_t)r.indexFormat;
         }
         a.sourceCount = count; a.indexCount = indexCount; a.format = c.format; a.mixedState = c.mixedState;
-        const auto no_memory = [&] { return give_up(b.log.failure("[Failure] - out of device memory for the combine scratch")); };
+        const auto no_memory = [&] { return out.give_up(b.log.failure("[Failure] - out of device memory for the combine scratch")); };
         PoolBlock head(b.devPool.get(), combine_head_bytes(a)), perTuple, staging;
         if (!head.p) return no_memory();
         // (after a failed launch the scratch goes back only when nothing can still touch it)
-        const auto failed = [&] { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); return give_up(b.log.failure("[Failure] - the combine kernels could not run")); };
+        const auto failed = [&] { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); return out.give_up(b.log.failure("[Failure] - the combine kernels could not run")); };
         CombineTuples t;
         if (combine_tuples(a, head.p, &t, stream) != hipSuccess) return failed();
         info.combinedTuples = t.tuples; info.skippedPrimitives = t.skipped;
-        CombineCounts n; memset(&n, 0, sizeof n);
+        RebuildCounts n; memset(&n, 0, sizeof n);
         if (t.tuples) {
             if (!perTuple.acquire(b.devPool.get(), combine_tuple_bytes(a, t.tuples))) return no_memory();
             CombinePlan plan;
             if (combine_plan(a, head.p, perTuple.p, t, &plan, stream) != hipSuccess) return failed();
             if (!staging.acquire(b.devPool.get(), (size_t)plan.stagingBytes)) return no_memory();
-            if (combine_join(a, head.p, perTuple.p, staging.p, t, plan, &n, stream) != hipSuccess) return failed();
-            if (n.arrayBytes > 0xFFFFFFFFull) return give_up(b.log.failure("[Failure] - the combined arrayData would exceed what a 32-bit descriptor offset can express"));
+            if (combine_join(a, perTuple.p, staging.p, t, plan, &n, stream) != hipSuccess) return failed();
             info.refinedTuples = plan.refined; info.uniformBlocks = n.uniform; info.duplicateBlocks = n.duplicate;
         }
+        const ommResult sized = out.allocate(n);
+        if (sized != ommResult_SUCCESS) return sized;
         info.arrayDataSize = n.arrayBytes; info.descArrayCount = n.descCount;
-        if (res) {
-            DeviceResult& R = res->R;
-            R.numDescs = n.descCount; R.arrayDataSize = n.arrayBytes;
-            if (n.descCount) { R.arrayData = (uint8_t*)R.dev_alloc((size_t)n.arrayBytes); R.descs = (ommCpuOpacityMicromapDesc*)R.dev_alloc(sizeof(ommCpuOpacityMicromapDesc) * (size_t)n.descCount); }
-            R.index = R.dev_alloc(4u * (size_t)indexCount);
-            if (!R.index || (n.descCount && (!R.arrayData || !R.descs))) return give_up(b.log.failure("[Failure] - out of device memory for the combined result"));
-            CombineOutputs o; o.arrayData = R.arrayData; o.descs = R.descs; o.index = (int32_t*)R.index; o.hist = hist;
+        if (out.res) {
+            const DeviceResult& R = out.res->R;
+            CombineOutputs o; o.arrayData = R.arrayData; o.descs = R.descs; o.index = (int32_t*)R.index; o.hist = out.hist;
             if (combine_emit(a, head.p, perTuple.p, staging.p, t, n, o, stream) != hipSuccess) return failed();
         }
     }
-    if (res) {
-        uint32_t nAH = 0, nIH = 0;
-        for (uint32_t l = 0; l < kCoarsenLevels; ++l)
-            for (uint32_t f = 0; f < 2; ++f) {
-                const uint32_t ah = hist[2 * l + f], ih = hist[2 * kCoarsenLevels + 2 * l + f];
-                if (ah) res->arrayHist[nAH++] = ommCpuOpacityMicromapUsageCount{ ah, (uint16_t)l, (uint16_t)(f + 1) };
-                if (ih) res->indexHist[nIH++] = ommCpuOpacityMicromapUsageCount{ ih, (uint16_t)l, (uint16_t)(f + 1) };
-            }
-        const DeviceResult& R = res->R;
-        fill_result_desc(&res->desc, R.arrayData, R.arrayDataSize, R.descs, R.numDescs, R.index, R.numTris, R.indexFormat, res->arrayHist, nAH, res->indexHist, nIH);
-        *outResult = (ommxDeviceBakeResult)res;
-    }
+    out.finish(outResult);
     if (outInfo) *outInfo = info;
     return ommResult_SUCCESS;
 }

@@ -7,6 +7,7 @@
 // fieldBits * 4^level bits of its ceil(. / 8) bytes count (levels 0 and 1 leave part of their single byte unused).
 #pragma once
 #include <stdint.h>
+#include "result_block.h"
 
 #ifdef __HIPCC__
 #define OMMX_STATS_FN __host__ __device__ __forceinline__
@@ -16,8 +17,6 @@
 
 namespace ommx {
 
-// what the bounds rule of include/omm_mi355x_lookup.h admits
-constexpr uint32_t kStatsMaxLevel = 12u;
 // work of the block histogram is cut into segments of this many bytes of one block (a level-12 4-state block is 256 of them)
 constexpr uint32_t kStatsSegmentBytes = 16384u;
 
@@ -53,9 +52,6 @@ OMMX_STATS_FN void stats_count_vec(const StatsVec q, uint32_t fieldBits, uint32_
     stats_count_word(q[0], 32u, fieldBits, c); stats_count_word(q[1], 32u, fieldBits, c);
     stats_count_word(q[2], 32u, fieldBits, c); stats_count_word(q[3], 32u, fieldBits, c);
 }
-
-// bytes a block of `level` <= 12 and fieldBits 1 or 2 occupies
-OMMX_STATS_FN uint64_t stats_block_bytes(uint32_t level, uint32_t fieldBits) { return (((uint64_t)fieldBits << (2u * level)) + 7u) >> 3; }
 
 // The share of lane `lane` of `lanes` in the bytes [begin, end) of one block (offsets relative to the block, end <= its size), added to c[0..3]:
 // the sum over all lanes is the histogram of that range.  `block` is the block's first byte, of any alignment.  The range is cut where the

@@ -9,6 +9,8 @@
 #include <rocprim/rocprim.hpp>
 #include "stats_kernels.h"
 #include "stats_count.h"
+#include "result_read.h"
+#include "bake_host.h"   // pad256
 #include "wave_search.h"
 
 namespace ommx {
@@ -19,24 +21,6 @@ constexpr uint32_t kStatsWaves = kStatsBlock / 64;
 constexpr uint64_t kStatsInlineBytes = 16;
 constexpr uint32_t kStatsMaxGrid = 65536;        // the strided kernels' grids: 32 workgroups per slot of the chip (256 CUs x 8), the rest by stride
 constexpr uint32_t kStatsAreaPerLane = 8;        // stats_known_area: a workgroup owns 256 x 8 consecutive primitives, whatever the grid
-
-static inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// The bounds rule: level <= 12, format 1 or 2, block inside arrayDataSize.  *bytes <- the block's size.
-__device__ __forceinline__ bool desc_ok(const ommCpuOpacityMicromapDesc d, uint32_t arrayDataSize, uint64_t* bytes)
-{
-    const uint32_t level = d.subdivisionLevel, bits = d.format;
-    if (level > kStatsMaxLevel || (bits != 1u && bits != 2u)) return false;
-    *bytes = stats_block_bytes(level, bits);
-    return (uint64_t)d.offset + *bytes <= (uint64_t)arrayDataSize;
-}
-
-__device__ __forceinline__ int32_t index_entry(const void* index, int format, uint64_t i)
-{
-    if (format == ommIndexFormat_UINT_8) return ((const int8_t*)index)[i];
-    if (format == ommIndexFormat_UINT_16) return ((const int16_t*)index)[i];
-    return ((const int32_t*)index)[i];
-}
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 {
@@ -95,7 +79,7 @@ __global__ __launch_bounds__(kStatsBlock) void stats_count_blocks(ommCpuBakeResu
     for (unsigned long long seg = blockIdx.x; seg < total; seg += gridDim.x) {
         const uint32_t d = owner_of_segment(segStart, r.descArrayCount, seg);
         const ommCpuOpacityMicromapDesc desc = r.descArray[d];   // (has segments, so it passed the bounds rule in stats_prepare)
-        const uint64_t bytes = stats_block_bytes(desc.subdivisionLevel, desc.format);
+        const uint64_t bytes = block_bytes(desc.subdivisionLevel, desc.format);
         const uint64_t begin = (uint64_t)(seg - segStart[d]) * kStatsSegmentBytes;
         const uint64_t end = begin + kStatsSegmentBytes < bytes ? begin + kStatsSegmentBytes : bytes;
         uint32_t c[4] = { 0u, 0u, 0u, 0u };

@@ -145,7 +145,7 @@ static void check_pieces()
     for (uint32_t level = 0; level <= 12; ++level)
         for (uint32_t fieldBits = 1; fieldBits <= 2; ++fieldBits) {
             const uint64_t bits = (uint64_t)fieldBits << (2 * level);
-            EXPECT(coarsen_block_bytes(level, fieldBits) == (bits < 8 ? 1 : bits / 8), "block bytes of level %u", level);
+            EXPECT(block_bytes(level, fieldBits) == (bits < 8 ? 1 : bits / 8), "block bytes of level %u", level);
         }
 }
 

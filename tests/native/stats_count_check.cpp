@@ -16,14 +16,14 @@ static uint64_t rng() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 
 int main()
 {
     const uint32_t cuts[5] = { 1u, 15u, 16u, 17u, kStatsSegmentBytes };
-    const size_t maxBytes = (size_t)stats_block_bytes(kStatsMaxLevel, 2u);
+    const size_t maxBytes = (size_t)block_bytes(kResultMaxLevel, 2u);
     uint8_t* buf = (uint8_t*)aligned_alloc(64, maxBytes + 64);
     std::vector<uint8_t> block(maxBytes);
     if (!buf) return 2;
     unsigned cases = 0;
-    for (uint32_t level = 0; level <= kStatsMaxLevel; ++level)
+    for (uint32_t level = 0; level <= kResultMaxLevel; ++level)
         for (uint32_t bits = 1; bits <= 2; ++bits) {
-            const uint64_t bytes = stats_block_bytes(level, bits), fields = 1ull << (2u * level);
+            const uint64_t bytes = block_bytes(level, bits), fields = 1ull << (2u * level);
             if (bytes != (fields * bits + 7u) / 8u) { printf("block bytes of level %u, %u bits: %llu\n", level, bits, (unsigned long long)bytes); return 1; }
             for (uint64_t i = 0; i < bytes; ++i) block[i] = (uint8_t)(rng() >> 32);
             uint32_t want[4] = { 0, 0, 0, 0 };

@@ -344,6 +344,51 @@ def test_commutative_and_idempotent(dll, hip, baker):
             src.close()
 
 
+# ---- the two callers of the shared tail ----
+@pytest.mark.parametrize("fmt", [1, 2], ids=["2state", "4state"])
+def test_one_source_equals_a_coarsening_that_keeps_every_level(dll, hip, baker, fmt):
+    """ommxCoarsenMicromap with cap 12 and ommxCombineMicromaps of the one source into its own format both keep every block as it is and then run the
+    same tail, so they return the same result.  Blocks are ordered by size class descending and, within a class, by source descriptor (coarsen) or
+    by lowest primitive (combine): the two coincide because descriptors first appear in ascending order in the index buffer.  One table of levels
+    0..9 in one format with an exact duplicate pair, a uniform block, special entries and entries that fail the bounds rule."""
+    blocks = []
+    for level in range(10):
+        states = next(s for s in (cu.planted_states(level, fmt, seed) for seed in range(70, 90)) if level == 0 or s.min() != s.max())
+        blocks.append((states, level, fmt))
+    blocks.append(blocks[5])                                          # descriptor 10: the bytes of descriptor 5 again
+    blocks.append((np.ones(4 ** 4, np.uint8), 4, fmt))                # descriptor 11: uniform
+    array_data, descs = cu.table_of_blocks(blocks, first_offset=3, gap=1)
+    descs = np.concatenate([descs, [(len(array_data) - 1, 3, fmt)]])  # descriptor 12: its block ends behind the array
+    specials = [-1, -2] if fmt == 1 else [-1, -2, -3, -4]             # (the 2-state format has no unknown states to keep)
+    index = list(range(13)) + specials + [10, 3, 5, -7, 11, 0, 9, 12]
+    src = cu.Source(hip, array_data, descs, index, ot.IDX_U8, array_align=1)
+    try:
+        ref = src.model(12)
+        assert ref["info"]["duplicateBlocks"] == 1 and ref["info"]["uniformBlocks"] == 2 and ref["info"]["descArrayCount"] == 9
+        assert ref["info"]["skippedPrimitives"] == 3 and ref["descs"][:, 1].tolist() == [9, 8, 7, 6, 5, 4, 3, 2, 1]
+        r, coarse_info, coarse = cu.coarsen(dll, baker, src.rd, 12)
+        assert r == ot.SUCCESS
+        try:
+            r, info, combined = mu.combine(dll, baker, [src.rd], fmt)
+            assert r == ot.SUCCESS
+            try:
+                a, b = cu.download_result(dll, hip, coarse), cu.download_result(dll, hip, combined)
+                assert (a["index_format"], b["index_format"]) == (ot.IDX_U8, ot.IDX_U32)
+                assert np.array_equal(a["array"], b["array"]) and np.array_equal(a["descs"], b["descs"])
+                assert np.array_equal(a["index"].astype(np.int64), b["index"].astype(np.int64))
+                assert a["array_hist"] == b["array_hist"] and a["index_hist"] == b["index_hist"]
+                for field in ("descArrayCount", "arrayDataSize", "uniformBlocks", "duplicateBlocks", "skippedPrimitives"):
+                    assert coarse_info[field] == info[field] == ref["info"][field], field
+                b["index"] = b["index"].astype(a["index"].dtype)
+                cu.assert_same(b, ref)
+            finally:
+                assert dll.ommxDestroyDeviceBakeResult(combined) == ot.SUCCESS
+        finally:
+            assert dll.ommxDestroyDeviceBakeResult(coarse) == ot.SUCCESS
+    finally:
+        src.close()
+
+
 # ---- real bakes ----
 def _level9_hits(rng, num_prims, count):
     """random hits inside level-9 micro-triangles: interior to their ancestors at every coarser level"""
