@@ -1,6 +1,9 @@
 // bake_host.h -- the host-side rules of a bake that need no device: flag bits, index formats, the raw triangle upload, histogram lists, the result descriptor
-// and the carve of the working set.  Plain C++ (no HIP): omm_host.cpp calls each directly, tests/native/bake_host_check.cpp runs them under sanitizers.
+// the carve of the working set, and the decisions and layouts of bake_core's stages that follow from a bake's counters alone (rank ranges, streamed result or
+// not, deferred generic pass, the states arena, the read-back slots).  Plain C++ (no HIP): omm_host.cpp calls each directly, tests/native/bake_host_check.cpp
+// runs them under sanitizers.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include "../../include/omm_mi355x.h"
@@ -128,4 +131,122 @@ inline BakeTables carve_bake_tables(uintptr_t base, uint32_t maxItems, size_t sc
     t.bytes = (size_t)(c.at - base);
     return t;
 }
+
+// ---- the decisions of a bake that follow from its counters alone (SetupCounters after the triage): bake_core's stages call them (omm_host.cpp) ----
+// rank ranges of the per-level active lists: rank r owns [b[l][r], b[l][r + 1]) of level l (single GPU: world 1, every range is the whole level group)
+inline void rank_ranges(const uint32_t* activeStart, uint32_t rank, uint32_t world, uint32_t (*b)[kBakeMaxRanks + 1], uint32_t* first, uint32_t* count)
+{
+    for (int l = 0; l < kBakeLevels; ++l) {
+        const uint64_t a = activeStart[l], cnt = activeStart[l + 1] - activeStart[l];
+        for (uint32_t r = 0; r <= world; ++r) b[l][r] = (uint32_t)(a + cnt * r / world);
+        first[l] = b[l][rank]; count[l] = b[l][rank + 1] - b[l][rank];
+    }
+}
+
+// The classification time is estimated from the two quantities that drive it: micro-triangles (sub-texel ones, mostly culled: 2.5e-10 ms each -- 27 ms for
+// 6.5e10, 128 ms for 6.0e11 measured) and texels under the triangles' boxes (micro-triangles of several texels walk them: 4e-9 ms each -- 55 ms for 1.4e10
+// measured on asset-sized cards, where streaming the 0.28 GB result made the bake 10 ms SLOWER).
+constexpr double kMsPerMicroTriangle = 2.5e-10, kMsPerWorkloadTexel = 4e-9;
+inline double classify_estimate_ms(double microTriangles, uint64_t workload) { return kMsPerMicroTriangle * microTriangles + kMsPerWorkloadTexel * (double)workload; }
+constexpr uint64_t kStreamMinStateBytes = 64ull << 20;   // a streamed result from 64 MiB of packed states on ...
+constexpr int kStreamRangeShift = 25;                    // ... one range per 32 MiB ...
+constexpr uint32_t kBakeMaxStreamRanges = 32;            // ... at most kMaxStreamRanges (round 3, classification-bound, at 1.27 GB: 8 / 16 / 24 / 32 ranges = 38.4 / 36.7 / 36.2 / 36.2 ms;
+                                                         //     round 4, copy-bound: 12 / 16 / 24 / 32 ranges = 32.4 / 31.8 / 31.0 / 30.9 ms)
+constexpr double kLinkBytesPerMs = 57e6;                 // ~57 GB/s over PCIe
+constexpr double kStreamClassifyShare = 0.25;            // streaming costs the classification about a quarter of its time (5 instead of 6 workgroups per CU, the placement kernels next to it)
+// the streamed against the compressed transfer (round 5: the codec stream over the link, expanded by the helper threads AFTER the bake), both priced from the same two
+// quantities, with this round's rates (1.35e-10 ms per micro-triangle: 8.8 ms for 6.5e10, 88 for 6.0e11) and 65 % of the packed states as the result (what is left
+// after promotion and dedup at the metric configuration):
+//     streamed    6 + max(1.15 classification + 2.7 (preview), result / 57 GB/s)       c2: 28.3 (29.4 measured)   configs[4]: 110 (was 118 at 95 ms)
+//     compressed  3.3 + classification + result / 150 GB/s + codec (0.63 ms per GB)       c2: 18.4 (17 - 20)         configs[4]: 117 (124)
+// -- a long classification hides the whole copy, a short one is better off with every workgroup on the chip and the expansion behind it.
+constexpr double kPricedMsPerMicroTriangle = 1.35e-10, kResultShareOfStates = 0.65;
+constexpr double kStreamedFixedMs = 6.0, kStreamedClassifyFactor = 1.15, kStreamedPreviewMs = 2.7;
+constexpr double kCompressedFixedMs = 3.3, kCompressedBytesPerMs = 150e6, kCodecMsPerByte = 0.63e-9;
+// Ranges of a streamed result (0: not streamed) for a bake that is eligible for one.  Worth it when the packed states are large enough for the copy to matter,
+// only when the copy is worth hiding (it saves at most the copy), and, when the compressed transfer is on offer too, only when streaming wins.  A forced count
+// (the knob) is only clamped.
+inline uint32_t stream_range_count(uint64_t stateBytes, double microTriangles, uint64_t workload, bool compressedAvailable, bool forced, uint32_t chunksWanted)
+{
+    uint32_t k = chunksWanted;
+    if (!forced) {
+        k = stateBytes >= kStreamMinStateBytes ? (uint32_t)(stateBytes >> kStreamRangeShift) : 0u; if (k > kBakeMaxStreamRanges) k = kBakeMaxStreamRanges;
+        const double classifyMs = classify_estimate_ms(microTriangles, workload), copyMs = (double)stateBytes / kLinkBytesPerMs;
+        if (copyMs <= kStreamClassifyShare * classifyMs) k = 0;
+        if (k && compressedAvailable) {
+            const double cMs = kPricedMsPerMicroTriangle * microTriangles + kMsPerWorkloadTexel * (double)workload, resultBytes = kResultShareOfStates * (double)stateBytes;
+            const double streamedMs = kStreamedFixedMs + std::max(kStreamedClassifyFactor * cMs + kStreamedPreviewMs, resultBytes / kLinkBytesPerMs), compressedMs = kCompressedFixedMs + cMs + resultBytes / kCompressedBytesPerMs + resultBytes * kCodecMsPerByte;
+            if (compressedMs <= streamedMs) k = 0;
+        }
+    }
+    return k > kBakeMaxStreamRanges ? kBakeMaxStreamRanges : k;
+}
+// how long the placement stream waits for a range before it gives the stream up: 100 x the estimate of the whole classification, never below 4 s
+inline double stream_wait_seconds(double microTriangles, uint64_t workload) { return 4.0 + 100.0 * 1e-3 * classify_estimate_ms(microTriangles, workload); }
+
+// Deferred generic pass (bake_kernels.hip: classify_generic): for bakes whose cost is in the texels under their micro-triangles, not in their number -- the
+// same two terms as above.  mode: ommxBakerKnob_GenericPass (0 = by cost, 1 = never, 2 = always).
+inline bool generic_pass_wanted(uint64_t mode, double microTriangles, uint64_t workload)
+{
+    return mode == 2 || (mode == 0 && kMsPerWorkloadTexel * (double)workload > kMsPerMicroTriangle * microTriangles);
+}
+constexpr uint64_t kGenericMaxEntries = 256ull << 20;   // at most 2 GB of entries (a tile that finds no room walks its micro-triangles itself)
+inline uint64_t generic_pass_capacity(uint64_t stateBytes, int storeBits)
+{
+    const uint64_t n = stateBytes * 8ull / (uint64_t)storeBits;   // every micro-triangle of every active item ...
+    return n > kGenericMaxEntries ? kGenericMaxEntries : n;       // ... up to the cap
+}
+
+// stride that interleaves a level's active list of cnt >= 3 items across the ranks (tail_kernels.hip: shard_interleave): golden-ratio start, the next number
+// coprime to cnt (cnt - 1 always is: terminates), already reduced % cnt
+inline uint32_t interleave_stride(uint32_t cnt)
+{
+    uint32_t stride = (uint32_t)((double)cnt * 0.6180339887498949); if (stride < 1) stride = 1;
+    auto gcd = [](uint32_t x, uint32_t y) { while (y) { const uint32_t t = x % y; x = y; y = t; } return x; };
+    while (gcd(stride, cnt) != 1) ++stride;
+    return stride % cnt;
+}
+
+// ---- the states arena of a bake: packed states of the active items | queue of open tiles | its control words | staging copy of a streamed result |
+//      deferred generic pass: count word (256 B), then the entries (8 bytes each).  Sized and carved by ONE traversal, like the tables above. ----
+constexpr size_t kBakeClassifyCtlWords = 512;   // kClassifyCtlWords
+struct BakeStates {
+    uint8_t *states, *tileQueue; uint32_t* queueCtl; uint8_t *stage, *genericCount; uint64_t* genericEntries;   // stage / generic*: null when absent
+    size_t stateBytes;   // of `states` (and of `stage`): at least 256
+    size_t bytes;        // end of the last slot, from the base
+};
+inline BakeStates carve_bake_states(uintptr_t base, uint64_t packedStateBytes, size_t queueBytes, bool streamed, uint64_t genericCapacity)
+{
+    BakeStates s = BakeStates(); CarveCursor c{ base };
+    s.stateBytes = pad256(packedStateBytes ? (size_t)packedStateBytes : 256);
+    s.states = c.take<uint8_t>(s.stateBytes);
+    s.tileQueue = c.take<uint8_t>(queueBytes);
+    s.queueCtl = c.take<uint32_t>(kBakeClassifyCtlWords);
+    if (streamed) s.stage = c.take<uint8_t>(s.stateBytes);
+    if (genericCapacity) { s.genericCount = c.take<uint8_t>(256); s.genericEntries = c.take<uint64_t>((size_t)genericCapacity); }
+    s.bytes = (size_t)(c.at - base);
+    return s;
+}
+
+// ---- the final read-backs in the arena's pinned host block: [0, 256) counters, [256, 512) tail summary, from 1 KiB the span [arrayHist, end of fine), the
+//      classification's control words, the three words of the generic pass.  !fits: they go to pageable memory instead. ----
+constexpr size_t kBakeHostBlockBytes = 64u << 10;   // kHostBlockBytes
+constexpr size_t kGenericReadbackBytes = 3 * sizeof(unsigned long long);   // reservations (incl. null padding), the pass's cursor, micro-triangles it classified
+struct ReadbackSlots { size_t spanAt, ctlAt, genAt; bool fits; };
+inline ReadbackSlots readback_slots(size_t spanBytes, size_t blockBytes = kBakeHostBlockBytes)
+{
+    ReadbackSlots s; s.spanAt = 1024; s.ctlAt = s.spanAt + pad256(spanBytes); s.genAt = s.ctlAt + sizeof(uint32_t) * kBakeClassifyCtlWords;
+    s.fits = s.genAt + kGenericReadbackBytes <= blockBytes;
+    return s;
+}
+
+// classify_tiles launches: one per level below 5, one for level 5, ONE for all levels >= 6 (bake_kernels.hip)
+inline uint32_t classify_launches(const uint32_t* activeStart)
+{
+    uint32_t n = 0; bool big = false;
+    for (int l = 0; l < kBakeLevels; ++l) { const bool any = activeStart[l + 1] != activeStart[l]; if (l < 6) n += any; else big = big || any; }
+    return n + big;
+}
+// every work item outside the active lists is uniform, and uniform items of one level and state share a digest: at most 13 x 4 of those
+inline uint32_t max_distinct_digests(uint32_t activeItems) { return activeItems + 64u; }
 } // namespace ommx

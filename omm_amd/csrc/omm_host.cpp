@@ -778,309 +778,281 @@ ommResult run_host_tail_for(const ommCpuBakeInputDesc& d, uint32_t T, std::vecto
     return ommResult_SUCCESS;
 }
 
-// The bake proper: bake_cpu_impl.cpp:1923-1985 re-organised for the device.  `din` points at device copies of the
-// caller's texCoords / indexBuffer / subdivisionLevels; `hostDesc` (may be null for device-resident callers) is the
-// same desc with host pointers, needed only by the serial fallbacks.
-ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInputs& din, const ommCpuBakeInputDesc* hostDesc,
-                    DeviceArena* arena, DeviceArena* statesArena, hipStream_t stream, EventTimer& et, DeviceResult& R, ommxBakeTimings& tm,
-                    ShardCtx* sh = nullptr, HostTailRequest* ht = nullptr, StreamOut* so = nullptr)
+static_assert(kBakeMaxStreamRanges == kMaxStreamRanges && kBakeClassifyCtlWords == kClassifyCtlWords && kBakeHostBlockBytes == kHostBlockBytes && sizeof(((ShardBounds*)nullptr)->b[0]) == sizeof(uint32_t) * (kBakeMaxRanks + 1),
+              "bake_host.h restates these constants of the kernel headers and of the pinned host block");
+
+// what the kernels read of one mip level (bake_core's classification, ommxResolveHits)
+DevMip dev_mip(const TexMip& tmip)
 {
-    const Logger& L = baker.log;
-    const uint32_t flags = (uint32_t)d.bakeFlags;
-    if (!R.pool) R.pool = baker.devPool;
-    const Texture& tex = *untag<Texture>(d.texture);
-    const uint32_t T = d.indexCount / 3u;
-    const int bits = (int)d.format;
+    DevMip dm; memset(&dm, 0, sizeof dm);
+    dm.texels = tmip.texels; dm.sat = tmip.sat; dm.w = tmip.w; dm.h = tmip.h;
+    dm.log2w = (int)ctz32((uint32_t)tmip.w); dm.log2h = (int)ctz32((uint32_t)tmip.h);
+    dm.pow2 = is_pow2(tmip.w) && is_pow2(tmip.h);
+    dm.fw = (float)tmip.w; dm.fh = (float)tmip.h; dm.rw = 1.f / (float)tmip.w; dm.rh = 1.f / (float)tmip.h;
+    return dm;
+}
+
+// ---- a bake in flight: the inputs of bake_core, what its stages hand on, and the stages themselves in the order they run ----
+struct BakeRun;
+// The streamed-result protocol (StreamOut above): the events behind the classification launches, what the hooks behind those launches need, the preview, the
+// loop that sends what each launch placed, and the comparison with the tail's exact layout.  The hooks point into `sc`: it outlives launch_classify.
+struct StreamRun {
+    struct EventList { hipEvent_t ev[2 * kMaxClassifyChunks + 3]; uint32_t n = 0; ~EventList() { for (uint32_t k = 0; k < n; ++k) (void)hipEventDestroy(ev[k]); } } events;   // range placed [K + 1] | fences [K + 2]
+    StreamCtx sc;
+    uint64_t sent = 0;        // bytes of the staging copy that are on their way to the caller's array
+    int pv0 = -1, pv1 = -1;   // HIP event marks around the preview
+    ommResult begin(BakeRun& b);    // reads the plan of the states; leaves the placement tables cleared, the events created, `sc` and b.cc set up, the preview's early flags
+    ommResult follow(BakeRun& b);   // reads the cursor each range publishes; leaves the placed bytes queued for the host array (SDMA or HIP copy), the range-ready times
+    ommResult verify(BakeRun& b);   // reads the tail's order and offsets; leaves b.streamed, after a discarded stream the fallback's PerfWarning, the stream fields of `so` and `tm`
+};
+struct BakeRun {
+    // ---- the call ----
+    Baker& baker; const ommCpuBakeInputDesc& d; const DeviceInputs& din; DeviceArena* const arena; DeviceArena* const statesArena; const hipStream_t stream;
+    EventTimer& et; DeviceResult& R; ommxBakeTimings& tm;
+    ShardCtx* const sh; HostTailRequest* const ht; StreamOut* const so;   // the mode, each null when it is not the one: sharded begin | host tail | streamed result on offer
+    const Logger& L; const Texture& tex;
+    const uint32_t flags, T, maxItems; const int bits;
     // DisableFineClassification with the 2-state format (internal flag bit 9): unresolved micro-triangles keep UnknownOpaque (3), which has no 1-bit form -- the
     // reference digests the unpacked states and ORs `3 << (i & 7)` into the packed bytes (bake_cpu_impl.cpp:1811).  The states are therefore kept in the
     // 2-bit packing up to the final gather, which applies that rule (launch_gather_omms: storeBits != bits).
-    const int storeBits = no_fine_two_state(d) ? 2 : bits;
-    const uint32_t maxItems = T ? T : 1;
+    const int storeBits;
+    const bool noDedup;
+    // ---- what the stages hand on ----
+    BakeTables tab; SetupParams S; SetupCounters hc; ClassifyParams P;
+    uint8_t* hostBlock = nullptr;   // the arena's pinned block, layout: [0, 256) counters, [256, 512) tail summary, [1 KiB, ..) the final read-backs (readback_slots)
+    uint32_t U = 0, numActive = 0; double microAll = 0;   // work items, active ones, micro-triangles of all
+    ShardBounds bounds; uint32_t lvlFirst[kNumLevels], lvlCount[kNumLevels];   // this rank's range of every level's active list
+    uint32_t streamChunks = 0; uint8_t* hostArray = nullptr; unsigned long long* hCursor = nullptr; bool hostPinned = false;   // streamed result: ranges (0: none), the caller's array, the pinned cursor words
+    uint64_t genericCapacity = 0;   // entries of the deferred generic pass (0: none)
+    BakeStates st;
+    ItemArrays A; ClassifyChunks cc; MarkCtx mk;
+    TailInputs ti; TailOutputs to; TailCounts counts;
+    bool streamed = false;   // the streamed result stands: no gather, no array on the device
+    unsigned long long fineCount = 0, genericMicro = 0; uint32_t queueTails[2] = { 0u, 0u };   // read-back statistics; open tiles of the two tile sizes
+    double coreT0 = 0; int e0 = -1, e1 = -1, e1b = -1, e2 = -1, e3 = -1, e4 = -1, e5 = -1;   // HIP event marks: setup | triage | classify | digest | tail | gather
 
-    // ---- device layout (worst case: every triangle is its own work item) ----
-    const size_t setupBytes = setup_scratch_bytes(T), tailBytes = tail_scratch_bytes(maxItems, T), streamScratch = so ? stream_scratch_bytes(maxItems) : 0;
-    const size_t scratchBytes = std::max(std::max(setupBytes, tailBytes), streamScratch);
-    // size and pointers from the same traversal (bake_host.h): first over offsets, then over the arena
-    if (!arena->reserve(carve_bake_tables(0, maxItems, scratchBytes, sh != nullptr, so != nullptr).bytes)) return L.failure("[Failure] - out of device memory for the bake working set");
-    const BakeTables tab = carve_bake_tables((uintptr_t)arena->base, maxItems, scratchBytes, sh != nullptr, so != nullptr);
-    R.triAreaScratch = tab.triArea;
-
-    // ---- SetupWorkItems (bake_cpu_impl.cpp:589-660) on the device ----
-    const double coreT0 = now_ms();
-    const int e0 = et.mark();
-    SetupParams S; memset(&S, 0, sizeof S);
-    S.texCoords = din.texCoords; S.indices = din.indices; S.perTriLevels = din.perTriLevels;
-    S.stride = uv_stride(d);
-    S.uvFormat = d.texCoordFormat; S.indexFormat = d.indexFormat; S.numTris = T;
-    S.globalLevel = d.maxSubdivisionLevel; S.dynScale = d.dynamicSubdivisionScale; S.edgeHeuristic = has_flag(flags, kBakeFlag_EnableEdgeHeuristic);   // (bake_cpu_impl.cpp:48,547)
-    S.texW = tex.mips[0].w; S.texH = tex.mips[0].h; S.disableDedup = has_flag(flags, ommCpuBakeFlags_DisableDuplicateDetection);
-    S.wantWorkload = 1;   // (also the input of the two shape decisions below: streamed result, deferred generic pass)
-    S.degenerateInvalid = has_flag(flags, kBakeFlag_DisableLevelLineIntersection);
-    const bool checkWorkload = has_flag(flags, ommCpuBakeFlags_EnableWorkloadValidation) || d.maxWorkloadSize != 0xFFFFFFFFFFFFFFFFull;
-    S.format = (int)d.format;   // (per-triangle formats other than the global one are refused above: one format per bake)
-    bool ok = HIP_OK(hipMemcpyAsync(tab.counters, &bake_head(), sizeof(BakeHead), hipMemcpyHostToDevice, stream));   // (counters and digest table are adjacent slots of the carve: see BakeHead)
-    ok = ok && HIP_OK(run_setup_fetch(S, tab.scratch, tab.scratchBytes, tab.counters, tab.known, maxItems, (uint32_t*)tab.fine, 2u * kFineSlots * kFineStride, tab.triArea, stream));
-    if (!ok) return L.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)");
-    SetupCounters hc; memset(&hc, 0, sizeof hc);
-    if (d.dynamicSubdivisionScale > 0.f && T) { // degenerate triangles under dynamic subdivision need glibc's log2f: host (bake_cpu_impl.cpp:511-528)
-        if (!HIP_OK(hipMemcpyAsync(&hc, tab.counters, sizeof hc, hipMemcpyDeviceToHost, stream)) || !HIP_OK(hipStreamSynchronize(stream)))
-            return L.failure("[Failure] - device work-item setup failed");
-        if (hc.numPending) {
-            std::vector<uint32_t> pend(hc.numPending); std::vector<float> puv((size_t)hc.numPending * 6); std::vector<uint8_t> plv(hc.numPending);
-            const PoolBlock tmp(baker.devPool.get(), (size_t)hc.numPending * 24 + 256);
-            if (!tmp.p) return L.failure("[Failure] - device work-item setup failed");
-            if (!HIP_OK(copy_pending_to_host(tab.scratch, tab.scratchBytes, T, hc.numPending, pend.data(), puv.data(), tmp.p, stream))) return L.failure("[Failure] - device work-item setup failed");
-            {   // (tiny triangles under dynamic subdivision are degenerate by the tens of thousands -- configs[4]: 1.5 ms of log2f on one thread; four share it)
-                ommCpuBakeInputDesc tmpDesc = d; tmpDesc.subdivisionLevels = nullptr;   // per-triangle overrides were already honoured on the device
-                auto part = [&](uint32_t k0, uint32_t k1) {
-                    for (uint32_t k = k0; k < k1; ++k) { HostTri t; memcpy(t.p, &puv[(size_t)k * 6], 24); plv[k] = (uint8_t)level_for_primitive(tmpDesc, flags, 0, t, S.texW, S.texH); }
-                };
-                // helper threads only with the caller's permission (ommCpuBakeFlags_EnableInternalThreads, omm.h:303: what the reference spends on its OpenMP
-                // loops); a thread that cannot be started (std::system_error: thread limit, cgroup pids) leaves its share to this thread -- nothing escapes the C ABI
-                const uint32_t n = hc.numPending, ways = (n >= 8192u && (flags & (uint32_t)ommCpuBakeFlags_EnableInternalThreads)) ? 4u : 1u;
-                std::vector<std::thread> helpers;
-                uint32_t started = 0;
-                try {
-                    helpers.reserve(ways);
-                    for (uint32_t w = 1; w < ways; ++w) { helpers.emplace_back(part, (uint32_t)((uint64_t)n * w / ways), (uint32_t)((uint64_t)n * (w + 1u) / ways)); started = w; }
-                } catch (...) {}
-                part(0u, (uint32_t)((uint64_t)n / ways));
-                for (auto& h : helpers) h.join();
-                for (uint32_t w = started + 1u; w < ways; ++w) part((uint32_t)((uint64_t)n * w / ways), (uint32_t)((uint64_t)n * (w + 1u) / ways));   // (shares whose thread did not start)
-            }
-            if (!HIP_OK(run_setup_fix_pending(S, tab.scratch, tab.scratchBytes, pend.data(), plv.data(), hc.numPending, tmp.p, stream))) return L.failure("[Failure] - device work-item setup failed");
-        }
-    }
-    if (!HIP_OK(run_setup_items(S, tab.scratch, tab.scratchBytes, tab.counters, tab.uv, tab.level, tab.degen, tab.triToItem, tab.itemIds, stream)))
-        return L.failure("[Failure] - device work-item setup failed");
-    const int e1 = et.mark();
-
-    // ---- classification parameters ----
-    ClassifyParams P; memset(&P, 0, sizeof P);
-    P.mipCount = (int)tex.mips.size();
-    for (int m = 0; m < P.mipCount; ++m) {
-        DevMip& dm = P.mips[m]; const TexMip& tmip = tex.mips[m];
-        dm.texels = tmip.texels; dm.sat = tmip.sat; dm.w = tmip.w; dm.h = tmip.h;
-        dm.log2w = (int)ctz32((uint32_t)tmip.w); dm.log2h = (int)ctz32((uint32_t)tmip.h);
-        dm.pow2 = is_pow2(tmip.w) && is_pow2(tmip.h);
-        dm.fw = (float)tmip.w; dm.fh = (float)tmip.h; dm.rw = 1.f / (float)tmip.w; dm.rh = 1.f / (float)tmip.h;
-    }
-    P.pow2Dispatch = P.mips[0].pow2;
-    P.texIsFp32 = tex.format == ommCpuTextureFormat_FP32;
-    P.addrMode = d.runtimeSamplerDesc.addressingMode;
-    P.filterLinear = d.runtimeSamplerDesc.filter == ommTextureFilterMode_Linear;
-    P.format = storeBits; P.promotion = d.unknownStatePromotion; P.stateGT = d.alphaCutoffGreater; P.stateLE = d.alphaCutoffLessEqual;
-    P.useCoarse = tex.mips[0].sat != nullptr && P.mipCount == 1 && P.filterLinear;
-    P.cutoff = d.alphaCutoff; P.borderAlpha = d.runtimeSamplerDesc.borderAlpha;
-    P.wantKnownCount = d.rejectionThreshold > 0.f;
-    P.noFine = has_flag(flags, kBakeFlag_DisableFineClassification);   // (bake_cpu_impl.cpp:45,822-823)
-    P.altKernel = has_flag(flags, kBakeFlag_DisableLevelLineIntersection) ? (has_flag(flags, kBakeFlag_EnableAABBTesting) ? 2 : 1) : 0;   // (bake_cpu_impl.cpp:44-45,915-966)
-
-    // ---- level-0 hierarchical query per item + compaction of the items that need per-micro-triangle work; ONE sync ----
-    launch_triage(P, tab.uv, tab.level, tab.degen, tab.counters, maxItems, tab.mask, tab.active, tab.scratch, stream);
-    uint8_t* const hostBlock = arena->host_block();   // layout: [0, 256) counters, [256, 512) tail summary, [1 KiB, ..) the final read-backs
-    SetupCounters* const hcDst = hostBlock ? (SetupCounters*)hostBlock : &hc;
-    if (!HIP_OK(run_prep(tab.itemIds, tab.active, tab.level, storeBits, maxItems, tab.counters, tab.activeIds, tab.stateOfs, tab.scratch, tab.scratchBytes, stream)) ||
-        !HIP_OK(hipMemcpyAsync(hcDst, tab.counters, sizeof hc, hipMemcpyDeviceToHost, stream)) || !HIP_OK(hipStreamSynchronize(stream)))
-        return L.failure("[Failure] - device work-list compaction failed");
-    if (hostBlock) memcpy(&hc, hcDst, sizeof hc);
-
-    uint32_t U = hc.numItems;
-    if (has_flag(flags, ommCpuBakeFlags_EnableValidation) && hc.numDisabled != 0) { // bake_cpu_impl.cpp:652-657
-        char buf[256];
-        snprintf(buf, sizeof buf, "[Info] - The workload consists of %d unclassifiable triangles, these will be classified as unresolvedTriState = %s.", hc.numDisabled, special_name(d.unresolvedTriState));
-        L.msg(ommMessageSeverity_Info, buf);
-    }
-    // ---- ValidateWorkloadSize (bake_cpu_impl.cpp:662-713) ----
-    if (checkWorkload) {
-        if (d.maxWorkloadSize != 0xFFFFFFFFFFFFFFFFull && hc.workload > d.maxWorkloadSize) return ommResult_WORKLOAD_TOO_BIG;
-        if (has_flag(flags, ommCpuBakeFlags_EnableWorkloadValidation) && hc.workload > (1ull << 27)) {
-            char buf[256];
-            snprintf(buf, sizeof buf, "[Perf Warning] - The workload consists of %lld work items (number of texels to classify), which corresponds to roughly %lld 1024x1024 textures."
-                     " This is unusually large and may result in long bake times.", (long long)hc.workload, (long long)(hc.workload >> 20));
-            L.msg(ommMessageSeverity_PerfWarning, buf);
-        }
-    }
-    if (has_flag(flags, kBakeFlag_EnableAABBTesting) && !has_flag(flags, kBakeFlag_DisableLevelLineIntersection))   // bake_cpu_impl.cpp:718-719 (ResampleCoarse is the first to look, behind the workload validation)
-        return L.invalid("[Invalid Arg] - EnableAABBTesting can't be used without also setting DisableLevelLineIntersection");
-    // rank ranges of the per-level active lists (single GPU: every range is the whole level group)
-    ShardBounds bounds; memset(&bounds, 0, sizeof bounds);
-    bounds.rank = sh ? sh->rank : 0; bounds.world = sh ? sh->world : 1;
-    uint32_t lvlFirst[kNumLevels], lvlCount[kNumLevels];
-    for (int l = 0; l < kNumLevels; ++l) {
-        const uint64_t a = hc.activeStart[l], cnt = hc.activeStart[l + 1] - hc.activeStart[l];
-        for (uint32_t r = 0; r <= bounds.world; ++r) bounds.b[l][r] = (uint32_t)(a + cnt * r / bounds.world);
-        lvlFirst[l] = bounds.b[l][bounds.rank]; lvlCount[l] = bounds.b[l][bounds.rank + 1] - bounds.b[l][bounds.rank];
-    }
-    // packed states of the active items + the queue of open tiles (48-byte records, bake_kernels.hip) + its 4 control words
-    const size_t stateBytes = pad256(hc.stateBytes ? (size_t)hc.stateBytes : 256), ctlBytes = pad256(sizeof(uint32_t) * kClassifyCtlWords);
-    const double microAll = (double)micro_triangles_of(hc.levelCount);
-    // ---- streamed result (ommCpuBake)?  Worth it when the packed states are large enough for the copy to matter ----
-    uint32_t streamChunks = 0; const uint32_t numActiveAll = hc.activeStart[kNumLevels];
-    uint8_t* hostArray = nullptr; unsigned long long* hCursor = nullptr; bool hostPinned = false;
-    if (so && numActiveAll && !has_flag(flags, ommCpuBakeFlags_DisableSpecialIndices) && !P.altKernel && storeBits == bits) {   // (with special indices disabled every uniform item is a block too: the plain path handles that)
-        uint32_t k = so->chunksWanted;
-        if (!so->forced) {
-            // >= 64 MiB of packed states: one range per 32 MiB, at most 32 (round 3, classification-bound, at 1.27 GB: 8 / 16 / 24 / 32 ranges = 38.4 / 36.7 / 36.2 / 36.2 ms)
-            k = hc.stateBytes >= (64ull << 20) ? (uint32_t)(hc.stateBytes >> 25) : 0u; if (k > kMaxStreamRanges) k = kMaxStreamRanges;   // (round 4, copy-bound: 12 / 16 / 24 / 32 ranges = 32.4 / 31.8 / 31.0 / 30.9 ms)
-            // ... and only when the copy is worth hiding.  Streaming costs the classification about a quarter of its time (5 instead of 6 workgroups per CU,
-            // the placement kernels next to it) and saves at most the copy (~57 GB/s over PCIe).  The classification time is estimated from the two
-            // quantities that drive it: micro-triangles (sub-texel ones, mostly culled: 2.5e-10 ms each -- 27 ms for 6.5e10, 128 ms for 6.0e11 measured) and
-            // texels under the triangles' boxes (micro-triangles of several texels walk them: 4e-9 ms each -- 55 ms for 1.4e10 measured on asset-sized
-            // cards, where streaming the 0.28 GB result made the bake 10 ms SLOWER).
-            const double classifyMs = 2.5e-10 * microAll + 4e-9 * (double)hc.workload, copyMs = (double)hc.stateBytes / 57e6;
-            if (copyMs <= 0.25 * classifyMs) k = 0;
-            // ... and, when the compressed transfer is available too (round 5: the codec stream over the link, expanded by the helper threads AFTER the bake), only
-            // when streaming wins.  Both are priced from the same two quantities, with this round's rates (1.35e-10 ms per micro-triangle: 8.8 ms for 6.5e10, 88 for
-            // 6.0e11) and 65 % of the packed states as the result (what is left after promotion and dedup at the metric configuration):
-            //     streamed    6 + max(1.15 classification + 2.7 (preview), result / 57 GB/s)       c2: 28.3 (29.4 measured)   configs[4]: 110 (was 118 at 95 ms)
-            //     compressed  3.3 + classification + result / 150 GB/s + codec (0.63 ms per GB)       c2: 18.4 (17 - 20)         configs[4]: 117 (124)
-            // -- a long classification hides the whole copy, a short one is better off with every workgroup on the chip and the expansion behind it.
-            if (k && so->compressedAvailable) {
-                const double cMs = 1.35e-10 * microAll + 4e-9 * (double)hc.workload, resultBytes = 0.65 * (double)hc.stateBytes;
-                const double streamedMs = 6.0 + std::max(1.15 * cMs + 2.7, resultBytes / 57e6), compressedMs = 3.3 + cMs + resultBytes / 150e6 + resultBytes * 0.63e-9;
-                if (compressedMs <= streamedMs) k = 0;
-            }
-        }
-        if (k > kMaxStreamRanges) k = kMaxStreamRanges;
-        if (k && so->set->pinned.reserve(4096) && (hostArray = so->alloc(so->allocUser, hc.stateBytes, &hostPinned)) != nullptr) { streamChunks = k; hCursor = (unsigned long long*)so->set->pinned.base; }
-    }
-    const size_t queueBytes = pad256((size_t)classify_queue_records(lvlCount, streamChunks > 1) * kTileRecordBytes + 16);
-    // ---- deferred generic pass?  (bake_kernels.hip: classify_generic)  For bakes whose cost is in the texels under their micro-triangles, not in their number:
-    // the same two terms as above.  Not for streamed bakes (a range must be complete when its queue sections are); a sharded rank defers the walks of
-    // its share like a single GPU does (asset-sized cards, 8 ranks: 15.0 -> 12 ms per step), except when the ranks merge their states by summation.
-    uint64_t genericCapacity = 0;
+    BakeRun(Baker& baker_, const ommCpuBakeInputDesc& d_, const DeviceInputs& din_, DeviceArena* arena_, DeviceArena* statesArena_, hipStream_t stream_, EventTimer& et_, DeviceResult& R_,
+            ommxBakeTimings& tm_, ShardCtx* sh_, HostTailRequest* ht_, StreamOut* so_)
+        : baker(baker_), d(d_), din(din_), arena(arena_), statesArena(statesArena_), stream(stream_), et(et_), R(R_), tm(tm_), sh(sh_), ht(ht_), so(so_), L(baker_.log),
+          tex(*untag<Texture>(d_.texture)), flags((uint32_t)d_.bakeFlags), T(d_.indexCount / 3u), maxItems(T ? T : 1), bits((int)d_.format), storeBits(no_fine_two_state(d_) ? 2 : bits),
+          noDedup(has_flag(flags, ommCpuBakeFlags_DisableDuplicateDetection))
     {
-        const uint64_t mode = baker.knob(ommxBakerKnob_GenericPass);
-        const bool wanted = mode == 2 || (mode == 0 && 4e-9 * (double)hc.workload > 2.5e-10 * microAll);
-        if (wanted && !streamChunks && !(sh && sh->mergeStates) && !ht && numActiveAll) {
-            genericCapacity = hc.stateBytes * 8ull / (uint64_t)storeBits;            // every micro-triangle of every active item ...
-            if (genericCapacity > (256ull << 20)) genericCapacity = 256ull << 20;   // ... at most 2 GB of entries (a tile that finds no room walks its micro-triangles itself)
-        }
+        if (!R.pool) R.pool = baker.devPool;
+        memset(&hc, 0, sizeof hc);
     }
-    const size_t genericBytes = genericCapacity ? pad256((size_t)genericCapacity * 8) + 256 : 0;
-    if (!statesArena->reserve(stateBytes + queueBytes + ctlBytes + (streamChunks ? stateBytes : 0) + genericBytes)) return L.failure("[Failure] - out of device memory for the packed micro-triangle states");
-    uint8_t* dStates = statesArena->base;
-    void* dTileQueue = statesArena->base + stateBytes; uint32_t* dQueueCtl = (uint32_t*)(statesArena->base + stateBytes + queueBytes);
-    uint8_t* dStage = streamChunks ? statesArena->base + stateBytes + queueBytes + ctlBytes : nullptr;
-    uint8_t* dGeneric = genericCapacity ? statesArena->base + stateBytes + queueBytes + ctlBytes + (streamChunks ? stateBytes : 0) : nullptr;   // count word (256 B), then the entries
-    const int e1b = et.mark();
 
-    // ---- ResampleCoarse + ResampleFine (bake_cpu_impl.cpp:715-1029) on the active items ----
-    ItemArrays A; A.uv = tab.uv; A.degenerate = tab.degen; A.stateOfs = tab.stateOfs; A.states = dStates; A.stateMask = tab.mask; A.knownCount = tab.known; A.fineCount = tab.fine;
-    // (tab.fine was zeroed by the first set-up launch, with the known counts)
-    if (sh && sh->mergeStates && !HIP_OK(hipMemsetAsync(dStates, 0, stateBytes, stream))) return L.failure("[Failure] - device memset failed");
-    if (sh && sh->world > 1) { // even out the per-rank cost: interleave every level's active list (tail_kernels.hip: shard_interleave)
+    // reads the triangle count and the mode; leaves the working set reserved and carved (worst case: every triangle is its own work item)
+    ommResult carve_tables()
+    {
+        const size_t setupBytes = setup_scratch_bytes(T), tailBytes = tail_scratch_bytes(maxItems, T), streamScratch = so ? stream_scratch_bytes(maxItems) : 0;
+        const size_t scratchBytes = std::max(std::max(setupBytes, tailBytes), streamScratch);
+        // size and pointers from the same traversal (bake_host.h): first over offsets, then over the arena
+        if (!arena->reserve(carve_bake_tables(0, maxItems, scratchBytes, sh != nullptr, so != nullptr).bytes)) return L.failure("[Failure] - out of device memory for the bake working set");
+        tab = carve_bake_tables((uintptr_t)arena->base, maxItems, scratchBytes, sh != nullptr, so != nullptr);
+        R.triAreaScratch = tab.triArea;
+        return ommResult_SUCCESS;
+    }
+    // SetupWorkItems (bake_cpu_impl.cpp:589-660) on the device: reads the raw triangles; leaves the work items (uv, level, degen, triToItem, itemIds) and their counters
+    ommResult setup_work_items()
+    {
+        coreT0 = now_ms();
+        e0 = et.mark();
+        memset(&S, 0, sizeof S);
+        S.texCoords = din.texCoords; S.indices = din.indices; S.perTriLevels = din.perTriLevels;
+        S.stride = uv_stride(d);
+        S.uvFormat = d.texCoordFormat; S.indexFormat = d.indexFormat; S.numTris = T;
+        S.globalLevel = d.maxSubdivisionLevel; S.dynScale = d.dynamicSubdivisionScale; S.edgeHeuristic = has_flag(flags, kBakeFlag_EnableEdgeHeuristic);   // (bake_cpu_impl.cpp:48,547)
+        S.texW = tex.mips[0].w; S.texH = tex.mips[0].h; S.disableDedup = noDedup;
+        S.wantWorkload = 1;   // (also the input of the two shape decisions of plan_states: streamed result, deferred generic pass)
+        S.degenerateInvalid = has_flag(flags, kBakeFlag_DisableLevelLineIntersection);
+        S.format = (int)d.format;   // (per-triangle formats other than the global one are refused above: one format per bake)
+        bool ok = HIP_OK(hipMemcpyAsync(tab.counters, &bake_head(), sizeof(BakeHead), hipMemcpyHostToDevice, stream));   // (counters and digest table are adjacent slots of the carve: see BakeHead)
+        ok = ok && HIP_OK(run_setup_fetch(S, tab.scratch, tab.scratchBytes, tab.counters, tab.known, maxItems, (uint32_t*)tab.fine, 2u * kFineSlots * kFineStride, tab.triArea, stream));
+        if (!ok) return L.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)");
+        if (d.dynamicSubdivisionScale > 0.f && T) { // degenerate triangles under dynamic subdivision need glibc's log2f: host (bake_cpu_impl.cpp:511-528)
+            if (!HIP_OK(hipMemcpyAsync(&hc, tab.counters, sizeof hc, hipMemcpyDeviceToHost, stream)) || !HIP_OK(hipStreamSynchronize(stream)))
+                return L.failure("[Failure] - device work-item setup failed");
+            if (hc.numPending) if (const ommResult r = fix_pending_levels()) return r;
+        }
+        if (!HIP_OK(run_setup_items(S, tab.scratch, tab.scratchBytes, tab.counters, tab.uv, tab.level, tab.degen, tab.triToItem, tab.itemIds, stream)))
+            return L.failure("[Failure] - device work-item setup failed");
+        e1 = et.mark();
+        return ommResult_SUCCESS;
+    }
+    // reads the hc.numPending triangles the device left undecided (setup scratch); leaves their levels, computed on the host, in the setup scratch
+    ommResult fix_pending_levels()
+    {
+        std::vector<uint32_t> pend(hc.numPending); std::vector<float> puv((size_t)hc.numPending * 6); std::vector<uint8_t> plv(hc.numPending);
+        const PoolBlock tmp(baker.devPool.get(), (size_t)hc.numPending * 24 + 256);
+        if (!tmp.p) return L.failure("[Failure] - device work-item setup failed");
+        if (!HIP_OK(copy_pending_to_host(tab.scratch, tab.scratchBytes, T, hc.numPending, pend.data(), puv.data(), tmp.p, stream))) return L.failure("[Failure] - device work-item setup failed");
+        {   // (tiny triangles under dynamic subdivision are degenerate by the tens of thousands -- configs[4]: 1.5 ms of log2f on one thread; four share it)
+            ommCpuBakeInputDesc tmpDesc = d; tmpDesc.subdivisionLevels = nullptr;   // per-triangle overrides were already honoured on the device
+            auto part = [&](uint32_t k0, uint32_t k1) {
+                for (uint32_t k = k0; k < k1; ++k) { HostTri t; memcpy(t.p, &puv[(size_t)k * 6], 24); plv[k] = (uint8_t)level_for_primitive(tmpDesc, flags, 0, t, S.texW, S.texH); }
+            };
+            // helper threads only with the caller's permission (ommCpuBakeFlags_EnableInternalThreads, omm.h:303: what the reference spends on its OpenMP
+            // loops); a thread that cannot be started (std::system_error: thread limit, cgroup pids) leaves its share to this thread -- nothing escapes the C ABI
+            const uint32_t n = hc.numPending, ways = (n >= 8192u && (flags & (uint32_t)ommCpuBakeFlags_EnableInternalThreads)) ? 4u : 1u;
+            std::vector<std::thread> helpers;
+            uint32_t started = 0;
+            try {
+                helpers.reserve(ways);
+                for (uint32_t w = 1; w < ways; ++w) { helpers.emplace_back(part, (uint32_t)((uint64_t)n * w / ways), (uint32_t)((uint64_t)n * (w + 1u) / ways)); started = w; }
+            } catch (...) {}
+            part(0u, (uint32_t)((uint64_t)n / ways));
+            for (auto& h : helpers) h.join();
+            for (uint32_t w = started + 1u; w < ways; ++w) part((uint32_t)((uint64_t)n * w / ways), (uint32_t)((uint64_t)n * (w + 1u) / ways));   // (shares whose thread did not start)
+        }
+        if (!HIP_OK(run_setup_fix_pending(S, tab.scratch, tab.scratchBytes, pend.data(), plv.data(), hc.numPending, tmp.p, stream))) return L.failure("[Failure] - device work-item setup failed");
+        return ommResult_SUCCESS;
+    }
+    // reads the desc and the texture; leaves the classification parameters P
+    void classify_params()
+    {
+        memset(&P, 0, sizeof P);
+        P.mipCount = (int)tex.mips.size();
+        for (int m = 0; m < P.mipCount; ++m) P.mips[m] = dev_mip(tex.mips[m]);
+        P.pow2Dispatch = P.mips[0].pow2;
+        P.texIsFp32 = tex.format == ommCpuTextureFormat_FP32;
+        P.addrMode = d.runtimeSamplerDesc.addressingMode;
+        P.filterLinear = d.runtimeSamplerDesc.filter == ommTextureFilterMode_Linear;
+        P.format = storeBits; P.promotion = d.unknownStatePromotion; P.stateGT = d.alphaCutoffGreater; P.stateLE = d.alphaCutoffLessEqual;
+        P.useCoarse = tex.mips[0].sat != nullptr && P.mipCount == 1 && P.filterLinear;
+        P.cutoff = d.alphaCutoff; P.borderAlpha = d.runtimeSamplerDesc.borderAlpha;
+        P.wantKnownCount = d.rejectionThreshold > 0.f;
+        P.noFine = has_flag(flags, kBakeFlag_DisableFineClassification);   // (bake_cpu_impl.cpp:45,822-823)
+        P.altKernel = has_flag(flags, kBakeFlag_DisableLevelLineIntersection) ? (has_flag(flags, kBakeFlag_EnableAABBTesting) ? 2 : 1) : 0;   // (bake_cpu_impl.cpp:44-45,915-966)
+    }
+    // level-0 hierarchical query per item + compaction of the items that need per-micro-triangle work: reads the work items; leaves mask, active, activeIds, stateOfs
+    // and the final counters on the host (hc, U) -- the ONE synchronisation of a bake before its result
+    ommResult triage_and_compact()
+    {
+        launch_triage(P, tab.uv, tab.level, tab.degen, tab.counters, maxItems, tab.mask, tab.active, tab.scratch, stream);
+        hostBlock = arena->host_block();
+        SetupCounters* const hcDst = hostBlock ? (SetupCounters*)hostBlock : &hc;
+        if (!HIP_OK(run_prep(tab.itemIds, tab.active, tab.level, storeBits, maxItems, tab.counters, tab.activeIds, tab.stateOfs, tab.scratch, tab.scratchBytes, stream)) ||
+            !HIP_OK(hipMemcpyAsync(hcDst, tab.counters, sizeof hc, hipMemcpyDeviceToHost, stream)) || !HIP_OK(hipStreamSynchronize(stream)))
+            return L.failure("[Failure] - device work-list compaction failed");
+        if (hostBlock) memcpy(&hc, hcDst, sizeof hc);
+        U = hc.numItems; numActive = hc.activeStart[kNumLevels]; microAll = (double)micro_triangles_of(hc.levelCount);
+        return ommResult_SUCCESS;
+    }
+    // reads the counters; leaves the reference's messages about the workload, or its refusals
+    ommResult report_workload()
+    {
+        if (has_flag(flags, ommCpuBakeFlags_EnableValidation) && hc.numDisabled != 0) { // bake_cpu_impl.cpp:652-657
+            char buf[256];
+            snprintf(buf, sizeof buf, "[Info] - The workload consists of %d unclassifiable triangles, these will be classified as unresolvedTriState = %s.", hc.numDisabled, special_name(d.unresolvedTriState));
+            L.msg(ommMessageSeverity_Info, buf);
+        }
+        // ---- ValidateWorkloadSize (bake_cpu_impl.cpp:662-713) ----
+        if (has_flag(flags, ommCpuBakeFlags_EnableWorkloadValidation) || d.maxWorkloadSize != 0xFFFFFFFFFFFFFFFFull) {
+            if (d.maxWorkloadSize != 0xFFFFFFFFFFFFFFFFull && hc.workload > d.maxWorkloadSize) return ommResult_WORKLOAD_TOO_BIG;
+            if (has_flag(flags, ommCpuBakeFlags_EnableWorkloadValidation) && hc.workload > (1ull << 27)) {
+                char buf[256];
+                snprintf(buf, sizeof buf, "[Perf Warning] - The workload consists of %lld work items (number of texels to classify), which corresponds to roughly %lld 1024x1024 textures."
+                         " This is unusually large and may result in long bake times.", (long long)hc.workload, (long long)(hc.workload >> 20));
+                L.msg(ommMessageSeverity_PerfWarning, buf);
+            }
+        }
+        if (has_flag(flags, kBakeFlag_EnableAABBTesting) && !has_flag(flags, kBakeFlag_DisableLevelLineIntersection))   // bake_cpu_impl.cpp:718-719 (ResampleCoarse is the first to look, behind the workload validation)
+            return L.invalid("[Invalid Arg] - EnableAABBTesting can't be used without also setting DisableLevelLineIntersection");
+        return ommResult_SUCCESS;
+    }
+    // reads the counters and the mode; leaves this rank's ranges, the two shape decisions (streamed result, with its host array; deferred generic pass) and the states arena
+    // reserved and carved.  The decisions themselves are bake_host.h's.
+    ommResult plan_states()
+    {
+        memset(&bounds, 0, sizeof bounds);
+        bounds.rank = sh ? sh->rank : 0; bounds.world = sh ? sh->world : 1;
+        rank_ranges(hc.activeStart, bounds.rank, bounds.world, bounds.b, lvlFirst, lvlCount);
+        // streamed result (ommCpuBake)?  (with special indices disabled every uniform item is a block too: the plain path handles that)
+        if (so && numActive && !has_flag(flags, ommCpuBakeFlags_DisableSpecialIndices) && !P.altKernel && storeBits == bits) {
+            const uint32_t k = stream_range_count(hc.stateBytes, microAll, hc.workload, so->compressedAvailable, so->forced, so->chunksWanted);
+            if (k && so->set->pinned.reserve(4096) && (hostArray = so->alloc(so->allocUser, hc.stateBytes, &hostPinned)) != nullptr) { streamChunks = k; hCursor = (unsigned long long*)so->set->pinned.base; }
+        }
+        // the queue of open tiles (kTileRecordBytes records, bake_kernels.hip)
+        const size_t queueBytes = (size_t)classify_queue_records(lvlCount, streamChunks > 1) * kTileRecordBytes + 16;
+        // deferred generic pass?  Not for streamed bakes (a range must be complete when its queue sections are); a sharded rank defers the walks of its share like a
+        // single GPU does (asset-sized cards, 8 ranks: 15.0 -> 12 ms per step), except when the ranks merge their states by summation.
+        if (generic_pass_wanted(baker.knob(ommxBakerKnob_GenericPass), microAll, hc.workload) && !streamChunks && !(sh && sh->mergeStates) && !ht && numActive)
+            genericCapacity = generic_pass_capacity(hc.stateBytes, storeBits);
+        if (!statesArena->reserve(carve_bake_states(0, hc.stateBytes, queueBytes, streamChunks != 0, genericCapacity).bytes)) return L.failure("[Failure] - out of device memory for the packed micro-triangle states");
+        st = carve_bake_states((uintptr_t)statesArena->base, hc.stateBytes, queueBytes, streamChunks != 0, genericCapacity);
+        e1b = et.mark();
+        return ommResult_SUCCESS;
+    }
+    // sharded bakes only: reads the active lists; leaves the states zeroed where the ranks merge them by summation, and every level's list interleaved, which evens
+    // out the per-rank cost (tail_kernels.hip: shard_interleave)
+    ommResult permute_for_ranks()
+    {
+        if (sh && sh->mergeStates && !HIP_OK(hipMemsetAsync(st.states, 0, st.stateBytes, stream))) return L.failure("[Failure] - device memset failed");
+        if (!sh || sh->world <= 1) return ommResult_SUCCESS;
         // the permuted copy goes through the (idle) setup / tail scratch block: no allocation, no synchronisation, stream ordered
         uint32_t* tmp = (uint32_t*)tab.scratch;
-        bool okp = (size_t)hc.activeStart[kNumLevels] * 4 <= tab.scratchBytes;
+        bool okp = (size_t)numActive * 4 <= tab.scratchBytes;
         for (int l = 0; l < kNumLevels && okp; ++l) {
             const uint32_t a = hc.activeStart[l], cnt = hc.activeStart[l + 1] - hc.activeStart[l];
             if (cnt < 3) continue;
-            uint32_t stride = (uint32_t)((double)cnt * 0.6180339887498949); if (stride < 1) stride = 1;
-            auto gcd = [](uint32_t x, uint32_t y) { while (y) { const uint32_t t = x % y; x = y; y = t; } return x; };
-            while (gcd(stride, cnt) != 1) ++stride;   // (cnt - 1 is always coprime: terminates)
-            launch_shard_interleave(tab.activeIds + a, tmp + a, cnt, stride % cnt, stream);
+            launch_shard_interleave(tab.activeIds + a, tmp + a, cnt, interleave_stride(cnt), stream);
             okp = HIP_OK(hipMemcpyAsync(tab.activeIds + a, tmp + a, (size_t)cnt * 4, hipMemcpyDeviceToDevice, stream));
         }
-        if (!okp) return L.failure("[Failure] - shard permutation failed");
+        return okp ? ommResult_SUCCESS : L.failure("[Failure] - shard permutation failed");
     }
-    // streamed: the active lists in the order of the final result, events behind the classification launches, the cursor published to a pinned word after each
-    struct EventList { hipEvent_t ev[2 * kMaxClassifyChunks + 3]; uint32_t n = 0; ~EventList() { for (uint32_t k = 0; k < n; ++k) (void)hipEventDestroy(ev[k]); } } chunkEvents;   // placement done [K + 1] | fences [K + 2]
-    StreamCtx sc; ClassifyChunks cc; memset(&cc, 0, sizeof cc); cc.count = 1;
-    MarkCtx mk; mk.et = &et; mk.mark = -1; mk.markGeneric = -1;
-    const bool noDedup = has_flag(flags, ommCpuBakeFlags_DisableDuplicateDetection);
-    int pv0 = -1, pv1 = -1;   // HIP event marks around the preview of a streamed bake
-    if (streamChunks) {
-        bool oks = HIP_OK(hipMemsetAsync(tab.placed, 0xFF, (size_t)maxItems * 8, stream)) && HIP_OK(hipMemsetAsync(tab.cursor, 0, 8, stream)) && HIP_OK(hipMemsetAsync(tab.streamCtl, 0, sizeof(uint32_t) * kStreamCtlWords, stream));
-        oks = oks && HIP_OK(run_stream_begin(tab.activeIds, numActiveAll, tab.uv, tab.level, tab.scratch, tab.scratchBytes, stream));
-        for (uint32_t k = 0; oks && k < 2u * streamChunks + 3u; ++k) { oks = HIP_OK(hipEventCreateWithFlags(&chunkEvents.ev[k], hipEventDisableTiming)); chunkEvents.n += oks ? 1u : 0u; }
-        if (!oks) return L.failure("[Failure] - could not set up the streamed result");
-        sc.stream = stream; sc.place = so->placeStream; sc.fences = chunkEvents.ev + streamChunks + 1u; sc.activeIds = tab.activeIds; sc.numActive = numActiveAll; sc.scratch = tab.scratch; sc.scratchBytes = tab.scratchBytes; sc.digests = tab.digests;
-        sc.cursor = tab.cursor; sc.stage = dStage; sc.placed = tab.placed; sc.ctl = tab.streamCtl; sc.hostCursor = hCursor; sc.events = chunkEvents.ev; sc.numEvents = streamChunks + 1u; sc.recorded = 0; sc.ok = true;
-        memset(&sc.proto, 0, sizeof sc.proto);
-        sc.proto.stateMask = tab.mask; sc.proto.knownCount = tab.known; sc.proto.digests = tab.digests; sc.proto.states = dStates; sc.proto.stateOfs = tab.stateOfs;
-        sc.proto.rejectionThreshold = d.rejectionThreshold; sc.proto.bits = bits; sc.proto.disableDedup = noDedup ? 1 : 0;
-        cc.count = streamChunks; cc.after = stream_hook; cc.mark = stream_mark_hook; cc.user = &sc; cc.early = nullptr; sc.queueCtl = dQueueCtl;
-        sc.paired = streamChunks > 1; sc.earlyList = nullptr; sc.earlyCapacity = 0; sc.itemLevel = tab.level;
-        sc.waitSeconds = 4.0 + 100.0 * 1e-3 * (2.5e-10 * microAll + 4e-9 * (double)hc.workload);   // (100 x the estimate of the whole classification, never below 4 s)
-        // preview (tail_kernels.hip): level-5 classification of the items of level >= 6 into buffers of its own; items that share their preview are classified early
-        const uint32_t first6 = hc.activeStart[6], count6 = numActiveAll - hc.activeStart[6];
-        if (count6 && streamChunks > 1) {
-            pv0 = et.mark();
-            ClassifyParams P2 = P; P2.format = 2; P2.promotion = 1; P2.wantKnownCount = 0; P2.noFine = 0;
-            ItemArrays A2 = A; A2.uv = tab.uv2; A2.stateOfs = tab.ofs2; A2.states = tab.states2; A2.stateMask = tab.mask2; A2.fineCount = tab.fine2;   // (its level-line statistic goes nowhere)
-            bool okp = HIP_OK(hipMemsetAsync(tab.early, 0, maxItems, stream)) && HIP_OK(hipMemsetAsync(tab.mask2, 0, (size_t)maxItems * 4, stream));
-            launch_stream_preview_prepare(tab.activeIds + first6, count6, tab.uv, P.mips[0].fw, P.mips[0].fh, tab.uv2, tab.ofs2, tab.early, stream);
-            {   // the preview items as ONE level-5 class of the ordinary classification: a 1024-tile each, tile triage (most previews are settled by one SAT
-                // query), LDS window and the single-texel pass for the rest -- through the bake's own tile queue, which is free until the real launch
-                static_assert(kPreviewLevel == 5, "the preview is the 1024-tile class");
-                uint32_t first2[kNumLevels], count2[kNumLevels];
-                for (int l = 0; l < kNumLevels; ++l) { first2[l] = 0; count2[l] = 0; }
-                first2[kPreviewLevel] = first6; count2[kPreviewLevel] = count6;
-                okp = okp && HIP_OK(launch_classify(P2, A2, tab.activeIds, first2, count2, dTileQueue, dQueueCtl, device_cu_count(), stream, nullptr));
-            }
-            ClassifyPlan plan; classify_plan(lvlFirst, lvlCount, streamChunks, &plan);   // (the ranges launch_classify will cut)
-            okp = okp && HIP_OK(run_stream_preview_flags(tab.activeIds + first6, count6, first6, numActiveAll, tab.states2, tab.level, tab.early, tab.streamCtl, tab.scratch, tab.scratchBytes, tab.earlyLead, tab.earlyList, plan, stream));
-            if (!okp) return L.failure("[Failure] - could not set up the streamed result");
-            cc.early = tab.early; cc.earlyLead = tab.earlyLead; cc.earlyStage = dStage; sc.proto.early = tab.early; sc.earlyList = tab.earlyList; sc.earlyCapacity = count6;
-            pv1 = et.mark();
+    // ResampleCoarse + ResampleFine (bake_cpu_impl.cpp:715-1029) on the active items: reads the work items, this rank's ranges and the plan; leaves the packed states
+    // (streamed: the placement enqueued behind every range, through `sr`)
+    ommResult classify(StreamRun& sr)
+    {
+        A.uv = tab.uv; A.degenerate = tab.degen; A.stateOfs = tab.stateOfs; A.states = st.states; A.stateMask = tab.mask; A.knownCount = tab.known; A.fineCount = tab.fine;
+        // (tab.fine was zeroed by the first set-up launch, with the known counts)
+        memset(&cc, 0, sizeof cc); cc.count = 1;
+        mk.et = &et; mk.mark = -1; mk.markGeneric = -1;
+        if (streamChunks) { if (const ommResult r = sr.begin(*this)) return r; }
+        else { cc.mark = mark_hook; cc.user = &mk; cc.early = nullptr; }   // (HIP event in front of the persistent launch of the levels >= 6)
+        if (genericCapacity) {
+            if (!HIP_OK(hipMemsetAsync(st.genericCount, 0, 256, stream))) return L.failure("[Failure] - device memset failed");
+            cc.generic.count = (unsigned long long*)st.genericCount; cc.generic.entries = (uint2*)st.genericEntries; cc.generic.capacity = (uint32_t)genericCapacity;
+            cc.markGeneric = mark_generic_hook;   // (cc.user is the MarkCtx: a deferred pass and a streamed result exclude each other)
         }
-    } else { cc.mark = mark_hook; cc.user = &mk; cc.early = nullptr; }   // (HIP event in front of the persistent launch of the levels >= 6)
-    if (dGeneric) {
-        if (!HIP_OK(hipMemsetAsync(dGeneric, 0, 256, stream))) return L.failure("[Failure] - device memset failed");
-        cc.generic.count = (unsigned long long*)dGeneric; cc.generic.entries = (uint2*)(dGeneric + 256); cc.generic.capacity = (uint32_t)genericCapacity;
-        cc.markGeneric = mark_generic_hook;   // (cc.user is the MarkCtx: a deferred pass and a streamed result exclude each other)
+        if (!HIP_OK(launch_classify(P, A, tab.activeIds, lvlFirst, lvlCount, st.tileQueue, st.queueCtl, device_cu_count(), stream, &cc))) return L.failure("[Failure] - kernel launch failed");
+        if (streamChunks && !sr.sc.ok) return L.failure("[Failure] - kernel launch failed");
+        e2 = et.mark();
+        return ommResult_SUCCESS;
     }
-    if (!HIP_OK(launch_classify(P, A, tab.activeIds, lvlFirst, lvlCount, dTileQueue, dQueueCtl, device_cu_count(), stream, &cc))) return L.failure("[Failure] - kernel launch failed");
-    if (streamChunks && !sc.ok) return L.failure("[Failure] - kernel launch failed");
-    const int e2 = et.mark();
-    if (ht) { // bring the per-micro-triangle states to the host for the serial tail (host_tail.cpp)
-        const ommResult gr = gather_host_items(L, stream, U, T, hc, tab.uv, tab.level, tab.active, tab.mask, tab.stateOfs, dStates, tab.triToItem, bits, ht->items);
+    // host-tail bakes end here: reads the per-micro-triangle states; leaves them on the host for the serial tail (host_tail.cpp), and the timings so far
+    ommResult gather_for_host_tail()
+    {
+        const ommResult gr = gather_host_items(L, stream, U, T, hc, tab.uv, tab.level, tab.active, tab.mask, tab.stateOfs, st.states, tab.triToItem, bits, ht->items);
         tm.setupMs = et.ms(e0, e1); tm.triageMs = et.ms(e1, e1b); tm.classifyMs = et.ms(e1b, e2); tm.uniqueItems = U;
         return gr;
     }
-    // ---- CalcDigest (bake_cpu_impl.cpp:1038-1040): active items here, uniform ones from the table in the tail ----
-    if (!noDedup && !streamChunks)   // (a streamed bake computed them range by range)
-        launch_digest_levels(dStates, tab.stateOfs, tab.activeIds, lvlFirst, lvlCount, (uint32_t)storeBits, tab.digests, stream);
-    if (!HIP_OK(hipGetLastError())) return L.failure("[Failure] - kernel launch failed");
-    const int e3 = et.mark();
-    // ---- streamed result: everything is enqueued; follow the classification launches and send what each one placed ----
-    uint64_t sent = 0;
-    SdmaCopier localSdma;   // (ommCpuBake: StreamOut's; its destructor waits for copies in flight: error paths included)
-    SdmaCopier& sdma = so ? so->sdma : localSdma;
-    if (streamChunks) {
-        const bool useSdma = hostPinned && sdma.open(so->device);
-        for (uint32_t k = 0; k < sc.recorded; ++k) {
-            if (!HIP_OK(hipEventSynchronize(chunkEvents.ev[k]))) return L.failure("[Failure] - the classification failed");
-            if (k + 1u == sc.recorded) so->classifyEndMs = now_ms();
-            if (k < 32u) tm.streamRangeReadyMs[k] = (float)(now_ms() - coreT0);
-            const uint64_t cur = *(volatile unsigned long long*)(hCursor + k);
-            if (cur > sent) {
-                // (a copy the DMA engine refuses goes through the HIP runtime instead of failing the bake)
-                const bool okc = cur <= hc.stateBytes && ((useSdma && sdma.copy_to_host(hostArray + sent, dStage + sent, (size_t)(cur - sent)))
-                                                          || HIP_OK(hipMemcpyAsync(hostArray + sent, dStage + sent, (size_t)(cur - sent), hipMemcpyDeviceToHost, so->copyStream)));
-                if (!okc) return L.failure("[Failure] - device to host transfer of the bake result failed");
-                if (sent == 0) tm.streamFirstCopyMs = (float)(now_ms() - coreT0);
-                tm.streamLastCopyMs = (float)(now_ms() - coreT0);
-                sent = cur;
-            }
-        }
+    // CalcDigest (bake_cpu_impl.cpp:1038-1040): reads the packed states of the active items; leaves their digests (uniform items: from the table, in the tail)
+    ommResult digest()
+    {
+        if (!noDedup && !streamChunks)   // (a streamed bake computed them range by range)
+            launch_digest_levels(st.states, tab.stateOfs, tab.activeIds, lvlFirst, lvlCount, (uint32_t)storeBits, tab.digests, stream);
+        if (!HIP_OK(hipGetLastError())) return L.failure("[Failure] - kernel launch failed");
+        e3 = et.mark();
+        return ommResult_SUCCESS;
     }
-    // ---- promote / dedup / sort / offsets on the device ----
-    TailInputs ti; memset(&ti, 0, sizeof ti);
-    ti.numItems = U; ti.numTris = T; ti.uv = tab.uv; ti.level = tab.level; ti.stateMask = tab.mask; ti.knownCount = tab.known; ti.digests = tab.digests;
-    ti.uniformDigest = tab.uniformDigest; ti.triToItem = tab.triToItem; ti.format = bits;
-    // every work item outside the active lists is uniform, and uniform items of one level and state share a digest: at most 13 x 4 of those
-    ti.maxDistinctDigests = hc.activeStart[kNumLevels] + 64u;
-    ti.disableSpecial = has_flag(flags, ommCpuBakeFlags_DisableSpecialIndices); ti.disableDedup = noDedup;
-    ti.rejectionThreshold = d.rejectionThreshold; ti.unresolved = (int32_t)d.unresolvedTriState; ti.errorFlag = tab.err;
-    TailOutputs to; memset(&to, 0, sizeof to);
-    to.special = tab.special; to.rep = tab.rep; to.order = tab.order; to.dstOfs = tab.dstOfs; to.sizes = tab.sizes; to.itemValue = tab.itemValue;
-    to.indexBuffer = tab.index; to.arrayHist = tab.arrayHist; to.indexHist = tab.indexHist;
-    if (sh) { // sharded bake: hand the per-item metadata of this rank's share to the caller and stop here (ommxShardedBegin)
-        const uint32_t numActive = hc.activeStart[kNumLevels];
-        sh->bounds = bounds; sh->ti = ti; sh->to = to; sh->hc = hc; sh->dStates = dStates; sh->tab = tab;
+    // reads the tables; leaves the tail's inputs and outputs (promote / dedup / sort / offsets on the device) -- what a sharded bake hands to its later phases
+    void tail_inputs()
+    {
+        memset(&ti, 0, sizeof ti);
+        ti.numItems = U; ti.numTris = T; ti.uv = tab.uv; ti.level = tab.level; ti.stateMask = tab.mask; ti.knownCount = tab.known; ti.digests = tab.digests;
+        ti.uniformDigest = tab.uniformDigest; ti.triToItem = tab.triToItem; ti.format = bits;
+        ti.maxDistinctDigests = max_distinct_digests(numActive);
+        ti.disableSpecial = has_flag(flags, ommCpuBakeFlags_DisableSpecialIndices); ti.disableDedup = noDedup;
+        ti.rejectionThreshold = d.rejectionThreshold; ti.unresolved = (int32_t)d.unresolvedTriState; ti.errorFlag = tab.err;
+        memset(&to, 0, sizeof to);
+        to.special = tab.special; to.rep = tab.rep; to.order = tab.order; to.dstOfs = tab.dstOfs; to.sizes = tab.sizes; to.itemValue = tab.itemValue;
+        to.indexBuffer = tab.index; to.arrayHist = tab.arrayHist; to.indexHist = tab.indexHist;
+    }
+    // sharded bakes end here (ommxShardedBegin): reads everything above; leaves it in the ShardCtx, with the metadata words of this rank's share packed for the exchange
+    ommResult hand_to_shard()
+    {
+        sh->bounds = bounds; sh->ti = ti; sh->to = to; sh->hc = hc; sh->dStates = st.states; sh->tab = tab;
         sh->flags = flags; sh->T = T; sh->bits = bits;
         launch_shard_pack_meta(bounds, tab.activeIds, numActive, tab.mask, tab.known, tab.digests, tab.meta, stream);
         if (!sh->asyncBegin && !HIP_OK(hipStreamSynchronize(stream))) return L.failure("[Failure] - sharded classification failed");   // (the one-call RCCL path stays on the stream)
@@ -1089,90 +1061,197 @@ ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInpu
         tm.microTriangles += micro_triangles_of(hc.levelCount);
         return ommResult_SUCCESS;
     }
-    // the index format depends on the triangle count alone: the tail's index kernel writes the narrowed buffer next to the int32 one (bake_cpu_impl.cpp:1872-1902)
-    R.indexFormat = index_format_for(T, flags);
-    R.index = R.dev_alloc((size_t)(T ? T : 1) * 4); // the reference narrows in place inside an int32 vector (:1882-1900)
-    if (!R.index) return L.failure("[Failure] - could not allocate the device result");
-    to.narrowIndex = R.index; to.narrowBytes = (int)index_bytes(R.indexFormat);
-    TailCounts counts;
-    if (!HIP_OK(run_tail(ti, to, tab.scratch, tab.scratchBytes, &counts, stream, hostBlock ? hostBlock + 256 : nullptr))) return L.failure("[Failure] - device tail failed");
-    if (counts.arrayDataSize > 0xFFFFFFFFull) return ommResult_FAILURE; // bake_cpu_impl.cpp:1774-1775
-    const int e4 = et.mark();
-
-    // ---- Serialize (bake_cpu_impl.cpp:1756-1920): gather the surviving blocks into arrayData order, descriptors, index narrowing ----
-    const uint32_t E = counts.numOmms;
-    R.bits = bits; R.numDescs = E; R.arrayDataSize = E ? counts.arrayDataSize : 0; R.numTris = T;
-    ok = true;
-    bool streamed = false;
-    if (streamChunks) {
-        // the blocks are (or will shortly be) at their final offsets in the caller's array, provided the speculative placement equals the exact layout the
-        // tail has just produced: compare, and fall back to the ordinary gather + copy otherwise
-        uint32_t hctl[4] = { 0u, 0u, 0u, 0u };
-        launch_stream_verify(tab.order, tab.dstOfs, E, tab.placed, tab.streamCtl, stream);
-        if (!HIP_OK(hipMemcpyAsync(hctl, tab.streamCtl, sizeof hctl, hipMemcpyDeviceToHost, stream)) || !HIP_OK(hipStreamSynchronize(stream)))
-            return L.failure("[Failure] - could not verify the streamed result");
-        streamed = hctl[2] == 0u && sent == R.arrayDataSize;
-        if (!streamed) {
-            (void)so->finish();   // (the caller is about to overwrite the host array with the ordinary copy: nothing of the discarded stream may still be landing in it)
-            char buf[256];
-            snprintf(buf, sizeof buf, "[Perf Warning] - the streamed result was discarded (%u blocks placed / %u expected, %llu bytes / %llu expected, duplicate owned by a later range: %u): "
-                     "falling back to one copy after the bake", hctl[0], E, (unsigned long long)sent, (unsigned long long)R.arrayDataSize, hctl[1]);
-            L.msg(ommMessageSeverity_PerfWarning, buf);
-        }
-        so->chunks = streamChunks; so->streamedBytes = sent; so->used = streamed; so->fellBack = !streamed;
-        tm.streamChunks = streamed ? streamChunks : 0u; tm.streamedBytes = sent; tm.streamEarlyItems = hctl[3];
+    // promote / dedup / sort / offsets on the device: reads ti; leaves the tail's tables, the index buffer of the result, `counts`, and the result's sizes in R
+    ommResult tail()
+    {
+        // the index format depends on the triangle count alone: the tail's index kernel writes the narrowed buffer next to the int32 one (bake_cpu_impl.cpp:1872-1902)
+        R.indexFormat = index_format_for(T, flags);
+        R.index = R.dev_alloc((size_t)(T ? T : 1) * 4); // the reference narrows in place inside an int32 vector (:1882-1900)
+        if (!R.index) return L.failure("[Failure] - could not allocate the device result");
+        to.narrowIndex = R.index; to.narrowBytes = (int)index_bytes(R.indexFormat);
+        if (!HIP_OK(run_tail(ti, to, tab.scratch, tab.scratchBytes, &counts, stream, hostBlock ? hostBlock + 256 : nullptr))) return L.failure("[Failure] - device tail failed");
+        if (counts.arrayDataSize > 0xFFFFFFFFull) return ommResult_FAILURE; // bake_cpu_impl.cpp:1774-1775
+        e4 = et.mark();
+        R.bits = bits; R.numDescs = counts.numOmms; R.arrayDataSize = counts.numOmms ? counts.arrayDataSize : 0; R.numTris = T;
+        return ommResult_SUCCESS;
     }
-    if (E) {
+    // Serialize (bake_cpu_impl.cpp:1756-1920): reads the tail's order and offsets; leaves the descriptors and, unless the streamed result stands, the surviving blocks
+    // gathered into arrayData order.  false: an allocation failed (reported by read_back_statistics, behind the read-backs it still queues)
+    bool materialise()
+    {
+        const uint32_t E = counts.numOmms;
+        if (!E) return true;
         R.descs = (ommCpuOpacityMicromapDesc*)R.dev_alloc(sizeof(ommCpuOpacityMicromapDesc) * (size_t)E);
         if (!streamed) R.arrayData = (uint8_t*)R.dev_alloc((size_t)counts.arrayDataSize);
-        ok = R.descs != nullptr && (streamed || R.arrayData != nullptr);
-        if (ok) {
-            if (!streamed) {
-                uint8_t* unitCodes = nullptr; uint32_t* blockRawCounts = nullptr;
-                if (R.gatherCodes && storeBits == bits && counts.smallOmms == 0 && !R.gatherCodes(counts.arrayDataSize, &unitCodes, &blockRawCounts)) { unitCodes = nullptr; blockRawCounts = nullptr; }
-                launch_gather_omms(dStates, tab.stateOfs, tab.active, tab.mask, tab.level, bits, storeBits, tab.order, tab.dstOfs, tab.sizes, E, R.arrayData, stream, unitCodes, blockRawCounts, R.descs);
-            } else launch_write_descs(tab.order, tab.dstOfs, tab.level, bits, E, R.descs, stream);   // (the gather writes the descriptors of its OMMs itself)
+        if (R.descs == nullptr || (!streamed && R.arrayData == nullptr)) return false;
+        if (!streamed) {
+            uint8_t* unitCodes = nullptr; uint32_t* blockRawCounts = nullptr;
+            if (R.gatherCodes && storeBits == bits && counts.smallOmms == 0 && !R.gatherCodes(counts.arrayDataSize, &unitCodes, &blockRawCounts)) { unitCodes = nullptr; blockRawCounts = nullptr; }
+            launch_gather_omms(st.states, tab.stateOfs, tab.active, tab.mask, tab.level, bits, storeBits, tab.order, tab.dstOfs, tab.sizes, E, R.arrayData, stream, unitCodes, blockRawCounts, R.descs);
+        } else launch_write_descs(tab.order, tab.dstOfs, tab.level, bits, E, R.descs, stream);   // (the gather writes the descriptors of its OMMs itself)
+        return true;
+    }
+    // reads the two histograms, the consistency word and the striped statistic counters, taken from the arena back to back (ONE read-back), the classification's
+    // control words and the generic pass's; leaves R.hist and the statistics, and the stream idle -- the second and last wait of a bake
+    ommResult read_back_statistics(bool ok)
+    {
+        std::vector<unsigned long long> fineSlots((size_t)kFineSlots * kFineStride, 0ull);
+        const size_t spanBytes = tab.readback_bytes();
+        // (into the arena's pinned block when there is one: three copies queued, ONE wait -- into pageable memory each copy is a wait of its own)
+        uint32_t hostCtlLocal[kClassifyCtlWords];
+        unsigned long long genericLocal[3] = { 0, 0, 0 };
+        static_assert(sizeof genericLocal == kGenericReadbackBytes, "the generic pass's words as readback_slots places them");
+        const ReadbackSlots at = readback_slots(spanBytes);
+        const bool pinnedBack = hostBlock && at.fits;
+        std::vector<uint8_t> spanLocal(pinnedBack ? 0 : spanBytes);
+        uint8_t* const span = pinnedBack ? hostBlock + at.spanAt : spanLocal.data();
+        uint32_t* const hostCtl = pinnedBack ? (uint32_t*)(hostBlock + at.ctlAt) : hostCtlLocal;
+        unsigned long long* const genericWords = pinnedBack ? (unsigned long long*)(hostBlock + at.genAt) : genericLocal;
+        memset(hostCtl, 0, sizeof hostCtlLocal); memset(genericWords, 0, sizeof genericLocal);
+        ok = ok && HIP_OK(hipMemcpyAsync(span, tab.arrayHist, spanBytes, hipMemcpyDeviceToHost, stream));
+        if (numActive) ok = ok && HIP_OK(hipMemcpyAsync(hostCtl, st.queueCtl, sizeof hostCtlLocal, hipMemcpyDeviceToHost, stream));
+        if (genericCapacity) ok = ok && HIP_OK(hipMemcpyAsync(genericWords, st.genericCount, sizeof genericLocal, hipMemcpyDeviceToHost, stream));
+        e5 = et.mark();
+        ok = ok && HIP_OK(hipStreamSynchronize(stream));
+        // (a streamed result may still be on its way to the host: the caller queues its small read-backs first and then waits, StreamOut::finish)
+        if (!ok) return L.failure("[Failure] - could not materialise the bake result on the device");
+        memcpy(R.hist, span, sizeof(uint32_t) * kNumLevels);
+        memcpy(R.hist + kNumLevels, span + ((const uint8_t*)tab.indexHist - (const uint8_t*)tab.arrayHist), sizeof(uint32_t) * kNumLevels);
+        memcpy(fineSlots.data(), span + ((const uint8_t*)tab.fine - (const uint8_t*)tab.arrayHist), sizeof(unsigned long long) * fineSlots.size());
+        for (int k = 0; k < kFineSlots; ++k) fineCount += fineSlots[(size_t)k * kFineStride];
+        queueTails[1] = hostCtl[kCtl1024 + kSecTails]; for (uint32_t k = 0; k < kMaxClassifyChunks; ++k) queueTails[0] += hostCtl[kSecTails + k];   // (1024-tile queue; sections of the 4096-tile queue)
+        genericMicro = genericWords[2];
+        return ommResult_SUCCESS;
+    }
+    // reads the event marks (all complete) and the statistics; leaves the timings of a whole bake
+    void fill_timings(const StreamRun& sr)
+    {
+        tm.uploadMs = 0.f; tm.hostSetupMs = 0.f; tm.setupMs = et.ms(e0, e1); tm.triageMs = et.ms(e1, e1b); tm.classifyMs = et.ms(e1b, e2); tm.digestMs = et.ms(e2, e3);
+        tm.streamPreviewMs = sr.pv0 >= 0 ? et.ms(sr.pv0, sr.pv1) : 0.f;
+        tm.tailMs = et.ms(e3, e4); tm.gatherMs = et.ms(e4, e5); tm.persistentMs = mk.mark >= 0 ? et.ms(mk.mark, mk.markGeneric >= 0 ? mk.markGeneric : e2) : 0.f;
+        tm.genericMs = mk.markGeneric >= 0 ? et.ms(mk.markGeneric, e2) : 0.f; tm.genericMicroTriangles = genericMicro;
+        tm.openTiles = queueTails[0] + queueTails[1]; tm.openTileMicroTriangles = (uint64_t)queueTails[0] * 4096u + (uint64_t)queueTails[1] * 1024u;
+        tm.fineMicroTriangles = fineCount; tm.uniqueItems = U; tm.activeItems = numActive; tm.stateBytes = hc.stateBytes; tm.microTriangles = micro_triangles_of(hc.levelCount);
+        tm.classifyLaunches += classify_launches(hc.activeStart);
+    }
+};
+
+// streamed: the active lists in the order of the final result, events behind the classification launches, the cursor published to a pinned word after each
+ommResult StreamRun::begin(BakeRun& b)
+{
+    const BakeTables& tab = b.tab; const hipStream_t stream = b.stream; const uint32_t streamChunks = b.streamChunks, numActive = b.numActive;
+    ClassifyChunks& cc = b.cc;
+    bool oks = HIP_OK(hipMemsetAsync(tab.placed, 0xFF, (size_t)b.maxItems * 8, stream)) && HIP_OK(hipMemsetAsync(tab.cursor, 0, 8, stream)) && HIP_OK(hipMemsetAsync(tab.streamCtl, 0, sizeof(uint32_t) * kStreamCtlWords, stream));
+    oks = oks && HIP_OK(run_stream_begin(tab.activeIds, numActive, tab.uv, tab.level, tab.scratch, tab.scratchBytes, stream));
+    for (uint32_t k = 0; oks && k < 2u * streamChunks + 3u; ++k) { oks = HIP_OK(hipEventCreateWithFlags(&events.ev[k], hipEventDisableTiming)); events.n += oks ? 1u : 0u; }
+    if (!oks) return b.L.failure("[Failure] - could not set up the streamed result");
+    sc.stream = stream; sc.place = b.so->placeStream; sc.fences = events.ev + streamChunks + 1u; sc.activeIds = tab.activeIds; sc.numActive = numActive; sc.scratch = tab.scratch; sc.scratchBytes = tab.scratchBytes; sc.digests = tab.digests;
+    sc.cursor = tab.cursor; sc.stage = b.st.stage; sc.placed = tab.placed; sc.ctl = tab.streamCtl; sc.hostCursor = b.hCursor; sc.events = events.ev; sc.numEvents = streamChunks + 1u; sc.recorded = 0; sc.ok = true;
+    memset(&sc.proto, 0, sizeof sc.proto);
+    sc.proto.stateMask = tab.mask; sc.proto.knownCount = tab.known; sc.proto.digests = tab.digests; sc.proto.states = b.st.states; sc.proto.stateOfs = tab.stateOfs;
+    sc.proto.rejectionThreshold = b.d.rejectionThreshold; sc.proto.bits = b.bits; sc.proto.disableDedup = b.noDedup ? 1 : 0;
+    cc.count = streamChunks; cc.after = stream_hook; cc.mark = stream_mark_hook; cc.user = &sc; cc.early = nullptr; sc.queueCtl = b.st.queueCtl;
+    sc.paired = streamChunks > 1; sc.earlyList = nullptr; sc.earlyCapacity = 0; sc.itemLevel = tab.level;
+    sc.waitSeconds = stream_wait_seconds(b.microAll, b.hc.workload);
+    // preview (tail_kernels.hip): level-5 classification of the items of level >= 6 into buffers of its own; items that share their preview are classified early
+    const uint32_t first6 = b.hc.activeStart[6], count6 = numActive - b.hc.activeStart[6];
+    if (count6 && streamChunks > 1) {
+        pv0 = b.et.mark();
+        ClassifyParams P2 = b.P; P2.format = 2; P2.promotion = 1; P2.wantKnownCount = 0; P2.noFine = 0;
+        ItemArrays A2 = b.A; A2.uv = tab.uv2; A2.stateOfs = tab.ofs2; A2.states = tab.states2; A2.stateMask = tab.mask2; A2.fineCount = tab.fine2;   // (its level-line statistic goes nowhere)
+        bool okp = HIP_OK(hipMemsetAsync(tab.early, 0, b.maxItems, stream)) && HIP_OK(hipMemsetAsync(tab.mask2, 0, (size_t)b.maxItems * 4, stream));
+        launch_stream_preview_prepare(tab.activeIds + first6, count6, tab.uv, b.P.mips[0].fw, b.P.mips[0].fh, tab.uv2, tab.ofs2, tab.early, stream);
+        {   // the preview items as ONE level-5 class of the ordinary classification: a 1024-tile each, tile triage (most previews are settled by one SAT
+            // query), LDS window and the single-texel pass for the rest -- through the bake's own tile queue, which is free until the real launch
+            static_assert(kPreviewLevel == 5, "the preview is the 1024-tile class");
+            uint32_t first2[kNumLevels], count2[kNumLevels];
+            for (int l = 0; l < kNumLevels; ++l) { first2[l] = 0; count2[l] = 0; }
+            first2[kPreviewLevel] = first6; count2[kPreviewLevel] = count6;
+            okp = okp && HIP_OK(launch_classify(P2, A2, tab.activeIds, first2, count2, b.st.tileQueue, b.st.queueCtl, device_cu_count(), stream, nullptr));
+        }
+        ClassifyPlan plan; classify_plan(b.lvlFirst, b.lvlCount, streamChunks, &plan);   // (the ranges launch_classify will cut)
+        okp = okp && HIP_OK(run_stream_preview_flags(tab.activeIds + first6, count6, first6, numActive, tab.states2, tab.level, tab.early, tab.streamCtl, tab.scratch, tab.scratchBytes, tab.earlyLead, tab.earlyList, plan, stream));
+        if (!okp) return b.L.failure("[Failure] - could not set up the streamed result");
+        cc.early = tab.early; cc.earlyLead = tab.earlyLead; cc.earlyStage = b.st.stage; sc.proto.early = tab.early; sc.earlyList = tab.earlyList; sc.earlyCapacity = count6;
+        pv1 = b.et.mark();
+    }
+    return ommResult_SUCCESS;
+}
+// everything is enqueued: follow the classification launches and send what each one placed
+ommResult StreamRun::follow(BakeRun& b)
+{
+    StreamOut& so = *b.so; ommxBakeTimings& tm = b.tm;
+    SdmaCopier& sdma = so.sdma;   // (ommCpuBake's: it outlives the bake, the caller waits for the copies in flight, StreamOut::finish)
+    const bool useSdma = b.hostPinned && sdma.open(so.device);
+    for (uint32_t k = 0; k < sc.recorded; ++k) {
+        if (!HIP_OK(hipEventSynchronize(events.ev[k]))) return b.L.failure("[Failure] - the classification failed");
+        if (k + 1u == sc.recorded) so.classifyEndMs = now_ms();
+        if (k < 32u) tm.streamRangeReadyMs[k] = (float)(now_ms() - b.coreT0);
+        const uint64_t cur = *(volatile unsigned long long*)(b.hCursor + k);
+        if (cur > sent) {
+            // (a copy the DMA engine refuses goes through the HIP runtime instead of failing the bake)
+            const bool okc = cur <= b.hc.stateBytes && ((useSdma && sdma.copy_to_host(b.hostArray + sent, b.st.stage + sent, (size_t)(cur - sent)))
+                                                        || HIP_OK(hipMemcpyAsync(b.hostArray + sent, b.st.stage + sent, (size_t)(cur - sent), hipMemcpyDeviceToHost, so.copyStream)));
+            if (!okc) return b.L.failure("[Failure] - device to host transfer of the bake result failed");
+            if (sent == 0) tm.streamFirstCopyMs = (float)(now_ms() - b.coreT0);
+            tm.streamLastCopyMs = (float)(now_ms() - b.coreT0);
+            sent = cur;
         }
     }
-    // the two histograms, the consistency word and the striped statistic counters were taken from the arena back to back: ONE read-back
-    unsigned long long fineCount = 0;
-    std::vector<unsigned long long> fineSlots((size_t)kFineSlots * kFineStride, 0ull);
-    const size_t spanBytes = tab.readback_bytes();
-    // (into the arena's pinned block when there is one: three copies queued, ONE wait -- into pageable memory each copy is a wait of its own)
-    uint32_t hostCtlLocal[kClassifyCtlWords];
-    unsigned long long genericLocal[3] = { 0, 0, 0 };   // reservations (incl. null padding), the pass's cursor, micro-triangles it classified
-    const size_t spanAt = 1024, ctlAt = spanAt + pad256(spanBytes), genAt = ctlAt + sizeof hostCtlLocal;
-    const bool pinnedBack = hostBlock && genAt + sizeof genericLocal <= kHostBlockBytes;
-    std::vector<uint8_t> spanLocal(pinnedBack ? 0 : spanBytes);
-    uint8_t* const span = pinnedBack ? hostBlock + spanAt : spanLocal.data();
-    uint32_t* const hostCtl = pinnedBack ? (uint32_t*)(hostBlock + ctlAt) : hostCtlLocal;
-    unsigned long long* const genericWords = pinnedBack ? (unsigned long long*)(hostBlock + genAt) : genericLocal;
-    memset(hostCtl, 0, sizeof hostCtlLocal); memset(genericWords, 0, sizeof genericLocal);
-    ok = ok && HIP_OK(hipMemcpyAsync(span, tab.arrayHist, spanBytes, hipMemcpyDeviceToHost, stream));
-    uint32_t queueTails[2] = { 0u, 0u };   // open tiles of the two tile sizes (statistics)
-    if (hc.activeStart[kNumLevels]) ok = ok && HIP_OK(hipMemcpyAsync(hostCtl, dQueueCtl, sizeof hostCtlLocal, hipMemcpyDeviceToHost, stream));
-    if (dGeneric) ok = ok && HIP_OK(hipMemcpyAsync(genericWords, dGeneric, sizeof genericLocal, hipMemcpyDeviceToHost, stream));
-    const int e5 = et.mark();
-    ok = ok && HIP_OK(hipStreamSynchronize(stream));
-    // (a streamed result may still be on its way to the host: the caller queues its small read-backs first and then waits, StreamOut::finish)
-    if (!ok) return L.failure("[Failure] - could not materialise the bake result on the device");
-    memcpy(R.hist, span, sizeof(uint32_t) * kNumLevels);
-    memcpy(R.hist + kNumLevels, span + ((const uint8_t*)tab.indexHist - (const uint8_t*)tab.arrayHist), sizeof(uint32_t) * kNumLevels);
-    memcpy(fineSlots.data(), span + ((const uint8_t*)tab.fine - (const uint8_t*)tab.arrayHist), sizeof(unsigned long long) * fineSlots.size());
-
-    tm.uploadMs = 0.f; tm.hostSetupMs = 0.f; tm.setupMs = et.ms(e0, e1); tm.triageMs = et.ms(e1, e1b); tm.classifyMs = et.ms(e1b, e2); tm.digestMs = et.ms(e2, e3);
-    tm.streamPreviewMs = pv0 >= 0 ? et.ms(pv0, pv1) : 0.f;
-    tm.tailMs = et.ms(e3, e4); tm.gatherMs = et.ms(e4, e5); tm.persistentMs = mk.mark >= 0 ? et.ms(mk.mark, mk.markGeneric >= 0 ? mk.markGeneric : e2) : 0.f;
-    tm.genericMs = mk.markGeneric >= 0 ? et.ms(mk.markGeneric, e2) : 0.f; tm.genericMicroTriangles = genericWords[2];
-    for (int k = 0; k < kFineSlots; ++k) fineCount += fineSlots[(size_t)k * kFineStride];
-    queueTails[1] = hostCtl[kCtl1024 + kSecTails]; for (uint32_t k = 0; k < kMaxClassifyChunks; ++k) queueTails[0] += hostCtl[kSecTails + k];   // (1024-tile queue; sections of the 4096-tile queue)
-    tm.openTiles = queueTails[0] + queueTails[1]; tm.openTileMicroTriangles = (uint64_t)queueTails[0] * 4096u + (uint64_t)queueTails[1] * 1024u;
-    tm.fineMicroTriangles = fineCount; tm.uniqueItems = U; tm.activeItems = hc.activeStart[kNumLevels]; tm.stateBytes = hc.stateBytes; tm.microTriangles = micro_triangles_of(hc.levelCount);
-    {   // classify_tiles launches: one per level below 5, one for level 5, ONE for all levels >= 6 (bake_kernels.hip)
-        bool big = false;
-        for (int l = 0; l < kNumLevels; ++l) { const bool any = hc.activeStart[l + 1] != hc.activeStart[l]; if (l < 6) tm.classifyLaunches += any; else big = big || any; }
-        tm.classifyLaunches += big;
+    return ommResult_SUCCESS;
+}
+// the blocks are (or will shortly be) at their final offsets in the caller's array, provided the speculative placement equals the exact layout the tail has just
+// produced: compare, and fall back to the ordinary gather + copy otherwise
+ommResult StreamRun::verify(BakeRun& b)
+{
+    const BakeTables& tab = b.tab; StreamOut& so = *b.so; const uint32_t E = b.counts.numOmms;
+    uint32_t hctl[4] = { 0u, 0u, 0u, 0u };
+    launch_stream_verify(tab.order, tab.dstOfs, E, tab.placed, tab.streamCtl, b.stream);
+    if (!HIP_OK(hipMemcpyAsync(hctl, tab.streamCtl, sizeof hctl, hipMemcpyDeviceToHost, b.stream)) || !HIP_OK(hipStreamSynchronize(b.stream)))
+        return b.L.failure("[Failure] - could not verify the streamed result");
+    const bool streamed = hctl[2] == 0u && sent == b.R.arrayDataSize;
+    if (!streamed) {
+        (void)so.finish();   // (the caller is about to overwrite the host array with the ordinary copy: nothing of the discarded stream may still be landing in it)
+        char buf[256];
+        snprintf(buf, sizeof buf, "[Perf Warning] - the streamed result was discarded (%u blocks placed / %u expected, %llu bytes / %llu expected, duplicate owned by a later range: %u): "
+                 "falling back to one copy after the bake", hctl[0], E, (unsigned long long)sent, (unsigned long long)b.R.arrayDataSize, hctl[1]);
+        b.L.msg(ommMessageSeverity_PerfWarning, buf);
     }
+    so.chunks = b.streamChunks; so.streamedBytes = sent; so.used = streamed; so.fellBack = !streamed;
+    b.tm.streamChunks = streamed ? b.streamChunks : 0u; b.tm.streamedBytes = sent; b.tm.streamEarlyItems = hctl[3];
+    b.streamed = streamed;
+    return ommResult_SUCCESS;
+}
+
+// The bake proper: bake_cpu_impl.cpp:1923-1985 re-organised for the device.  `din` points at device copies of the caller's texCoords / indexBuffer /
+// subdivisionLevels.  The mode pointers: `sh` a sharded begin (stops behind the digests), `ht` a host tail (stops behind the classification), `so` a streamed
+// result on offer (ommCpuBake).  Two waits on the stream per bake (three with degenerate triangles under dynamic subdivision, or a streamed result to verify).
+// What goes when, on every path out: the stages' own temporaries go when the stage returns (the pooled block of fix_pending_levels before the work items are
+// written, the read-back buffers with read_back_statistics); `streamRun`, declared first, goes last and destroys the events behind the ranges of a streamed
+// result.  The SdmaCopier of a streamed result is `so`'s and outlives the call: the copies in flight are the caller's to wait for (StreamOut::finish), on error
+// paths too, while those events are already gone -- as before, when a copier of this function's own (never opened: streaming needs `so`) went first.
+ommResult bake_core(Baker& baker, const ommCpuBakeInputDesc& d, const DeviceInputs& din, DeviceArena* arena, DeviceArena* statesArena, hipStream_t stream, EventTimer& et,
+                    DeviceResult& R, ommxBakeTimings& tm, ShardCtx* sh = nullptr, HostTailRequest* ht = nullptr, StreamOut* so = nullptr)
+{
+    StreamRun streamRun;
+    BakeRun b(baker, d, din, arena, statesArena, stream, et, R, tm, sh, ht, so);
+    if (const ommResult r = b.carve_tables()) return r;
+    if (const ommResult r = b.setup_work_items()) return r;
+    b.classify_params();
+    if (const ommResult r = b.triage_and_compact()) return r;
+    if (const ommResult r = b.report_workload()) return r;
+    if (const ommResult r = b.plan_states()) return r;
+    if (const ommResult r = b.permute_for_ranks()) return r;
+    if (const ommResult r = b.classify(streamRun)) return r;
+    if (ht) return b.gather_for_host_tail();
+    if (const ommResult r = b.digest()) return r;
+    if (b.streamChunks) if (const ommResult r = streamRun.follow(b)) return r;
+    b.tail_inputs();
+    if (sh) return b.hand_to_shard();
+    if (const ommResult r = b.tail()) return r;
+    if (b.streamChunks) if (const ommResult r = streamRun.verify(b)) return r;
+    if (const ommResult r = b.read_back_statistics(b.materialise())) return r;
+    b.fill_timings(streamRun);
     return ommResult_SUCCESS;
 }
 
@@ -1197,6 +1276,13 @@ ommResult scope_fences(const Baker& baker, const ommCpuBakeInputDesc& d, bool fo
     return ommResult_SUCCESS;
 }
 
+// the dispatch table lookup precedes ValidateDesc (bake_cpu_impl.cpp:297-304): unknown sampler enums of a bake from a texture of this library -> FAILURE
+bool sampler_enums_unknown(const ommCpuBakeInputDesc& desc)
+{
+    return tag_of(desc.texture) == kTexture &&
+           ((unsigned)desc.runtimeSamplerDesc.addressingMode >= (unsigned)ommTextureAddressMode_MAX_NUM ||
+            (unsigned)desc.runtimeSamplerDesc.filter >= (unsigned)ommTextureFilterMode_MAX_NUM);
+}
 // What every bake entry point checks first, in the reference's order.  `outIsSet`: ommxBakeDevice reports a null result pointer together with a null desc.
 ommResult check_bake_entry(ommBaker baker, const ommCpuBakeInputDesc* desc, Baker** outB, bool outIsSet = true)
 {
@@ -1205,11 +1291,7 @@ ommResult check_bake_entry(ommBaker baker, const ommCpuBakeInputDesc* desc, Bake
     if (desc == 0 || !outIsSet) return b->log.invalid("input desc was not set");
     if (tag_of(baker) != kCpuBaker) return b->log.invalid("Baker was not created as the right type");
     if (desc->texture == 0) return b->log.invalid("[Invalid Argument] - ommCpuBakeInputDesc has no texture set"); // bake_cpu_impl.cpp:97-103
-    // the dispatch table lookup precedes ValidateDesc (bake_cpu_impl.cpp:297-304): unknown sampler enums -> FAILURE
-    if (tag_of(desc->texture) == kTexture &&
-        ((unsigned)desc->runtimeSamplerDesc.addressingMode >= (unsigned)ommTextureAddressMode_MAX_NUM ||
-         (unsigned)desc->runtimeSamplerDesc.filter >= (unsigned)ommTextureFilterMode_MAX_NUM))
-        return ommResult_FAILURE;
+    if (sampler_enums_unknown(*desc)) return ommResult_FAILURE;
     *outB = b;
     return validate_desc(*b, *desc);
 }
@@ -1657,7 +1739,7 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
     if (wants_host_tail(d)) {
         // near-duplicate merge / size budget: device classification, then the reference's serial tail on the host (host_tail.cpp)
         HostTailRequest ht;
-        const ommResult hr = bake_core(baker, d, din, &d, ses.arena, ses.states, stream, et, R, tm, nullptr, &ht);
+        const ommResult hr = bake_core(baker, d, din, ses.arena, ses.states, stream, et, R, tm, nullptr, &ht);
         if (hr != ommResult_SUCCESS) return hr;
         HostTailResult hres; ommIndexFormat ifmt = ommIndexFormat_UINT_32;
         if (run_host_tail_for(d, T, ht.items, hres, ifmt) != ommResult_SUCCESS) return ommResult_FAILURE;
@@ -1698,7 +1780,7 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
         *unitCodes = k ? codec.at.unitCodes : nullptr; *blockRawCounts = k ? codec.at.blockRawCounts : nullptr; return k; };
     // zeroing ahead: only with the default allocator, the compressed transfer on offer, helper threads, and an idle pool block of the last compressed result's size
     if (wantCompressed && baker.mem.alloc == default_alloc && baker.knob(ommxBakerKnob_RetainMemory) == 0 && baker.knob(ommxBakerKnob_ZeroAhead) == 0) array.zero_ahead(expandThreads);
-    const ommResult br = bake_core(baker, d, din, &d, ses.arena, ses.states, stream, et, R, tm, nullptr, nullptr, canStream ? &so : nullptr);
+    const ommResult br = bake_core(baker, d, din, ses.arena, ses.states, stream, et, R, tm, nullptr, nullptr, canStream ? &so : nullptr);
     R.gatherCodes = nullptr;
     if (br != ommResult_SUCCESS) return br;
 
@@ -2279,7 +2361,7 @@ OMM_MI355X_API ommResult ommxBakeDevice(ommBaker baker, const ommCpuBakeInputDes
     if (wants_host_tail(*desc)) {
         // near-duplicate merge / size budget: classification on the device, the reference's serial tail on the host, result uploaded again
         HostTailRequest ht; DeviceResult scratchR;
-        ommResult hr = bake_core(*b, *desc, din, nullptr, ses.arena, ses.states, ses.stream, et, scratchR, tm, nullptr, &ht);
+        ommResult hr = bake_core(*b, *desc, din, ses.arena, ses.states, ses.stream, et, scratchR, tm, nullptr, &ht);
         HostTailResult hres; ommIndexFormat ifmt = ommIndexFormat_UINT_32;
         if (hr == ommResult_SUCCESS) hr = run_host_tail_for(*desc, desc->indexCount / 3u, ht.items, hres, ifmt);
         if (hr == ommResult_SUCCESS) hr = upload_host_tail(*b, hres, ifmt, desc->indexCount / 3u, (int)desc->format, ses.stream, res);
@@ -2290,7 +2372,7 @@ OMM_MI355X_API ommResult ommxBakeDevice(ommBaker baker, const ommCpuBakeInputDes
         *outResult = (ommxDeviceBakeResult)res;
         return ommResult_SUCCESS;
     }
-    r = bake_core(*b, *desc, din, nullptr, ses.arena, ses.states, ses.stream, et, res->R, tm);
+    r = bake_core(*b, *desc, din, ses.arena, ses.states, ses.stream, et, res->R, tm);
     if (r == ommResult_SUCCESS && !keep_tri_areas(res->R, res->R.triAreaScratch, desc->indexCount / 3u, ses.stream)) r = b->log.failure("[Failure] - could not keep the triangle areas on the device");
     if (r != ommResult_SUCCESS) { (void)hipStreamSynchronize(ses.stream); b->mem.destroy(res); return r; } // (pooled blocks go back only when the stream is idle)
     finish_device_result(res);
@@ -2448,7 +2530,7 @@ ommResult sharded_begin(Baker* b, const ommCpuBakeInputDesc* desc, uint32_t rank
     sb->et.reset(new EventTimer(sb->ses.stream));
     DeviceResult unused;
     DeviceInputs din; din.texCoords = desc->texCoords; din.indices = desc->indexBuffer; din.perTriLevels = desc->subdivisionLevels;
-    const ommResult r = bake_core(*b, *desc, din, nullptr, sb->ses.arena, sb->ses.states, sb->ses.stream, *sb->et, unused, sb->tm, &sb->ctx);
+    const ommResult r = bake_core(*b, *desc, din, sb->ses.arena, sb->ses.states, sb->ses.stream, *sb->et, unused, sb->tm, &sb->ctx);
     if (r != ommResult_SUCCESS) { b->mem.destroy(sb); return r; }
     *out = sb;
     return ommResult_SUCCESS;
@@ -3268,10 +3350,7 @@ OMM_MI355X_API ommResult ommxResolveHits(ommBaker baker, const ommCpuBakeInputDe
     if (desc == 0) return b->log.invalid("input desc was not set");
     if (tag_of(baker) != kCpuBaker) return b->log.invalid("Baker was not created as the right type");
     if (desc->texture == 0) return b->log.invalid("[Invalid Argument] - ommCpuBakeInputDesc has no texture set");
-    if (tag_of(desc->texture) == kTexture &&
-        ((unsigned)desc->runtimeSamplerDesc.addressingMode >= (unsigned)ommTextureAddressMode_MAX_NUM ||
-         (unsigned)desc->runtimeSamplerDesc.filter >= (unsigned)ommTextureFilterMode_MAX_NUM))
-        return ommResult_FAILURE;
+    if (sampler_enums_unknown(*desc)) return ommResult_FAILURE;
     ommResult r = validate_desc(*b, *desc);
     if (r != ommResult_SUCCESS) return r;
     r = scope_fences(*b, *desc, false);
@@ -3284,13 +3363,8 @@ OMM_MI355X_API ommResult ommxResolveHits(ommBaker baker, const ommCpuBakeInputDe
     if (hits == nullptr || out == nullptr) return b->log.invalid("[Invalid Argument] - ommxResolveHits: hits / out are not set");
     ResolveParams rp; memset(&rp, 0, sizeof rp);
     ClassifyParams& P = rp.tex;
-    const TexMip& tm = tex.mips[0];
-    DevMip& dm = P.mips[0];
-    dm.texels = tm.texels; dm.sat = tm.sat; dm.w = tm.w; dm.h = tm.h;
-    dm.log2w = (int)ctz32((uint32_t)tm.w); dm.log2h = (int)ctz32((uint32_t)tm.h);
-    dm.pow2 = is_pow2(tm.w) && is_pow2(tm.h);
-    dm.fw = (float)tm.w; dm.fh = (float)tm.h; dm.rw = 1.f / (float)tm.w; dm.rh = 1.f / (float)tm.h;
-    P.mipCount = 1; P.pow2Dispatch = dm.pow2;
+    P.mips[0] = dev_mip(tex.mips[0]);
+    P.mipCount = 1; P.pow2Dispatch = P.mips[0].pow2;
     P.texIsFp32 = tex.format == ommCpuTextureFormat_FP32;
     P.addrMode = desc->runtimeSamplerDesc.addressingMode;
     P.filterLinear = desc->runtimeSamplerDesc.filter == ommTextureFilterMode_Linear;

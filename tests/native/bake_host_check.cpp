@@ -173,6 +173,209 @@ static void carve()
     }
 }
 
+// ---- the decisions and layouts of bake_core's stages: each held to the expression it had inline in bake_core (omm_host.cpp at a8c6db0), restated verbatim ----
+static void rank_range_rules()
+{
+    const uint32_t worlds[5] = { 1, 2, 3, 8, 16 };
+    for (uint32_t world : worlds) {
+        const uint32_t counts[5] = { 0, 1, world - 1, world + 1, 1000003 };
+        uint32_t activeStart[kBakeLevels + 1]; activeStart[0] = 7;   // (the lists need not start at zero for the rule to hold)
+        for (int l = 0; l < kBakeLevels; ++l) activeStart[l + 1] = activeStart[l] + counts[(l + world) % 5];
+        uint32_t end[kBakeLevels];
+        for (int l = 0; l < kBakeLevels; ++l) end[l] = activeStart[l];
+        for (uint32_t rank = 0; rank < world; ++rank) {
+            uint32_t b[kBakeLevels][kBakeMaxRanks + 1], first[kBakeLevels], count[kBakeLevels];
+            uint32_t wantB[kBakeLevels][kBakeMaxRanks + 1], lvlFirst[kBakeLevels], lvlCount[kBakeLevels];
+            memset(b, 0, sizeof b); memset(wantB, 0, sizeof wantB);
+            rank_ranges(activeStart, rank, world, b, first, count);
+            for (int l = 0; l < kBakeLevels; ++l) {
+                const uint64_t a = activeStart[l], cnt = activeStart[l + 1] - activeStart[l];
+                for (uint32_t r = 0; r <= world; ++r) wantB[l][r] = (uint32_t)(a + cnt * r / world);
+                lvlFirst[l] = wantB[l][rank]; lvlCount[l] = wantB[l][rank + 1] - wantB[l][rank];
+            }
+            CHECK(memcmp(b, wantB, sizeof b) == 0, "bounds of world %u as seen by rank %u", world, rank);
+            CHECK(memcmp(first, lvlFirst, sizeof first) == 0 && memcmp(count, lvlCount, sizeof count) == 0, "range of rank %u of %u", rank, world);
+            for (int l = 0; l < kBakeLevels; ++l) { CHECK(first[l] == end[l], "level %d: rank %u of %u starts where the rank before it ends", l, rank, world); end[l] = first[l] + count[l]; }
+        }
+        for (int l = 0; l < kBakeLevels; ++l) CHECK(end[l] == activeStart[l + 1], "level %d: the last rank of %u ends with the list", l, world);
+    }
+}
+
+static uint32_t parent_stream_chunks(uint64_t stateBytes, double microAll, uint64_t workload, bool compressedAvailable, bool forced, uint32_t chunksWanted)
+{
+    const uint32_t kMaxStreamRanges = 32;
+    uint32_t k = chunksWanted;
+    if (!forced) {
+        k = stateBytes >= (64ull << 20) ? (uint32_t)(stateBytes >> 25) : 0u; if (k > kMaxStreamRanges) k = kMaxStreamRanges;
+        const double classifyMs = 2.5e-10 * microAll + 4e-9 * (double)workload, copyMs = (double)stateBytes / 57e6;
+        if (copyMs <= 0.25 * classifyMs) k = 0;
+        if (k && compressedAvailable) {
+            const double cMs = 1.35e-10 * microAll + 4e-9 * (double)workload, resultBytes = 0.65 * (double)stateBytes;
+            const double streamedMs = 6.0 + std::max(1.15 * cMs + 2.7, resultBytes / 57e6), compressedMs = 3.3 + cMs + resultBytes / 150e6 + resultBytes * 0.63e-9;
+            if (compressedMs <= streamedMs) k = 0;
+        }
+    }
+    if (k > kMaxStreamRanges) k = kMaxStreamRanges;
+    return k;
+}
+// the integers around a real workload (none when it is not a workload at all)
+static void around(double w, std::vector<uint64_t>& out) { if (w >= 2.0 && w < 1e18) for (int k = -1; k <= 2; ++k) out.push_back((uint64_t)w + (uint64_t)(int64_t)k); }
+static void stream_range_rules()
+{
+    std::vector<uint64_t> states = { 0, (64ull << 20) - 1, 64ull << 20, (64ull << 20) + 1, 1270000000ull, 5400000000ull };   // (the last two: the sizes of the two anchors below)
+    for (uint64_t k = 3; k <= 34; ++k) states.push_back(k << 25);   // 32 MiB multiples, up to beyond 32 ranges
+    const double micros[3] = { 0.0, 6.5e10, 6.0e11 };
+    long copyFlips = 0, priceFlips = 0;
+    for (uint64_t sb : states) for (double micro : micros) for (int comp = 0; comp < 2; ++comp) {
+        std::vector<uint64_t> workloads = { 0, 14000000000ull };
+        // copyMs == 0.25 * classifyMs
+        const double copyMs = (double)sb / 57e6;
+        const size_t copyAt = workloads.size();
+        around((4.0 * copyMs - 2.5e-10 * micro) / 4e-9, workloads);
+        // compressedMs == streamedMs, on either branch of the max: 0.15 cMs == X - 5.4 (the classification hides the copy) | cMs == 2.7 + copy - X (it does not)
+        const double r = 0.65 * (double)sb, X = r / 150e6 + r * 0.63e-9;
+        const size_t priceAt = workloads.size();
+        around(((X - 5.4) / 0.15 - 1.35e-10 * micro) / 4e-9, workloads);
+        around((2.7 + r / 57e6 - X - 1.35e-10 * micro) / 4e-9, workloads);
+        long wrong = 0;
+        for (uint64_t w : workloads) wrong += stream_range_count(sb, micro, w, comp != 0, false, 0) != parent_stream_chunks(sb, micro, w, comp != 0, false, 0);
+        CHECK(wrong == 0, "%ld of %zu workloads at %llu bytes of states, %g micro-triangles, compressed transfer %d", wrong, workloads.size(), (unsigned long long)sb, micro, comp);
+        // (the points do straddle the thresholds: the decision differs between the two sides at some of them)
+        if (priceAt - copyAt == 4 && !comp) copyFlips += stream_range_count(sb, micro, workloads[copyAt], false, false, 0) != stream_range_count(sb, micro, workloads[copyAt + 3], false, false, 0);
+        for (size_t at = priceAt; at + 4 <= workloads.size() && comp; at += 4) priceFlips += stream_range_count(sb, micro, workloads[at], true, false, 0) != stream_range_count(sb, micro, workloads[at + 3], true, false, 0);
+    }
+    CHECK(copyFlips > 0, "no grid point straddles copyMs == 0.25 classifyMs");
+    CHECK(priceFlips > 0, "no grid point straddles compressedMs == streamedMs");
+    const uint32_t forcedValues[3] = { 1, 3, 32 };
+    for (uint32_t f : forcedValues) for (uint64_t sb : states)
+        CHECK(stream_range_count(sb, 6.5e10, 0, true, true, f) == f && parent_stream_chunks(sb, 6.5e10, 0, true, true, f) == f, "%u forced ranges at %llu bytes", f, (unsigned long long)sb);
+    CHECK(stream_range_count(256, 0.0, 0, false, true, 33) == 32 && parent_stream_chunks(256, 0.0, 0, false, true, 33) == 32, "a forced count is clamped");
+    // the two anchors of the pricing (bake_host.h): the metric configuration takes the compressed transfer, a classification of 100 ms streams
+    CHECK(stream_range_count(1270000000ull, 6.5e10, 0, true, false, 0) == 0, "c2-like: 6.5e10 micro-triangles, 1.27 GB, compressed transfer on offer");
+    CHECK(stream_range_count(5400000000ull, 6.0e11, 1750000000ull, true, false, 0) > 1, "configs[4]-like: 6.0e11 micro-triangles");
+}
+
+static void generic_pass_rules()
+{
+    const double micros[2] = { 6.5e10, 6.0e11 };
+    for (uint64_t mode = 0; mode < 3; ++mode) for (double microAll : micros) {
+        std::vector<uint64_t> workloads = { 0, 14000000000ull };
+        around(2.5e-10 * microAll / 4e-9, workloads);   // both sides of 4e-9 * workload > 2.5e-10 * micro
+        CHECK(workloads.size() == 6, "four workloads around the threshold");
+        for (uint64_t workload : workloads) {
+            const bool wanted = mode == 2 || (mode == 0 && 4e-9 * (double)workload > 2.5e-10 * microAll);
+            CHECK(generic_pass_wanted(mode, microAll, workload) == wanted, "mode %llu, %g micro-triangles, workload %llu", (unsigned long long)mode, microAll, (unsigned long long)workload);
+        }
+    }
+    CHECK(!generic_pass_wanted(0, 6.5e10, 0) && generic_pass_wanted(0, 6.5e10, 14000000000ull), "by cost: texels under the micro-triangles against their number");
+    CHECK(!generic_pass_wanted(1, 6.5e10, 14000000000ull) && generic_pass_wanted(2, 6.5e10, 0), "never / always");
+    for (int storeBits = 1; storeBits <= 2; ++storeBits) {
+        const uint64_t onCap = (32ull << 20) * (uint64_t)storeBits;   // bytes of states whose micro-triangles are exactly 256 Mi
+        const uint64_t states[7] = { 0, 256, 1ull << 20, onCap - 1, onCap, onCap + 1, 1270000000ull };
+        for (uint64_t stateBytes : states) {
+            uint64_t genericCapacity = stateBytes * 8ull / (uint64_t)storeBits;
+            if (genericCapacity > (256ull << 20)) genericCapacity = 256ull << 20;
+            CHECK(generic_pass_capacity(stateBytes, storeBits) == genericCapacity, "%llu bytes of %d-bit states", (unsigned long long)stateBytes, storeBits);
+        }
+        CHECK(generic_pass_capacity(onCap - 1, storeBits) < (256ull << 20), "below the cap");
+        CHECK(generic_pass_capacity(onCap, storeBits) == (256ull << 20), "on the cap");
+        CHECK(generic_pass_capacity(onCap + 1, storeBits) == (256ull << 20), "the first size with entries above the cap");
+    }
+}
+
+static uint32_t gcd_of(uint32_t x, uint32_t y) { while (y) { const uint32_t t = x % y; x = y; y = t; } return x; }
+static void interleave_rules()
+{
+    std::vector<uint32_t> counts;
+    for (uint32_t cnt = 3; cnt <= 4096; ++cnt) counts.push_back(cnt);
+    const uint32_t large[9] = { 65521u, 1000003u, 16777213u, 2147483647u, 4294967291u, 1u << 16, 1u << 20, 1u << 24, 1u << 31 };   // primes, powers of two
+    counts.insert(counts.end(), large, large + 9);
+    std::vector<uint8_t> hit;
+    for (uint32_t cnt : counts) {
+        uint32_t stride = (uint32_t)((double)cnt * 0.6180339887498949); if (stride < 1) stride = 1;
+        auto gcd = [](uint32_t x, uint32_t y) { while (y) { const uint32_t t = x % y; x = y; y = t; } return x; };
+        while (gcd(stride, cnt) != 1) ++stride;
+        const uint32_t got = interleave_stride(cnt);
+        CHECK(got == stride % cnt, "cnt %u: %u, %u before", cnt, got, stride % cnt);
+        CHECK(gcd_of(got, cnt) == 1, "cnt %u: stride %u is not coprime", cnt, got);
+        CHECK(got >= 1 && got < cnt, "cnt %u: stride %u", cnt, got);
+        if (cnt > 4096) continue;
+        hit.assign(cnt, 0);
+        for (uint32_t p = 0; p < cnt; ++p) hit[(size_t)((uint64_t)p * got % cnt)]++;
+        CHECK(std::count(hit.begin(), hit.end(), 1) == (long)cnt, "cnt %u: p -> p * %u %% cnt is no permutation", cnt, got);
+    }
+}
+
+static void states_carve()
+{
+    const uint64_t states[3] = { 256, 1ull << 20, 1270000000ull };
+    const size_t queues[3] = { 16, 1000 * 112 + 16, 300000 * 112 + 16 };   // records of kTileRecordBytes + 16
+    const uint64_t generics[3] = { 0, 1, 256ull << 20 };
+    for (uint64_t hcStateBytes : states) for (size_t queueRaw : queues) for (int streamChunks = 0; streamChunks < 2; ++streamChunks) for (uint64_t genericCapacity : generics) {
+        const BakeStates sized = carve_bake_states(0, hcStateBytes, queueRaw, streamChunks != 0, genericCapacity);
+        // what bake_core summed by hand
+        const size_t stateBytes = p256(hcStateBytes ? (size_t)hcStateBytes : 256), ctlBytes = p256(sizeof(uint32_t) * 512), queueBytes = p256(queueRaw);
+        const size_t genericBytes = genericCapacity ? p256((size_t)genericCapacity * 8) + 256 : 0;
+        const size_t total = stateBytes + queueBytes + ctlBytes + (streamChunks ? stateBytes : 0) + genericBytes;
+        const size_t dTileQueue = stateBytes, dQueueCtl = stateBytes + queueBytes, dStage = stateBytes + queueBytes + ctlBytes, dGeneric = stateBytes + queueBytes + ctlBytes + (streamChunks ? stateBytes : 0);
+        CHECK(sized.states == nullptr && (size_t)sized.tileQueue == dTileQueue && (size_t)sized.queueCtl == dQueueCtl && sized.stateBytes == stateBytes && sized.bytes == total &&
+              (!streamChunks || (size_t)sized.stage == dStage) && (!genericCapacity || (size_t)sized.genericCount == dGeneric), "offsets and total %zu, %zu before", sized.bytes, total);
+        CHECK((sized.stage != nullptr) == (streamChunks != 0), "a staging copy for a streamed result only");
+        if (genericCapacity) CHECK((uintptr_t)sized.genericEntries == (uintptr_t)sized.genericCount + 256, "the count word lies 256 bytes before the entries");
+        else CHECK(!sized.genericCount && !sized.genericEntries, "no generic pass");
+        std::vector<Region> r = { { "states", (uintptr_t)sized.states, sized.stateBytes }, { "tileQueue", (uintptr_t)sized.tileQueue, queueRaw }, { "queueCtl", (uintptr_t)sized.queueCtl, 4 * 512 } };
+        if (streamChunks) r.push_back(Region{ "stage", (uintptr_t)sized.stage, sized.stateBytes });
+        if (genericCapacity) { r.push_back(Region{ "genericCount", (uintptr_t)sized.genericCount, 256 }); r.push_back(Region{ "genericEntries", (uintptr_t)sized.genericEntries, (size_t)genericCapacity * 8 }); }
+        bool apart = r.back().at + p256(r.back().bytes) == sized.bytes;   // (the slots are in carve order: each ends before the next, the last with the reservation)
+        for (size_t k = 0; k < r.size(); ++k) apart = apart && r[k].at % 256 == 0 && (k + 1 == r.size() || r[k].at + r[k].bytes <= r[k + 1].at);
+        CHECK(apart, "slots are aligned, disjoint and end with the reservation");
+        if (sized.bytes > ((size_t)32 << 20)) continue;
+        uint8_t* block = (uint8_t*)aligned_alloc(256, sized.bytes);   // (exact size: a slot that runs over is the sanitizer's to report)
+        const BakeStates s = carve_bake_states((uintptr_t)block, hcStateBytes, queueRaw, streamChunks != 0, genericCapacity);
+        memset(s.states, 1, s.stateBytes); memset(s.tileQueue, 2, queueRaw); memset(s.queueCtl, 3, 4 * 512);
+        if (s.stage) memset(s.stage, 4, s.stateBytes);
+        if (s.genericCount) { memset(s.genericCount, 5, 256); memset(s.genericEntries, 6, (size_t)genericCapacity * 8); }
+        CHECK(block != nullptr && s.states == block && s.bytes == sized.bytes && s.tileQueue == block + dTileQueue && (uint8_t*)s.queueCtl == block + dQueueCtl && s.states[s.stateBytes - 1] == 1 && s.tileQueue[0] == 2,
+              "both passes agree, every slot was written end to end");
+        free(block);
+    }
+}
+
+static void readback_and_small_rules()
+{
+    const size_t actual = 768 + kBakeFineWords * 8;   // BakeTables::readback_bytes
+    const size_t spans[6] = { 0, 1, 256, actual, 62208, 62209 };
+    for (size_t spanBytes : spans) {
+        const size_t spanAt = 1024, ctlAt = spanAt + p256(spanBytes), genAt = ctlAt + sizeof(uint32_t[512]);
+        const bool pinnedBack = genAt + sizeof(unsigned long long[3]) <= ((size_t)64u << 10);
+        const ReadbackSlots s = readback_slots(spanBytes);
+        CHECK(s.spanAt == spanAt && s.ctlAt == ctlAt && s.genAt == genAt && s.fits == pinnedBack, "read-back slots of a span of %zu bytes", spanBytes);
+    }
+    const ReadbackSlots s = readback_slots(actual);
+    CHECK(readback_slots(actual, s.genAt + 24).fits, "the last word ends with the block");
+    CHECK(!readback_slots(actual, s.genAt + 23).fits, "the last word ends one byte behind the block");
+    CHECK(readback_slots(62208).fits && readback_slots(62208).genAt + 24 + 232 == ((size_t)64 << 10), "the longest span the 64 KiB block takes");
+    CHECK(!readback_slots(62209).fits, "one byte more");
+    uint32_t activeStart[kBakeLevels + 1];
+    for (int only = -1; only <= kBakeLevels; ++only) {   // no level | one level | every level
+        activeStart[0] = 5;
+        for (int l = 0; l < kBakeLevels; ++l) activeStart[l + 1] = activeStart[l] + ((l == only || only == kBakeLevels) ? 3u : 0u);
+        uint32_t classifyLaunches = 0; bool big = false;
+        for (int l = 0; l < kBakeLevels; ++l) { const bool any = activeStart[l + 1] != activeStart[l]; if (l < 6) classifyLaunches += any; else big = big || any; }
+        classifyLaunches += big;
+        CHECK(classify_launches(activeStart) == classifyLaunches, "launches with level %d active", only);
+        if (only == -1) CHECK(classifyLaunches == 0, "nothing to classify");
+        if (only == 9) CHECK(classifyLaunches == 1, "the levels from 6 on share ONE launch");
+        if (only == kBakeLevels) CHECK(classifyLaunches == 7, "six launches below level 6 and the persistent one");
+    }
+    const double micros[3] = { 0.0, 6.5e10, 6.0e11 }; const uint64_t workloads[2] = { 0, 14000000000ull };
+    for (double microAll : micros) for (uint64_t workload : workloads)
+        CHECK(stream_wait_seconds(microAll, workload) == 4.0 + 100.0 * 1e-3 * (2.5e-10 * microAll + 4e-9 * (double)workload), "wait for %g micro-triangles, workload %llu", microAll, (unsigned long long)workload);
+    CHECK(stream_wait_seconds(0.0, 0) == 4.0, "never below 4 s");
+    const uint32_t actives[3] = { 0u, 1u, 0xFFFFFFBFu };
+    for (uint32_t active : actives) CHECK(max_distinct_digests(active) == active + 64u, "%u active items", active);
+}
+
 int main()
 {
     index_formats();
@@ -180,6 +383,12 @@ int main()
     result_descs();
     raw_inputs();
     carve();
+    rank_range_rules();
+    stream_range_rules();
+    generic_pass_rules();
+    interleave_rules();
+    states_carve();
+    readback_and_small_rules();
     printf("ok %ld\n", g_checks);
     return 0;
 }

@@ -1,6 +1,6 @@
 """The block exchange of a sharded bake (omm_amd/csrc/tail_kernels.hip: shard_interleave, owner_of_position, shard_pack_meta / shard_unpack_meta,
 shard_masked_sizes / shard_take_offsets, shard_gather_contribution, shard_scatter_contributions, the device codec shard_codec_* and
-shard_scatter_streams; omm_host.cpp: the bounds of bake_core, sharded_tail's stride and cap, shard_chunk_bytes) restated in numpy / Python, and the
+shard_scatter_streams; bake_host.h: rank_ranges and interleave_stride; omm_host.cpp: sharded_tail's stride and cap, shard_chunk_bytes) restated in numpy / Python, and the
 cases of tests/test_shard_reference.py (no GPU) and tests/test_shard_gpu.py.
 
 What is restated, from the comments and the code named above:

@@ -1,7 +1,9 @@
 """The host-side rules of a bake (omm_amd/csrc/bake_host.h) without a GPU: index formats, histogram lists, the result descriptor, the layout of the raw
 triangle upload and the carve of the working set -- a stand-alone program, tests/native/bake_host_check.cpp, under AddressSanitizer and UBSan.  The carve
 is run twice per shape, from a null base (the size to reserve) and over an exact-size heap block that every slot is then filled in: a slot that is not
-aligned, overlaps another, runs over the reservation, or breaks one of the two adjacency contracts (counters + digest table, the read-back span) stops it."""
+aligned, overlaps another, runs over the reservation, or breaks one of the two adjacency contracts (counters + digest table, the read-back span) stops it.
+The decisions and layouts that bake_core's stages take from that header -- rank ranges, the ranges of a streamed result, the deferred generic pass, the
+interleave stride, the carve of the states arena, the read-back slots -- are each held to the expression they replaced, restated in the program."""
 import os
 import subprocess
 
@@ -22,4 +24,19 @@ def test_bake_host_rules_and_working_set_carve(tmp_path):
     raw_inputs = 10 * 3 * 3 * 2 * 6
     # per shape 4 checks per slot and 6 of the whole; 26 slots, 4 more sharded, 11 more streamed; one check per absent group
     carve = 5 * 2 * ((4 * 26 + 8) + (4 * 30 + 7) + (4 * 37 + 7) + (4 * 41 + 6))
-    assert int(r.stdout.split()[1]) == index_formats + histograms + result_descs + raw_inputs + carve
+    # the decisions and layouts of bake_core's stages, each against the expression it had inline:
+    # worlds 1, 2, 3, 8, 16 (30 ranks): per rank the bounds, its range and 13 levels that start where the rank before ended; per world 13 levels that end with the list
+    rank_ranges = 30 * (2 + 13) + 5 * 13
+    # 38 sizes of the states x 3 micro-triangle counts x compressed transfer on / off, each over all its workloads; 2 threshold-straddling checks;
+    # 3 forced counts x 38 sizes; the clamp of a forced count; the two anchors of the pricing
+    stream_ranges = 38 * 3 * 2 + 2 + 3 * 38 + 1 + 2
+    # 3 modes x 2 micro-triangle counts x (1 + 6 workloads); 2 of the modes' meaning; per storeBits 7 sizes and 3 at the cap
+    generic_pass = 3 * 2 * 7 + 2 + 2 * (7 + 3)
+    # cnt 3..4096 and 9 large ones: equal, coprime, in range; up to 4096 also a permutation
+    interleave = 3 * (4094 + 9) + 4094
+    # 3 sizes of the states x 3 queues x streamed on / off x 3 generic capacities, 4 checks each; the 16 shapes of at most 32 MiB are also written end to end
+    states_carve = 3 * 3 * 2 * 3 * 4 + 16
+    # read-back slots: 6 spans, 2 + 2 at the block size; launches: no / each / every level (15) + 3 values; 6 + 1 waits; 3 digest bounds
+    readback_and_small = 6 + 2 + 2 + 15 + 3 + 6 + 1 + 3
+    stages = rank_ranges + stream_ranges + generic_pass + interleave + states_carve + readback_and_small
+    assert int(r.stdout.split()[1]) == index_formats + histograms + result_descs + raw_inputs + carve + stages
