@@ -490,6 +490,83 @@ OMM_MI355X_API ommResult ommxCombineMicromaps(ommBaker baker, const ommCpuBakeRe
                                               const ommxCombineDesc* desc, ommxDeviceBakeResult* outResult /* NULL: info only */,
                                               ommxCombineInfo* outInfo /* or NULL */, void* hipStream);
 
+/* ---- one micromap from chosen primitives of several results ----
+ * ommxGatherMicromaps    makes a new device-resident result whose primitives are CHOSEN primitives of the sources, with the same bits: the one entry
+ *                        that changes which primitives a result describes.  For a BLAS built from several meshes or a scene-wide OMM array (equal
+ *                        blocks of different bakes become one block); for a subset or a reordering of one mesh (an LOD, a meshlet split, an index
+ *                        buffer reordered after the bake, the survivors of a culling pass: descriptors that are no longer referenced leave
+ *                        arrayData); and for more inputs than ommxCombineMicromaps takes.  Nothing is downloaded.
+ *   sources              resultCount is 1..OMMX_GATHER_MAX_SOURCES.  Each element of deviceResults is a HOST struct over DEVICE arrays as for
+ *                        ommxCombineMicromaps.  indexCount and the index formats (8, 16 and 32 bits) may differ between sources; a source may have
+ *                        indexCount == 0; the same source may be given more than once.  No source is modified.  Larger scenes chain calls: the
+ *                        output is an ordinary result and is accepted as a source.
+ *   output primitive i   names (k, p): selection[i], or -- when selection is NULL -- the i-th primitive of the concatenation of the sources (every
+ *                        primitive of source 0, then of source 1, ...).  k >= resultCount or p >= source k's indexCount: the primitive is SKIPPED.
+ *                        Otherwise e = source k's index entry p.  An entry -1..-4 passes through unchanged under every flag.  An entry >= 0 selects
+ *                        descArray_k[e] by the bounds rule of omm_mi355x_lookup.h.  An entry below -4, an entry at or beyond descArrayCount_k, a level
+ *                        above 12, a format other than 1 or 2, a block outside arrayDataSize_k: the primitive is SKIPPED.  For a skipped primitive
+ *                        nothing is read through a descriptor, its output entry is -4, and it counts once in skippedPrimitives.  The same (k, p) may
+ *                        be selected many times.
+ *   blocks               every distinct accepted (k, e) is one item; its block is copied with level and format unchanged.  The unused bits of a
+ *                        one-byte block are ignored on input and zero on output.  One output may hold blocks of both formats.  No byte outside
+ *                        [offset, offset + size) of a block is read: a block may end at the last byte of the caller's allocation.
+ *   uniform blocks       as in ommxCoarsenMicromap: a block whose states all equal s is uniform; without DisableSpecialIndices it is not emitted and
+ *                        its primitives get the entry -(s + 1).
+ *   duplicates           as in ommxCoarsenMicromap: without DisableDuplicateDetection two blocks are one when level, format and every byte are equal
+ *                        (a 64-bit digest finds the candidates, the bytes confirm).  An item's rank is (k, e) in lexicographic order; the
+ *                        representative of a class is its lowest-ranked member.
+ *   order, offsets       output descriptors are ordered by block size in bytes descending, then by the representative's rank ascending; a block's
+ *                        size is max(1, 4^level * bits / 8).  Blocks are packed without gaps from offset 0; every size is a power of two, so every
+ *                        block is naturally aligned.  An arrayDataSize above what a 32-bit descriptor offset can express is FAILURE with a log line.
+ *   index buffer         primitiveCount entries, always ommIndexFormat_UINT_32: the special index of a source special, a skipped primitive or a
+ *                        promoted block, otherwise the output descriptor of the block's representative.
+ *   histograms           as in ommxCoarsenMicromap.
+ *   purity               the output is a pure function of the inputs: two calls return the same bytes.  With selection == NULL and resultCount == 1,
+ *                        arrayData, descArray, both histograms and the index VALUES equal those of ommxCoarsenMicromap with maxSubdivisionLevel = 12
+ *                        and the same flags on that source.
+ *   outResult            an ordinary ommxDeviceBakeResult from the baker's device pool.  It carries no triangle areas and is accepted by the lookup,
+ *                        resolve, stats, geometry, coarsen and combine entries and by ommxGatherMicromaps itself.
+ *   info                 see ommxGatherInfo.  With default flags referencedBlocks == descArrayCount + uniformBlocks + duplicateBlocks.  With
+ *                        outResult == NULL the same numbers are computed and no output arrays are allocated.
+ *   stream, memory       the kernels run on `hipStream` (null = the null stream), which the call synchronises before it returns; the selection is
+ *                        read there, behind whatever the caller queued on that stream.  Scratch comes from the baker's device pool and is back there
+ *                        when the call returns.  *outResult is written on SUCCESS only.
+ *   result codes         judged before the device is touched, each INVALID_ARGUMENT with a log line of its own: a null baker, a baker of unknown
+ *                        type, null deviceResults, null desc, resultCount 0 or above 4096, a null element of deviceResults, outResult and outInfo
+ *                        both null, unknown flag bits, non-zero reserved, a null selection with selectionCount != 0, an unknown indexFormat in any
+ *                        source, null arrays with non-zero counts as in ommxCombineMicromaps, a sum of indexCount (NULL selection) or of
+ *                        descArrayCount over the sources above 2^32 - 1.  primitiveCount == 0 -> SUCCESS without a launch: the info is all zeros and
+ *                        *outResult is an empty result that can be destroyed.  Without a usable device, or when device memory runs out -> FAILURE
+ *                        with a log line. */
+#define OMMX_GATHER_MAX_SOURCES 4096
+typedef struct ommxPrimitiveRef {
+    uint32_t source;        /* index into deviceResults */
+    uint32_t primitive;     /* index into that source's index buffer */
+} ommxPrimitiveRef;
+typedef enum ommxGatherFlags {                       /* same values and meaning as ommxCoarsenFlags */
+    ommxGatherFlags_None                      = 0,
+    ommxGatherFlags_DisableSpecialIndices     = 1,
+    ommxGatherFlags_DisableDuplicateDetection = 2
+} ommxGatherFlags;
+typedef struct ommxGatherDesc {
+    const ommxPrimitiveRef* selection;  /* DEVICE memory, selectionCount entries; NULL: every primitive of source 0, then of source 1, ... */
+    uint32_t selectionCount;            /* must be 0 when selection is NULL */
+    uint32_t flags;                     /* ommxGatherFlags */
+    uint32_t reserved;                  /* must be 0 */
+} ommxGatherDesc;
+typedef struct ommxGatherInfo {
+    uint64_t arrayDataSize;      /* of the output */
+    uint32_t descArrayCount;     /* of the output */
+    uint32_t primitiveCount;     /* of the output: selectionCount, or the sum of the sources' indexCount */
+    uint32_t referencedBlocks;   /* distinct (source, descriptor) pairs that a selected primitive selects and the bounds rule accepts */
+    uint32_t uniformBlocks;      /* of those: every state equal (promoted to a special index unless disabled) */
+    uint32_t duplicateBlocks;    /* of those: merged into another block */
+    uint32_t skippedPrimitives;
+} ommxGatherInfo;
+OMM_MI355X_API ommResult ommxGatherMicromaps(ommBaker baker, const ommCpuBakeResultDesc* const* deviceResults, uint32_t resultCount,
+                                             const ommxGatherDesc* desc, ommxDeviceBakeResult* outResult /* NULL: info only */,
+                                             ommxGatherInfo* outInfo /* or NULL */, void* hipStream);
+
 /* ---- an alpha texture from an image that is already in device memory ----
  * ommxCreateTextureDevice  ommCpuCreateTexture for texels that live in HBM: ONE channel of an interleaved (or packed single-channel) image is read where
  *                        it is; nothing is downloaded, restaged or uploaded.  The result is an ordinary ommCpuTexture, byte for byte the texture

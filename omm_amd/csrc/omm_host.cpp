@@ -16,6 +16,7 @@
 #include "geometry_cut.h"
 #include "coarsen_kernels.h"
 #include "combine_kernels.h"
+#include "gather_kernels.h"
 #include "texture_kernels.h"
 #include "block_kernels.h"
 #include "bc7_kernels.h"
@@ -1310,7 +1311,7 @@ void finish_device_result(DeviceBakeResult* res)
     fill_result_desc(&res->desc, R.arrayData, R.arrayDataSize, R.descs, R.numDescs, R.index, R.numTris, R.indexFormat, res->arrayHist, nAH, res->indexHist, nIH);
 }
 
-// ---- the entries that take device-resident results: what a caller's result must be; and, for ommxCoarsenMicromap and ommxCombineMicromaps, the new handle ----
+// ---- the entries that take device-resident results: what a caller's result must be; and, for ommxCoarsenMicromap, ommxCombineMicromaps and ommxGatherMicromaps, the new handle ----
 bool is_index_format(ommIndexFormat f) { return f == ommIndexFormat_UINT_8 || f == ommIndexFormat_UINT_16 || f == ommIndexFormat_UINT_32; }
 bool has_null_array(const ommCpuBakeResultDesc& r)
 {
@@ -1324,7 +1325,7 @@ bool usable_device()
     return false;
 }
 struct DerivedResult {
-    Baker& b; hipStream_t stream; const char* noun;   // noun: the new result in a message ("coarsened", "combined")
+    Baker& b; hipStream_t stream; const char* noun;   // noun: the new result in a message ("coarsened", "combined", "gathered")
     DeviceBakeResult* res = nullptr;                  // stays null when the caller wants the info only
     uint32_t hist[2 * kRebuildHist];                  // array | index by (level, format - 1): the operation's last stage fills it
     DerivedResult(Baker& b_, hipStream_t stream_, const char* noun_) : b(b_), stream(stream_), noun(noun_) { memset(hist, 0, sizeof hist); }
@@ -3338,6 +3339,82 @@ OMM_MI355X_API ommResult ommxCombineMicromaps(ommBaker baker, const ommCpuBakeRe
         if (deviceResults[k] == nullptr) return b->log.invalid("[Invalid Arg] - an element of deviceResults was not set");
     if (outResult == nullptr && outInfo == nullptr) return b->log.invalid("[Invalid Arg] - neither outResult nor outInfo was set");
     return guarded(&b->log, [&] { return combine_device(*b, deviceResults, resultCount, *desc, outResult, outInfo, (hipStream_t)hipStream); });
+}
+
+// One result from chosen primitives of several device-resident results (include/omm_mi355x_ext.h; kernels in gather_kernels.hip): build the source table
+// with its scans, mark the descriptors the selection reaches and size the staging arena, copy and compare, judge the output's size on the host, then
+// allocate the new result's arrays and fill them.
+namespace {
+ommResult gather_device(Baker& b, const ommCpuBakeResultDesc* const* results, uint32_t count, const ommxGatherDesc& g, ommxDeviceBakeResult* outResult,
+                        ommxGatherInfo* outInfo, hipStream_t stream)
+{
+    if ((g.flags & ~(uint32_t)(ommxGatherFlags_DisableSpecialIndices | ommxGatherFlags_DisableDuplicateDetection)) != 0) return b.log.invalid("[Invalid Arg] - ommxGatherDesc.flags has unknown bits");
+    if (g.reserved != 0) return b.log.invalid("[Invalid Arg] - ommxGatherDesc.reserved must be 0");
+    if (g.selection == nullptr && g.selectionCount != 0) return b.log.invalid("[Invalid Arg] - ommxGatherDesc.selection was not set but selectionCount is not 0");
+    for (uint32_t k = 0; k < count; ++k)
+        if (!is_index_format(results[k]->indexFormat)) return b.log.invalid("[Invalid Arg] - a source's indexFormat is not an index format");
+    for (uint32_t k = 0; k < count; ++k)
+        if (has_null_array(*results[k])) return b.log.invalid("[Invalid Arg] - a source has a null array with a non-zero count");
+    std::vector<GatherSource> table(count);
+    uint64_t prims = 0, descs = 0;
+    for (uint32_t k = 0; k < count; ++k) {
+        const ommCpuBakeResultDesc& r = *results[k];
+        GatherSource& s = table[k];
+        s.arrayData = (const uint8_t*)r.arrayData; s.descs = r.descArray; s.index = r.indexBuffer;
+        s.arrayDataSize = r.arrayDataSize; s.descCount = r.descArrayCount; s.indexCount = r.indexCount; s.indexFormat = (int32_t)r.indexFormat;
+        s.primBase = (uint32_t)prims; s.descBase = (uint32_t)descs;   // (a sum that does not fit is refused below, before the table is used)
+        prims += r.indexCount; descs += r.descArrayCount;
+    }
+    if (g.selection == nullptr && prims > 0xFFFFFFFFull) return b.log.invalid("[Invalid Arg] - the sources' indexCount values add up to more than 2^32 - 1 primitives");
+    if (descs > 0xFFFFFFFFull) return b.log.invalid("[Invalid Arg] - the sources' descArrayCount values add up to more than 2^32 - 1 descriptors");
+    const uint32_t primitiveCount = g.selection ? g.selectionCount : (uint32_t)prims;
+    ommxGatherInfo info; memset(&info, 0, sizeof info);
+    DerivedResult out(b, stream, "gathered");
+    const ommResult made = outResult ? out.create(primitiveCount, ommIndexFormat_UINT_32) : ommResult_SUCCESS;
+    if (made != ommResult_SUCCESS) return made;
+    if (primitiveCount) {
+        if (!usable_device()) return out.give_up(b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)"));
+        const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
+        GatherArgs a; a.sources = table.data(); a.sourceCount = count; a.selection = g.selection; a.primitiveCount = primitiveCount; a.descTotal = (uint32_t)descs; a.flags = g.flags;
+        const auto no_memory = [&] { return out.give_up(b.log.failure("[Failure] - out of device memory for the gather scratch")); };
+        PoolBlock head(b.devPool.get(), gather_head_bytes(a)), staging;
+        if (!head.p) return no_memory();
+        // (after a failed launch the scratch goes back only when nothing can still touch it)
+        const auto failed = [&] { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); return out.give_up(b.log.failure("[Failure] - the gather kernels could not run")); };
+        GatherPlan plan;
+        if (gather_plan(a, head.p, &plan, stream) != hipSuccess) return failed();
+        if (plan.stagingBytes && !staging.acquire(b.devPool.get(), (size_t)plan.stagingBytes)) return no_memory();
+        RebuildCounts n;
+        if (gather_stage(a, head.p, staging.p, plan, &n, stream) != hipSuccess) return failed();
+        const ommResult sized = out.allocate(n);
+        if (sized != ommResult_SUCCESS) return sized;
+        info.arrayDataSize = n.arrayBytes; info.descArrayCount = n.descCount; info.primitiveCount = primitiveCount; info.referencedBlocks = plan.referenced;
+        info.uniformBlocks = n.uniform; info.duplicateBlocks = n.duplicate; info.skippedPrimitives = plan.skipped;
+        if (out.res) {
+            const DeviceResult& R = out.res->R;
+            GatherOutputs o; o.arrayData = R.arrayData; o.descs = R.descs; o.index = (int32_t*)R.index; o.hist = out.hist;
+            if (gather_emit(a, head.p, staging.p, n, o, stream) != hipSuccess) return failed();
+        }
+    }
+    out.finish(outResult);
+    if (outInfo) *outInfo = info;
+    return ommResult_SUCCESS;
+}
+}
+
+OMM_MI355X_API ommResult ommxGatherMicromaps(ommBaker baker, const ommCpuBakeResultDesc* const* deviceResults, uint32_t resultCount, const ommxGatherDesc* desc,
+                                             ommxDeviceBakeResult* outResult, ommxGatherInfo* outInfo, void* hipStream)
+{
+    if (baker == 0) return ommResult_INVALID_ARGUMENT;
+    if (tag_of(baker) != kCpuBaker && tag_of(baker) != kGpuBaker) return ommResult_INVALID_ARGUMENT;
+    Baker* b = untag<Baker>(baker);
+    if (deviceResults == nullptr) return b->log.invalid("[Invalid Arg] - deviceResults was not set");
+    if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxGatherDesc was not set");
+    if (resultCount == 0 || resultCount > OMMX_GATHER_MAX_SOURCES) return b->log.invalid("[Invalid Arg] - resultCount must be 1..OMMX_GATHER_MAX_SOURCES (4096)");
+    for (uint32_t k = 0; k < resultCount; ++k)
+        if (deviceResults[k] == nullptr) return b->log.invalid("[Invalid Arg] - an element of deviceResults was not set");
+    if (outResult == nullptr && outInfo == nullptr) return b->log.invalid("[Invalid Arg] - neither outResult nor outInfo was set");
+    return guarded(&b->log, [&] { return gather_device(*b, deviceResults, resultCount, *desc, outResult, outInfo, (hipStream_t)hipStream); });
 }
 
 // Any-hit resolution of hits against a device-resident result (include/omm_mi355x_ext.h; kernels in lookup_kernels.hip).  The desc is checked as
