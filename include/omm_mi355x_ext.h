@@ -379,10 +379,13 @@ OMM_MI355X_API ommResult ommxExpandMicroNodes(const ommxMicroNode* nodes, uint64
  *                        unknown states the same way).
  *   uniform blocks       an output block whose states all equal s is uniform.  Without DisableSpecialIndices it is not emitted and its primitives
  *                        get the entry -(s + 1); this holds for blocks with L <= T too.
- *   duplicates           without DisableDuplicateDetection two output blocks are one when level, format and every byte are equal (a 64-bit
- *                        digest finds the candidates, the bytes confirm).  The representative of a class is its member with the lowest SOURCE
- *                        descriptor index.  A source descriptor selected by several primitives is always reduced once and yields one block,
- *                        with or without the flag.
+ *   duplicates           without DisableDuplicateDetection two output blocks are one when level, format and every byte are equal.  A 64-bit
+ *                        digest of the bytes, keyed with level and format, finds ONE candidate per block -- the block with the lowest SOURCE
+ *                        descriptor index under the same key -- and level, format and bytes confirm it.  The representative of a class is its
+ *                        member with the lowest source descriptor index.  A block that shares its key with a lower block of other bytes (a
+ *                        collision: never seen on baked data, but constructible) is kept, and so is every later block equal to it: each is
+ *                        compared with the same candidate only.  That is a loss of compression, never a wrong state, and deterministic.  A
+ *                        source descriptor selected by several primitives is always reduced once and yields one block, with or without the flag.
  *   order, offsets       output descriptors are ordered by block size in bytes descending, then by representative source index ascending; a
  *                        block's size is max(1, 4^T * bits / 8).  Blocks are packed without gaps from offset 0; sizes are powers of two in
  *                        descending order, so every block is naturally aligned.  An output larger than a 32-bit descriptor offset can express
@@ -447,9 +450,11 @@ OMM_MI355X_API ommResult ommxCoarsenMicromap(ommBaker baker, const ommCpuBakeRes
  *                        r & 1, which is ommx_force_2state(r).  The rule is symmetric and associative (the join of ommxCoarsenMicromap's rule).
  *   only special entries no block is made: the output entry is -(r + 1) for format 2 and -((r & 1) + 1) for format 1.
  *   uniform blocks       an output block whose states all equal s is always promoted: it is not emitted and its primitives get the entry -(s + 1).
- *   duplicates           two output blocks are one when their level and every byte are equal (a 64-bit digest finds the candidates, the bytes
- *                        confirm; two blocks that collide in the digest without being equal are both kept -- a loss of compression, never a wrong
- *                        state).  The representative of a class is the member whose lowest primitive index is lowest.
+ *   duplicates           two output blocks are one when their level and every byte are equal.  A 64-bit digest of the bytes, keyed with the level,
+ *                        finds ONE candidate per block -- the block under the same key whose tuple has the lowest primitive index -- and level
+ *                        and bytes confirm it.  A block that shares its key with a lower block of other bytes is kept, and so is every later
+ *                        block equal to it: each is compared with the same candidate only -- a loss of compression, never a wrong state, and
+ *                        deterministic.  The representative of a class is the member whose lowest primitive index is lowest.
  *   order, offsets       output descriptors are ordered by block size in bytes descending, then by the representative's lowest primitive index
  *                        ascending.  Blocks are packed from offset 0 without gaps; a block's size is max(1, 4^T * bits / 8), and the unused bits of a
  *                        one-byte block are zero.  An arrayDataSize above what a 32-bit descriptor offset can express is FAILURE with a log line.
@@ -512,9 +517,11 @@ OMM_MI355X_API ommResult ommxCombineMicromaps(ommBaker baker, const ommCpuBakeRe
  *                        [offset, offset + size) of a block is read: a block may end at the last byte of the caller's allocation.
  *   uniform blocks       as in ommxCoarsenMicromap: a block whose states all equal s is uniform; without DisableSpecialIndices it is not emitted and
  *                        its primitives get the entry -(s + 1).
- *   duplicates           as in ommxCoarsenMicromap: without DisableDuplicateDetection two blocks are one when level, format and every byte are equal
- *                        (a 64-bit digest finds the candidates, the bytes confirm).  An item's rank is (k, e) in lexicographic order; the
- *                        representative of a class is its lowest-ranked member.
+ *   duplicates           as in ommxCoarsenMicromap: without DisableDuplicateDetection two blocks are one when level, format and every byte are equal.
+ *                        An item's rank is (k, e) in lexicographic order.  A 64-bit digest of the bytes, keyed with level and format, finds ONE
+ *                        candidate per block -- the lowest-ranked block under the same key -- and level, format and bytes confirm it; the
+ *                        representative of a class is its lowest-ranked member.  A block that shares its key with a lower-ranked block of other
+ *                        bytes is kept, and so is every later block equal to it -- a loss of compression, never a wrong state, and deterministic.
  *   order, offsets       output descriptors are ordered by block size in bytes descending, then by the representative's rank ascending; a block's
  *                        size is max(1, 4^level * bits / 8).  Blocks are packed without gaps from offset 0; every size is a power of two, so every
  *                        block is naturally aligned.  An arrayDataSize above what a 32-bit descriptor offset can express is FAILURE with a log line.

@@ -28,7 +28,7 @@ inline HashTable hash_table_at(void* base, uint32_t slots)   // layout: keys | v
 inline size_t hash_table_bytes(uint32_t slots, uint32_t extraWords = 0) { return (size_t)slots * 8 + ((size_t)slots + 1 + extraWords) * 4; }
 
 // Fibonacci hashing: the keys of the UV dedup can be small integers (triangles that must not merge), the digests are already mixed
-__device__ __forceinline__ uint32_t hash_slot_of(const HashTable& t, uint64_t k) { return (uint32_t)((k * 0x9E3779B97F4A7C15ull) >> t.shift); }
+__host__ __device__ __forceinline__ uint32_t hash_slot_of(const HashTable& t, uint64_t k) { return (uint32_t)((k * 0x9E3779B97F4A7C15ull) >> t.shift); }
 
 // probe for `k` (claiming an empty slot if it is not in the table yet) and lower the slot's value to `i`.  Plain (L2-coherent) loads
 // first: a slot's value only ever decreases, so a value <= i read here -- however stale -- proves that i is not the first occurrence and

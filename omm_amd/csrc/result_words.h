@@ -15,15 +15,15 @@ __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int d)
     const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d);
     return ((uint64_t)hi << 32) | lo;
 }
-__device__ __forceinline__ uint64_t mix64(uint64_t x)
+__host__ __device__ __forceinline__ uint64_t mix64(uint64_t x)
 {
     x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
     return x;
 }
 // the digest of a block is the sum of these over its 64-bit words (the last one padded with zeros): any partition of the words gives the same sum
-__device__ __forceinline__ uint64_t word_digest(uint64_t w, uint64_t index) { return mix64(w ^ ((index + 1u) * 0x9E3779B97F4A7C15ull)); }
+__host__ __device__ __forceinline__ uint64_t word_digest(uint64_t w, uint64_t index) { return mix64(w ^ ((index + 1u) * 0x9E3779B97F4A7C15ull)); }
 // the hash-table key of a block (its value never shows in a result: equal keys are confirmed by level, format and bytes)
-__device__ __forceinline__ uint64_t block_key(uint64_t digest, uint32_t level, uint32_t bits) { return mix64(digest + (uint64_t)((level << 2) | bits) * 0xD6E8FEB86659FD93ull); }
+__host__ __device__ __forceinline__ uint64_t block_key(uint64_t digest, uint32_t level, uint32_t bits) { return mix64(digest + (uint64_t)((level << 2) | bits) * 0xD6E8FEB86659FD93ull); }
 
 // a workgroup's counters: zeroed, added to in LDS, then one global atomic per counter that is not zero
 template <uint32_t N> __device__ __forceinline__ void counters_begin(uint32_t* s) { if (threadIdx.x < N) s[threadIdx.x] = 0u; __syncthreads(); }

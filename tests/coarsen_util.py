@@ -76,10 +76,16 @@ def _valid(desc, size):
     return l <= 12 and f in (1, 2) and o + su.block_bytes(l, f) <= size
 
 
-def restate_coarsen(array_data, descs, index, index_format, max_level, mixed=3, flags=0, array_data_size=None, unpacked=None):
+def representatives(merge, order, items):
+    """a merge rule other than "equal level, format and bytes" (tests/rebuild_cases.py): merge([(level, format, bytes)] in item order) answers each
+    item's representative as a position in that list -> {item: representative item}"""
+    return {d: order[int(c)] for d, c in zip(order, merge(items))}
+
+
+def restate_coarsen(array_data, descs, index, index_format, max_level, mixed=3, flags=0, array_data_size=None, unpacked=None, merge=None):
     """What ommxCoarsenMicromap answers, from host copies (array_data uint8, descs (D, 3) rows of (offset, level, format), index signed) -> dict:
     array (uint8), descs (E, 3) int64, index (in the format's dtype), array_hist / index_hist ({(level, format): count}), info ({field: int}).
-    unpacked: a dict that keeps the unpacked states of the source blocks between calls on the same arrays"""
+    unpacked: a dict that keeps the unpacked states of the source blocks between calls on the same arrays; merge: see representatives()"""
     size = len(array_data) if array_data_size is None else array_data_size
     descs = np.asarray(descs, np.int64).reshape(-1, 3)
     e = np.asarray(index).astype(np.int64)
@@ -119,6 +125,9 @@ def restate_coarsen(array_data, descs, index, index_format, max_level, mixed=3, 
             info["duplicateBlocks"] += 1
         else:
             rep[d] = seen[key] = d
+    if merge is not None and not flags & NO_DEDUP:
+        rep = representatives(merge, sorted(blocks), [target_of[d] + (blocks[d],) for d in sorted(blocks)])
+        info["duplicateBlocks"] = sum(d != r for d, r in rep.items())
     emitted = sorted((d for d in blocks if rep[d] == d), key=lambda d: (-len(blocks[d]), d))
     place = {d: j for j, d in enumerate(emitted)}
     out_descs, at = [], 0

@@ -72,10 +72,11 @@ def _valid_rows(descs, size):
     return ok & (d[:, 0] + bytes_ <= size)
 
 
-def restate_combine(sources, fmt, mixed=3, unpacked=None):
+def restate_combine(sources, fmt, mixed=3, unpacked=None, merge=None):
     """What ommxCombineMicromaps answers.  sources: [(array_data uint8, descs (D, 3) rows of (offset, level, format), index, arrayDataSize or None)] ->
     dict: array (uint8), descs (E, 3) int64, index (int32), array_hist / index_hist ({(level, format): count}), info ({field: int}).
-    unpacked: a dict that keeps the unpacked states of source blocks between calls on the same sources (keyed by id of the array)"""
+    unpacked: a dict that keeps the unpacked states of source blocks between calls on the same sources (keyed by id of the array); merge: see
+    coarsen_util.representatives()"""
     K = len(sources)
     T = len(sources[0][2])
     entries = np.stack([np.asarray(s[2]).astype(np.int64) for s in sources], 1) if T else np.zeros((0, K), np.int64)
@@ -139,6 +140,9 @@ def restate_combine(sources, fmt, mixed=3, unpacked=None):
             info["duplicateBlocks"] += 1
         else:
             rep[t] = seen[key] = t
+    if merge is not None:
+        rep = cu.representatives(merge, sorted(blocks), [(level_of[t], fmt, blocks[t]) for t in sorted(blocks)])
+        info["duplicateBlocks"] = sum(t != r for t, r in rep.items())
     emitted = sorted((t for t in blocks if rep[t] == t), key=lambda t: (-len(blocks[t]), t))
     place = {t: j for j, t in enumerate(emitted)}
     out_descs, at = [], 0

@@ -52,10 +52,11 @@ def refs(pairs):
 
 
 # ---- the definition, twice ----
-def restate_gather(sources, selection=None, flags=0, unpacked=None):
+def restate_gather(sources, selection=None, flags=0, unpacked=None, merge=None):
     """What ommxGatherMicromaps answers.  sources: [(array_data uint8, descs (D, 3) rows of (offset, level, format), index, arrayDataSize or None)];
     selection: None or (N, 2) rows of (source, primitive) -> dict: array (uint8), descs (E, 3) int64, index (int32), array_hist / index_hist
-    ({(level, format): count}), info ({field: int}).  unpacked: a dict that keeps the packed bytes of source blocks between calls on the same sources"""
+    ({(level, format): count}), info ({field: int}).  unpacked: a dict that keeps the packed bytes of source blocks between calls on the same sources;
+    merge: see coarsen_util.representatives()"""
     K = len(sources)
     counts = np.array([len(s[2]) for s in sources], np.int64)
     tables = [np.asarray(s[1], np.int64).reshape(-1, 3) for s in sources]
@@ -116,6 +117,9 @@ def restate_gather(sources, selection=None, flags=0, unpacked=None):
             info["duplicateBlocks"] += 1
         else:
             rep[it] = seen[key] = it
+    if merge is not None and not flags & NO_DEDUP:
+        rep = cu.representatives(merge, sorted(blocks), [kind[it] + (blocks[it],) for it in sorted(blocks)])
+        info["duplicateBlocks"] = sum(it != r for it, r in rep.items())
     emitted = sorted((it for it in blocks if rep[it] == it), key=lambda it: (-len(blocks[it]), it))
     place = {it: j for j, it in enumerate(emitted)}
     out_descs, at = [], 0
