@@ -19,15 +19,11 @@ struct CoarsenPlan {               // after the index buffer has been read
     uint32_t skipped, deepBlocks;  // skipped primitives; blocks that need a second reduction pass
     uint32_t referenced, coarsened;   // selected blocks; those above maxLevel
 };
-struct CoarsenOutputs {            // device memory of the new result; hist: host memory, [2][kRebuildLevels][2] = array | index, level, format - 1
-    uint8_t* arrayData; ommCpuOpacityMicromapDesc* descs; void* index;
-    uint32_t* hist;
-};
 
 size_t coarsen_head_bytes(const CoarsenArgs& a);
 // each: every launch on `stream`, the answer copied to the host, the stream synchronised.  indexCount must be > 0.
 hipError_t coarsen_plan(const CoarsenArgs& a, void* head, CoarsenPlan* out, hipStream_t stream);
 hipError_t coarsen_reduce(const CoarsenArgs& a, void* head, void* staging, const CoarsenPlan& plan, RebuildCounts* out, hipStream_t stream);
-hipError_t coarsen_emit(const CoarsenArgs& a, void* head, const void* staging, const RebuildCounts& counts, const CoarsenOutputs& o, hipStream_t stream);
+hipError_t coarsen_emit(const CoarsenArgs& a, void* head, const void* staging, const RebuildCounts& counts, const RebuildOutputs& o, hipStream_t stream);   // o.index: the source's format
 
 } // namespace ommx

@@ -16,12 +16,10 @@
 // All counters are integers and every output byte has one writer, so the result does not depend on the order of arrival.
 #include <hip/hip_runtime.h>
 #include <string.h>
-#include <rocprim/rocprim.hpp>
 #include "coarsen_kernels.h"
 #include "coarsen_reduce.h"
 #include "result_read.h"
 #include "result_words.h"
-#include "bake_host.h"   // pad256
 #include "wave_search.h"
 
 namespace ommx {
@@ -57,15 +55,10 @@ __global__ __launch_bounds__(kCoBlock) void coarsen_mark(ommCpuBakeResultDesc r,
 {
     __shared__ uint32_t s_n[1];
     counters_begin<1>(s_n);
+    const ResultView s = view_of(r);
     uint32_t skipped = 0;
     const uint64_t stride = (uint64_t)gridDim.x * kCoBlock;
-    for (uint64_t i = (uint64_t)blockIdx.x * kCoBlock + threadIdx.x; i < r.indexCount; i += stride) {
-        const int32_t e = index_entry(r.indexBuffer, (int)r.indexFormat, i);
-        if (e < 0) { skipped += e < -4 ? 1u : 0u; continue; }
-        bool ok = (uint32_t)e < r.descArrayCount;
-        if (ok) ok = desc_ok(load_desc(r.descArray + e), r.arrayDataSize);
-        if (ok) atomicOr(&ref[e], 1u); else skipped++;
-    }
+    for (uint64_t i = (uint64_t)blockIdx.x * kCoBlock + threadIdx.x; i < s.indexCount; i += stride) skipped += mark_selected(s, i, ref);
     if (skipped) atomicAdd(&s_n[0], skipped);
     counters_end<1>(s_n, &hdr->skipped);
 }
@@ -203,81 +196,46 @@ __global__ __launch_bounds__(kCoBlock) void coarsen_index(ommCpuBakeResultDesc r
 {
     __shared__ uint32_t s_n[kRebuildHist];
     counters_begin<kRebuildHist>(s_n);
+    const ResultView s = view_of(r);
     const uint64_t stride = (uint64_t)gridDim.x * kCoBlock;
-    for (uint64_t i = (uint64_t)blockIdx.x * kCoBlock + threadIdx.x; i < r.indexCount; i += stride) {
-        const int32_t e = index_entry(r.indexBuffer, (int)r.indexFormat, i);
-        int32_t v = -4;
-        uint32_t w;
-        if (e < 0) v = e >= -4 ? e : -4;
-        else if ((uint32_t)e < r.descArrayCount && (w = item[e]) != 0u) {   // (marked: it passed the bounds rule)
-            v = tail.special[e];
-            if (v == 0) {
-                v = (int32_t)tail.newIndex[tail.rep[e]];
-                atomicAdd(&s_n[2u * item_level(w) + item_bits(w) - 1u], 1u);
-            }
-        }
-        index_store(outIndex, (int)r.indexFormat, i, v);
-    }
+    for (uint64_t i = (uint64_t)blockIdx.x * kCoBlock + threadIdx.x; i < s.indexCount; i += stride)
+        index_store(outIndex, s.indexFormat, i, index_back(s, i, item, 0u, tail, s_n));
     counters_end<kRebuildHist>(s_n, tail.indexHist);
 }
 
-struct CoarsenLayout { size_t header, ref, item, slot, units, digest, umask, deepList, temp, tail, bytes; size_t tempBytes; };
-CoarsenLayout coarsen_layout(const CoarsenArgs& a)
+// the call's scratch: the header and the marks behind it (ONE memset clears both), the deep list, the arrays of the tail
+struct CoarsenScratch { CoarsenHeader* hdr; uint32_t *ref, *deepList; TailArrays t; size_t bytes; };
+CoarsenScratch coarsen_scratch(const CoarsenArgs& a, void* base)
 {
-    CoarsenLayout L; size_t o = 0;
+    CoarsenScratch s; CarveCursor c{ (uintptr_t)base };
     const size_t D = a.result.descArrayCount;
-    const auto take = [&o](size_t bytes) { const size_t at = o; o += pad256(bytes); return at; };
-    L.header = take(sizeof(CoarsenHeader));
-    L.ref = take(4 * D); L.item = take(4 * D);
-    L.slot = take(8 * (D + 1)); L.units = take(8 * (D + 1));
-    L.digest = take(8 * D); L.umask = take(4 * D); L.deepList = take(4 * D);
-    L.tempBytes = 0;
-    if (D) (void)rocprim::exclusive_scan(nullptr, L.tempBytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, 0ull, D + 1, rocprim::plus<unsigned long long>());
-    L.temp = take(L.tempBytes);
-    L.tail = take(rebuild_bytes(a.result.descArrayCount, a.flags));
-    L.bytes = o;
-    return L;
-}
-RebuildInputs tail_inputs(const CoarsenArgs& a, const CoarsenLayout& L, uint8_t* base, const void* staging)
-{
-    RebuildInputs in;
-    in.items = a.result.descArrayCount; in.flags = a.flags;
-    in.item = (const uint32_t*)(base + L.item); in.slotStart = (const unsigned long long*)(base + L.slot);
-    in.digest = (const unsigned long long*)(base + L.digest); in.umask = (const uint32_t*)(base + L.umask);
-    in.staging = (const uint8_t*)staging; in.scratch = base + L.tail;
-    return in;
+    s.hdr = c.take<CoarsenHeader>(1); s.ref = c.take<uint32_t>(D);
+    s.deepList = c.take<uint32_t>(D);
+    s.t = rebuild_arrays(c, a.result.descArrayCount, a.flags);
+    s.bytes = (size_t)(c.at - (uintptr_t)base);
+    return s;
 }
 
 } // namespace
 
-size_t coarsen_head_bytes(const CoarsenArgs& a) { return coarsen_layout(a).bytes; }
+size_t coarsen_head_bytes(const CoarsenArgs& a) { return coarsen_scratch(a, nullptr).bytes; }
 
 hipError_t coarsen_plan(const CoarsenArgs& a, void* head, CoarsenPlan* out, hipStream_t stream)
 {
-    const CoarsenLayout L = coarsen_layout(a);
-    uint8_t* base = (uint8_t*)head;
+    const CoarsenScratch s = coarsen_scratch(a, head);
     const ommCpuBakeResultDesc& r = a.result;
     const uint32_t D = r.descArrayCount;
-    CoarsenHeader* hdr = (CoarsenHeader*)(base + L.header);
-    uint32_t* ref = (uint32_t*)(base + L.ref);
-    unsigned long long* slot = (unsigned long long*)(base + L.slot);
-    unsigned long long* units = (unsigned long long*)(base + L.units);
-    REBUILD_CHECK(hipMemsetAsync(hdr, 0, L.ref - L.header + 4 * (size_t)D, stream));   // (the header and the marks behind it)
-    coarsen_mark<<<strided_grid(r.indexCount), kCoBlock, 0, stream>>>(r, ref, hdr);
+    REBUILD_CHECK(hipMemsetAsync(s.hdr, 0, (size_t)((uint8_t*)s.ref - (uint8_t*)s.hdr) + 4 * (size_t)D, stream));   // (the header and the marks behind it)
+    coarsen_mark<<<strided_grid(r.indexCount), kCoBlock, 0, stream>>>(r, s.ref, s.hdr);
     REBUILD_CHECK(hipGetLastError());
     unsigned long long stagingBytes = 0;
     if (D) {
-        coarsen_prepare<<<per_item_grid((uint64_t)D + 1u), kCoBlock, 0, stream>>>(r, a.maxLevel, ref, (uint32_t*)(base + L.item), slot, units, (unsigned long long*)(base + L.digest),
-                                                                                 (uint32_t*)(base + L.umask), (uint32_t*)(base + L.deepList), hdr);
+        coarsen_prepare<<<per_item_grid((uint64_t)D + 1u), kCoBlock, 0, stream>>>(r, a.maxLevel, s.ref, s.t.item, s.t.slotStart, s.t.units, s.t.digest, s.t.umask, s.deepList, s.hdr);
         REBUILD_CHECK(hipGetLastError());
-        size_t tb = L.tempBytes;   // (in place: every element is read before it is written)
-        REBUILD_CHECK(rocprim::exclusive_scan(base + L.temp, tb, slot, slot, 0ull, (size_t)D + 1, rocprim::plus<unsigned long long>(), stream));
-        tb = L.tempBytes;
-        REBUILD_CHECK(rocprim::exclusive_scan(base + L.temp, tb, units, units, 0ull, (size_t)D + 1, rocprim::plus<unsigned long long>(), stream));
-        REBUILD_CHECK(hipMemcpyAsync(&stagingBytes, slot + D, sizeof stagingBytes, hipMemcpyDeviceToHost, stream));
+        REBUILD_CHECK(rebuild_scan(s.t, D, &stagingBytes, nullptr, stream));   // (the units' sum is not read back: coarsen_reduce sizes its grid from a bound)
     }
     CoarsenHeader h;
-    REBUILD_CHECK(hipMemcpyAsync(&h, hdr, sizeof h, hipMemcpyDeviceToHost, stream));
+    REBUILD_CHECK(hipMemcpyAsync(&h, s.hdr, sizeof h, hipMemcpyDeviceToHost, stream));
     REBUILD_CHECK(hipStreamSynchronize(stream));
     out->stagingBytes = stagingBytes; out->skipped = h.skipped; out->deepBlocks = h.deepBlocks; out->referenced = h.referenced; out->coarsened = h.coarsened;
     return hipSuccess;
@@ -285,32 +243,26 @@ hipError_t coarsen_plan(const CoarsenArgs& a, void* head, CoarsenPlan* out, hipS
 
 hipError_t coarsen_reduce(const CoarsenArgs& a, void* head, void* staging, const CoarsenPlan& plan, RebuildCounts* out, hipStream_t stream)
 {
-    const CoarsenLayout L = coarsen_layout(a);
-    uint8_t* base = (uint8_t*)head;
+    const CoarsenScratch s = coarsen_scratch(a, head);
     const ommCpuBakeResultDesc& r = a.result;
     const uint32_t D = r.descArrayCount;
     if (D) {
-        const unsigned long long* slot = (const unsigned long long*)(base + L.slot);
-        unsigned long long* digest = (unsigned long long*)(base + L.digest);
-        uint32_t* umask = (uint32_t*)(base + L.umask);
         // no read-back to size the grid: blocks that do not overlap have at most this many units, and the kernel strides over any more
         const uint64_t bound = (uint64_t)r.arrayDataSize / (kCoUnitFields / 8u) + D;
-        coarsen_units<<<(uint32_t)(bound < kRebuildMaxGrid ? bound : kRebuildMaxGrid), kCoBlock, 0, stream>>>(r, a.maxLevel, a.mixedState, (const unsigned long long*)(base + L.units), slot,
-                                                                                                            (uint8_t*)staging, digest, umask);
+        coarsen_units<<<(uint32_t)(bound < kRebuildMaxGrid ? bound : kRebuildMaxGrid), kCoBlock, 0, stream>>>(r, a.maxLevel, a.mixedState, s.t.units, s.t.slotStart, (uint8_t*)staging,
+                                                                                                            s.t.digest, s.t.umask);
         REBUILD_CHECK(hipGetLastError());
         if (plan.deepBlocks) {
-            coarsen_deep<<<plan.deepBlocks, kCoBlock, 0, stream>>>(r, a.maxLevel, a.mixedState, (const uint32_t*)(base + L.deepList), slot, (uint8_t*)staging, digest, umask);
+            coarsen_deep<<<plan.deepBlocks, kCoBlock, 0, stream>>>(r, a.maxLevel, a.mixedState, s.deepList, s.t.slotStart, (uint8_t*)staging, s.t.digest, s.t.umask);
             REBUILD_CHECK(hipGetLastError());
         }
     }
-    return rebuild_count(tail_inputs(a, L, base, staging), out, stream);
+    return rebuild_count(tail_inputs(s.t, D, a.flags, staging), out, stream);
 }
 
-hipError_t coarsen_emit(const CoarsenArgs& a, void* head, const void* staging, const RebuildCounts& counts, const CoarsenOutputs& o, hipStream_t stream)
+hipError_t coarsen_emit(const CoarsenArgs& a, void* head, const void* staging, const RebuildCounts& counts, const RebuildOutputs& o, hipStream_t stream)
 {
-    const CoarsenLayout L = coarsen_layout(a);
-    uint8_t* base = (uint8_t*)head;
-    const RebuildInputs in = tail_inputs(a, L, base, staging);
+    const RebuildInputs in = tail_inputs(coarsen_scratch(a, head).t, a.result.descArrayCount, a.flags, staging);
     REBUILD_CHECK(rebuild_emit(in, counts, o.arrayData, o.descs, stream));
     coarsen_index<<<strided_grid(a.result.indexCount), kCoBlock, 0, stream>>>(a.result, in.item, rebuild_tables(in), o.index);
     REBUILD_CHECK(hipGetLastError());

@@ -8,12 +8,8 @@
 
 namespace ommx {
 
-struct CombineSource {             // arrays in device memory; indexFormat already checked
-    const uint8_t* arrayData; const ommCpuOpacityMicromapDesc* descs; const void* index;
-    uint32_t arrayDataSize, descCount; int32_t indexFormat; uint32_t pad;
-};
 struct CombineArgs {
-    CombineSource source[OMMX_COMBINE_MAX_SOURCES];
+    ResultView source[OMMX_COMBINE_MAX_SOURCES];   // (result_read.h)
     uint32_t sourceCount;          // 1..16
     uint32_t indexCount;           // of every source, > 0
     uint32_t format;               // of every output block: 1 or 2
@@ -27,10 +23,6 @@ struct CombinePlan {               // after the tuples have been listed
     uint64_t units;                // work units of the streaming pass
     uint32_t refined;              // tuples with a block coarser than their output
 };
-struct CombineOutputs {            // device memory of the new result; hist: host memory, [2][kRebuildLevels][2] = array | index, level, format - 1
-    uint8_t* arrayData; ommCpuOpacityMicromapDesc* descs; int32_t* index;
-    uint32_t* hist;
-};
 
 size_t combine_head_bytes(const CombineArgs& a);                     // scratch per primitive
 size_t combine_tuple_bytes(const CombineArgs& a, uint32_t tuples);   // scratch per tuple
@@ -38,8 +30,8 @@ size_t combine_tuple_bytes(const CombineArgs& a, uint32_t tuples);   // scratch 
 hipError_t combine_tuples(const CombineArgs& a, void* head, CombineTuples* out, hipStream_t stream);
 hipError_t combine_plan(const CombineArgs& a, void* head, void* perTuple, const CombineTuples& t, CombinePlan* out, hipStream_t stream);
 hipError_t combine_join(const CombineArgs& a, void* perTuple, void* staging, const CombineTuples& t, const CombinePlan& plan, RebuildCounts* out, hipStream_t stream);
-// perTuple and staging may be null when t.tuples == 0
+// perTuple and staging may be null when t.tuples == 0; o.index: 32-bit entries
 hipError_t combine_emit(const CombineArgs& a, void* head, void* perTuple, const void* staging, const CombineTuples& t, const RebuildCounts& counts,
-                        const CombineOutputs& o, hipStream_t stream);
+                        const RebuildOutputs& o, hipStream_t stream);
 
 } // namespace ommx

@@ -44,7 +44,7 @@ __device__ __forceinline__ uint32_t norm_level(uint64_t n) { return (uint32_t)(n
 __device__ __forceinline__ uint32_t norm_state(uint64_t n) { return (uint32_t)(n >> 48) & 3u; }
 
 // entry e of a source -> false: it fails the rule; otherwise its normalised form
-__device__ __forceinline__ bool normalise(const CombineSource& s, int32_t e, uint64_t* out)
+__device__ __forceinline__ bool normalise(const ResultView& s, int32_t e, uint64_t* out)
 {
     if (e < 0) { *out = norm_special((uint32_t)(-(e + 1))); return e >= -4; }
     if ((uint32_t)e >= s.descCount) return false;
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(kCbBlock) void combine_entries(CombineArgs a, HashT
         uint32_t allSide = 1u, anySide = 0u, anyUnknown = 0u;
         uint64_t h = 0ull;
         for (uint32_t k = 0; k < a.sourceCount && ok; ++k) {
-            const CombineSource& s = a.source[k];
+            const ResultView& s = a.source[k];
             const int32_t e = index_entry(s.index, s.indexFormat, i);
             uint64_t n = 0ull;
             ok = normalise(s, e, &n);
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(kCbBlock) void combine_leaders(CombineArgs a, HashT
         if (c != (uint32_t)i) {   // (two tuples under one 64-bit hash: the later one is joined on its own, and merged again as a duplicate)
             bool same = true;
             for (uint32_t k = 0; k < a.sourceCount && same; ++k) {
-                const CombineSource& s = a.source[k];
+                const ResultView& s = a.source[k];
                 same = index_entry(s.index, s.indexFormat, c) == index_entry(s.index, s.indexFormat, i);
             }
             if (!same) c = (uint32_t)i;
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(kCbBlock) void combine_prepare(CombineArgs a, uint3
         const uint32_t t = tupleStart[i];
         uint32_t top = 0u, low = kResultMaxLevel;
         for (uint32_t k = 0; k < a.sourceCount; ++k) {
-            const CombineSource& s = a.source[k];
+            const ResultView& s = a.source[k];
             uint64_t n = 0ull;
             (void)normalise(s, index_entry(s.index, s.indexFormat, i), &n);   // (it passed in combine_entries)
             norm[(uint64_t)t * a.sourceCount + k] = n;
@@ -209,12 +209,7 @@ __global__ __launch_bounds__(kCbBlock) void combine_index(uint32_t indexCount, c
         int32_t v = code[i];
         if (v == 0) {
             const uint32_t t = tupleStart[leader[i]];
-            v = tail.special[t];
-            if (v == 0) {
-                const uint32_t w = item[t];
-                v = (int32_t)tail.newIndex[tail.rep[t]];
-                atomicAdd(&s_n[2u * item_level(w) + item_bits(w) - 1u], 1u);
-            }
+            v = index_back(tail, t, item[t], s_n);
         }
         outIndex[i] = v;
     }
@@ -237,36 +232,21 @@ HeadLayout head_layout(const CombineArgs& a)
     L.bytes = o;
     return L;
 }
-struct TupleLayout { size_t norm, item, slot, units, digest, umask, temp, tail, bytes; size_t tempBytes; };
-TupleLayout tuple_layout(const CombineArgs& a, uint32_t tuples)
+// the scratch per tuple: the normalised entries, the arrays of the tail
+struct TupleScratch { unsigned long long* norm; TailArrays t; size_t bytes; };
+TupleScratch tuple_scratch(const CombineArgs& a, uint32_t tuples, void* base)
 {
-    TupleLayout L; size_t o = 0;
-    const size_t M = tuples;
-    const auto take = [&o](size_t bytes) { const size_t at = o; o += pad256(bytes); return at; };
-    L.norm = take(8 * M * a.sourceCount); L.item = take(4 * M);
-    L.slot = take(8 * (M + 1)); L.units = take(8 * (M + 1));
-    L.digest = take(8 * M); L.umask = take(4 * M);
-    L.tempBytes = 0;
-    (void)rocprim::exclusive_scan(nullptr, L.tempBytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, 0ull, M + 1, rocprim::plus<unsigned long long>());
-    L.temp = take(L.tempBytes);
-    L.tail = take(rebuild_bytes(tuples, 0u));
-    L.bytes = o;
-    return L;
-}
-RebuildInputs tail_inputs(const TupleLayout& U, uint32_t tuples, uint8_t* tb, const void* staging)
-{
-    RebuildInputs in;
-    in.items = tuples; in.flags = 0u;
-    in.item = (const uint32_t*)(tb + U.item); in.slotStart = (const unsigned long long*)(tb + U.slot);
-    in.digest = (const unsigned long long*)(tb + U.digest); in.umask = (const uint32_t*)(tb + U.umask);
-    in.staging = (const uint8_t*)staging; in.scratch = tb + U.tail;
-    return in;
+    TupleScratch s; CarveCursor c{ (uintptr_t)base };
+    s.norm = c.take<unsigned long long>((size_t)tuples * a.sourceCount);
+    s.t = rebuild_arrays(c, tuples, 0u);
+    s.bytes = (size_t)(c.at - (uintptr_t)base);
+    return s;
 }
 
 } // namespace
 
 size_t combine_head_bytes(const CombineArgs& a) { return head_layout(a).bytes; }
-size_t combine_tuple_bytes(const CombineArgs& a, uint32_t tuples) { return tuple_layout(a, tuples).bytes; }
+size_t combine_tuple_bytes(const CombineArgs& a, uint32_t tuples) { return tuple_scratch(a, tuples, nullptr).bytes; }
 
 hipError_t combine_tuples(const CombineArgs& a, void* head, CombineTuples* out, hipStream_t stream)
 {
@@ -298,24 +278,16 @@ hipError_t combine_tuples(const CombineArgs& a, void* head, CombineTuples* out, 
 hipError_t combine_plan(const CombineArgs& a, void* head, void* perTuple, const CombineTuples& t, CombinePlan* out, hipStream_t stream)
 {
     const HeadLayout L = head_layout(a);
-    const TupleLayout U = tuple_layout(a, t.tuples);
-    uint8_t *base = (uint8_t*)head, *tb = (uint8_t*)perTuple;
+    const TupleScratch U = tuple_scratch(a, t.tuples, perTuple);
+    uint8_t* base = (uint8_t*)head;
     const uint32_t N = a.indexCount, M = t.tuples;
     CombineHeader* hdr = (CombineHeader*)(base + L.header);
-    unsigned long long* slot = (unsigned long long*)(tb + U.slot);
-    unsigned long long* units = (unsigned long long*)(tb + U.units);
     combine_prepare<<<per_item_grid((uint64_t)N + 1u), kCbBlock, 0, stream>>>(a, M, (const int32_t*)(base + L.code), (const uint32_t*)(base + L.leader),
-                                                                             (const uint32_t*)(base + L.tupleStart), (unsigned long long*)(tb + U.norm), (uint32_t*)(tb + U.item),
-                                                                             slot, units, (unsigned long long*)(tb + U.digest), (uint32_t*)(tb + U.umask), hdr);
+                                                                             (const uint32_t*)(base + L.tupleStart), U.norm, U.t.item, U.t.slotStart, U.t.units, U.t.digest, U.t.umask, hdr);
     REBUILD_CHECK(hipGetLastError());
-    size_t n = U.tempBytes;   // (in place: every element is read before it is written)
-    REBUILD_CHECK(rocprim::exclusive_scan(tb + U.temp, n, slot, slot, 0ull, (size_t)M + 1, rocprim::plus<unsigned long long>(), stream));
-    n = U.tempBytes;
-    REBUILD_CHECK(rocprim::exclusive_scan(tb + U.temp, n, units, units, 0ull, (size_t)M + 1, rocprim::plus<unsigned long long>(), stream));
     unsigned long long stagingBytes = 0, totalUnits = 0;
+    REBUILD_CHECK(rebuild_scan(U.t, M, &stagingBytes, &totalUnits, stream));
     CombineHeader h;
-    REBUILD_CHECK(hipMemcpyAsync(&stagingBytes, slot + M, sizeof stagingBytes, hipMemcpyDeviceToHost, stream));
-    REBUILD_CHECK(hipMemcpyAsync(&totalUnits, units + M, sizeof totalUnits, hipMemcpyDeviceToHost, stream));
     REBUILD_CHECK(hipMemcpyAsync(&h, hdr, sizeof h, hipMemcpyDeviceToHost, stream));
     REBUILD_CHECK(hipStreamSynchronize(stream));
     out->stagingBytes = stagingBytes; out->units = totalUnits; out->refined = h.refined;
@@ -324,17 +296,14 @@ hipError_t combine_plan(const CombineArgs& a, void* head, void* perTuple, const 
 
 hipError_t combine_join(const CombineArgs& a, void* perTuple, void* staging, const CombineTuples& t, const CombinePlan& plan, RebuildCounts* out, hipStream_t stream)
 {
-    const TupleLayout U = tuple_layout(a, t.tuples);
-    uint8_t* tb = (uint8_t*)perTuple;
-    const RebuildInputs in = tail_inputs(U, t.tuples, tb, staging);
-    combine_units<<<(uint32_t)(plan.units < kRebuildMaxGrid ? plan.units : kRebuildMaxGrid), kCbBlock, 0, stream>>>(a, t.tuples, (const unsigned long long*)(tb + U.norm), in.item,
-                                                                                                                   (const unsigned long long*)(tb + U.units), in.slotStart, (uint8_t*)staging,
-                                                                                                                   (unsigned long long*)(tb + U.digest), (uint32_t*)(tb + U.umask));
+    const TupleScratch U = tuple_scratch(a, t.tuples, perTuple);
+    combine_units<<<(uint32_t)(plan.units < kRebuildMaxGrid ? plan.units : kRebuildMaxGrid), kCbBlock, 0, stream>>>(a, t.tuples, U.norm, U.t.item, U.t.units, U.t.slotStart, (uint8_t*)staging,
+                                                                                                                   U.t.digest, U.t.umask);
     REBUILD_CHECK(hipGetLastError());
-    return rebuild_count(in, out, stream);
+    return rebuild_count(tail_inputs(U.t, t.tuples, 0u, staging), out, stream);
 }
 
-hipError_t combine_emit(const CombineArgs& a, void* head, void* perTuple, const void* staging, const CombineTuples& t, const RebuildCounts& counts, const CombineOutputs& o,
+hipError_t combine_emit(const CombineArgs& a, void* head, void* perTuple, const void* staging, const CombineTuples& t, const RebuildCounts& counts, const RebuildOutputs& o,
                         hipStream_t stream)
 {
     const HeadLayout L = head_layout(a);
@@ -342,12 +311,12 @@ hipError_t combine_emit(const CombineArgs& a, void* head, void* perTuple, const 
     RebuildInputs in; memset(&in, 0, sizeof in);
     RebuildTables tail; memset(&tail, 0, sizeof tail);
     if (t.tuples) {
-        in = tail_inputs(tuple_layout(a, t.tuples), t.tuples, (uint8_t*)perTuple, staging);
+        in = tail_inputs(tuple_scratch(a, t.tuples, perTuple).t, t.tuples, 0u, staging);
         tail = rebuild_tables(in);
         REBUILD_CHECK(rebuild_emit(in, counts, o.arrayData, o.descs, stream));
     }
     combine_index<<<strided_grid(a.indexCount), kCbBlock, 0, stream>>>(a.indexCount, (const int32_t*)(base + L.code), (const uint32_t*)(base + L.leader),
-                                                                       (const uint32_t*)(base + L.tupleStart), in.item, tail, o.index);
+                                                                       (const uint32_t*)(base + L.tupleStart), in.item, tail, (int32_t*)o.index);
     REBUILD_CHECK(hipGetLastError());
     return t.tuples ? rebuild_histograms(in, o.hist, stream) : hipStreamSynchronize(stream);   // (hist: the caller's zeros stand)
 }

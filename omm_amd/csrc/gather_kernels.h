@@ -8,9 +8,8 @@
 
 namespace ommx {
 
-struct GatherSource {              // a row of the source table; arrays in device memory; indexFormat already checked
-    const uint8_t* arrayData; const ommCpuOpacityMicromapDesc* descs; const void* index;
-    uint32_t arrayDataSize, descCount, indexCount; int32_t indexFormat;
+struct GatherSource {              // a row of the source table
+    ResultView view;               // (result_read.h)
     uint32_t primBase, descBase;   // exclusive scans of indexCount and descCount over the sources
 };
 struct GatherArgs {
@@ -26,16 +25,12 @@ struct GatherPlan {                // after the selection and the index buffers 
     uint64_t units;                // work units of the copy
     uint32_t skipped, referenced;  // skipped primitives; distinct accepted (source, descriptor) pairs
 };
-struct GatherOutputs {             // device memory of the new result; hist: host memory, [2][kRebuildLevels][2] = array | index, level, format - 1
-    uint8_t* arrayData; ommCpuOpacityMicromapDesc* descs; int32_t* index;
-    uint32_t* hist;
-};
 
 size_t gather_head_bytes(const GatherArgs& a);
 // each: every launch on `stream`, the answer copied to the host, the stream synchronised
 hipError_t gather_plan(const GatherArgs& a, void* head, GatherPlan* out, hipStream_t stream);
 // staging may be null when plan.units == 0
 hipError_t gather_stage(const GatherArgs& a, void* head, void* staging, const GatherPlan& plan, RebuildCounts* out, hipStream_t stream);
-hipError_t gather_emit(const GatherArgs& a, void* head, const void* staging, const RebuildCounts& counts, const GatherOutputs& o, hipStream_t stream);
+hipError_t gather_emit(const GatherArgs& a, void* head, const void* staging, const RebuildCounts& counts, const RebuildOutputs& o, hipStream_t stream);   // o.index: 32-bit entries
 
 } // namespace ommx

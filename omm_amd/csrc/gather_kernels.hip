@@ -18,12 +18,10 @@
 // All counters are integers and every output byte has one writer, so the result does not depend on the order of arrival.
 #include <hip/hip_runtime.h>
 #include <string.h>
-#include <rocprim/rocprim.hpp>
 #include "gather_kernels.h"
 #include "gather_copy.h"
 #include "result_read.h"
 #include "result_words.h"
-#include "bake_host.h"   // pad256
 #include "wave_search.h"
 
 namespace ommx {
@@ -54,7 +52,7 @@ __device__ __forceinline__ bool resolve(const GatherSource* __restrict__ table, 
 {
     if (selection) {
         *k = selection[i].source; *p = selection[i].primitive;
-        return *k < sources && *p < table[*k].indexCount;
+        return *k < sources && *p < table[*k].view.indexCount;
     }
     *k = row_of(sources, i, [table](uint32_t r) { return (uint64_t)table[r].primBase; });
     *p = (uint32_t)(i - table[*k].primBase);   // (i < the sum of indexCount, so p < indexCount of that row)
@@ -70,18 +68,12 @@ __global__ __launch_bounds__(kGaBlock) void gather_mark(const GatherSource* __re
     uint32_t skipped = 0;
     const uint64_t stride = (uint64_t)gridDim.x * kGaBlock;
     for (uint64_t i = (uint64_t)blockIdx.x * kGaBlock + threadIdx.x; i < primitives; i += stride) {
-        uint32_t k = 0u, p = 0u;
-        int32_t e = -5;                                        // (a primitive that names none is skipped like an entry below -4)
-        bool ok = false;
+        uint32_t k, p, skip = 1u;                                  // (a primitive that names none is skipped like an entry below -4)
         if (resolve(table, sources, selection, i, &k, &p)) {
             const GatherSource s = table[k];
-            e = index_entry(s.index, s.indexFormat, p);
-            if (e >= 0 && (uint32_t)e < s.descCount && desc_ok(load_desc(s.descs + e), s.arrayDataSize)) {
-                ok = true;
-                atomicOr(&ref[(uint64_t)s.descBase + (uint32_t)e], 1u);
-            }
+            skip = mark_selected(s.view, p, ref + s.descBase);
         }
-        skipped += e < -4 || (e >= 0 && !ok) ? 1u : 0u;
+        skipped += skip;
     }
     if (skipped) atomicAdd(&s_n[0], skipped);
     counters_end<1>(s_n, &hdr->skipped);
@@ -102,10 +94,10 @@ __global__ __launch_bounds__(kGaBlock) void gather_prepare(const GatherSource* _
             uint32_t w = 0u;
             if (ref[d]) {
                 const GatherSource s = table[row_of(sources, d, [table](uint32_t r) { return (uint64_t)table[r].descBase; })];
-                const ommCpuOpacityMicromapDesc desc = load_desc(s.descs + (d - s.descBase));   // (marked: it passed the bounds rule)
+                const ommCpuOpacityMicromapDesc desc = load_desc(s.view.descs + (d - s.descBase));   // (marked: it passed the bounds rule)
                 bytes = block_bytes(desc.subdivisionLevel, desc.format);
                 n = bytes > kGaUnitBytes ? bytes / kGaUnitBytes : 1ull;
-                srcAddr[d] = (unsigned long long)(uintptr_t)(s.arrayData + desc.offset);
+                srcAddr[d] = (unsigned long long)(uintptr_t)(s.view.arrayData + desc.offset);
                 bytes = (bytes + kRebuildSlotAlign - 1u) & ~(unsigned long long)(kRebuildSlotAlign - 1u);
                 digest[d] = 0ull; umask[d] = 0xFu;
                 w = item_word(desc.subdivisionLevel, desc.format);
@@ -185,82 +177,45 @@ __global__ __launch_bounds__(kGaBlock) void gather_index(const GatherSource* __r
         uint32_t k, p;
         if (resolve(table, sources, selection, i, &k, &p)) {
             const GatherSource s = table[k];
-            const int32_t e = index_entry(s.index, s.indexFormat, p);
-            uint32_t w;
-            if (e < 0) v = e >= -4 ? e : -4;
-            else if ((uint32_t)e < s.descCount && (w = item[(uint64_t)s.descBase + (uint32_t)e]) != 0u) {   // (marked: it passed the bounds rule)
-                const uint64_t d = (uint64_t)s.descBase + (uint32_t)e;
-                v = tail.special[d];
-                if (v == 0) {
-                    v = (int32_t)tail.newIndex[tail.rep[d]];
-                    atomicAdd(&s_n[2u * item_level(w) + item_bits(w) - 1u], 1u);
-                }
-            }
+            v = index_back(s.view, p, item, s.descBase, tail, s_n);
         }
         outIndex[i] = v;
     }
     counters_end<kRebuildHist>(s_n, tail.indexHist);
 }
 
-struct GatherLayout { size_t header, ref, table, item, slot, units, srcAddr, digest, umask, temp, tail, bytes; size_t tempBytes; };
-GatherLayout gather_layout(const GatherArgs& a)
+// the call's scratch: the header and the marks behind it (ONE memset clears both), the source table, the blocks' addresses, the arrays of the tail
+struct GatherScratch { GatherHeader* hdr; uint32_t* ref; GatherSource* table; unsigned long long* srcAddr; TailArrays t; size_t bytes; };
+GatherScratch gather_scratch(const GatherArgs& a, void* base)
 {
-    GatherLayout L; size_t o = 0;
-    const size_t D = a.descTotal;
-    const auto take = [&o](size_t bytes) { const size_t at = o; o += pad256(bytes); return at; };
-    L.header = take(sizeof(GatherHeader));
-    L.ref = take(4 * D); L.table = take(sizeof(GatherSource) * (size_t)a.sourceCount); L.item = take(4 * D);
-    L.slot = take(8 * (D + 1)); L.units = take(8 * (D + 1)); L.srcAddr = take(8 * D);
-    L.digest = take(8 * D); L.umask = take(4 * D);
-    L.tempBytes = 0;
-    if (D) (void)rocprim::exclusive_scan(nullptr, L.tempBytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, 0ull, D + 1, rocprim::plus<unsigned long long>());
-    L.temp = take(L.tempBytes);
-    L.tail = take(rebuild_bytes(a.descTotal, a.flags));
-    L.bytes = o;
-    return L;
-}
-RebuildInputs tail_inputs(const GatherArgs& a, const GatherLayout& L, uint8_t* base, const void* staging)
-{
-    RebuildInputs in;
-    in.items = a.descTotal; in.flags = a.flags;   // (ommxGatherFlags have the values of ommxCoarsenFlags)
-    in.item = (const uint32_t*)(base + L.item); in.slotStart = (const unsigned long long*)(base + L.slot);
-    in.digest = (const unsigned long long*)(base + L.digest); in.umask = (const uint32_t*)(base + L.umask);
-    in.staging = (const uint8_t*)staging; in.scratch = base + L.tail;
-    return in;
+    GatherScratch s; CarveCursor c{ (uintptr_t)base };
+    s.hdr = c.take<GatherHeader>(1); s.ref = c.take<uint32_t>(a.descTotal);
+    s.table = c.take<GatherSource>(a.sourceCount); s.srcAddr = c.take<unsigned long long>(a.descTotal);
+    s.t = rebuild_arrays(c, a.descTotal, a.flags);   // (ommxGatherFlags have the values of ommxCoarsenFlags)
+    s.bytes = (size_t)(c.at - (uintptr_t)base);
+    return s;
 }
 
 } // namespace
 
-size_t gather_head_bytes(const GatherArgs& a) { return gather_layout(a).bytes; }
+size_t gather_head_bytes(const GatherArgs& a) { return gather_scratch(a, nullptr).bytes; }
 
 hipError_t gather_plan(const GatherArgs& a, void* head, GatherPlan* out, hipStream_t stream)
 {
-    const GatherLayout L = gather_layout(a);
-    uint8_t* base = (uint8_t*)head;
+    const GatherScratch s = gather_scratch(a, head);
     const uint32_t D = a.descTotal, K = a.sourceCount;
-    GatherHeader* hdr = (GatherHeader*)(base + L.header);
-    uint32_t* ref = (uint32_t*)(base + L.ref);
-    const GatherSource* table = (const GatherSource*)(base + L.table);
-    unsigned long long* slot = (unsigned long long*)(base + L.slot);
-    unsigned long long* units = (unsigned long long*)(base + L.units);
-    REBUILD_CHECK(hipMemsetAsync(hdr, 0, L.ref - L.header + 4 * (size_t)D, stream));   // (the header and the marks behind it)
-    REBUILD_CHECK(hipMemcpyAsync(base + L.table, a.sources, sizeof(GatherSource) * (size_t)K, hipMemcpyHostToDevice, stream));
-    gather_mark<<<strided_grid(a.primitiveCount), kGaBlock, 0, stream>>>(table, K, a.selection, a.primitiveCount, ref, hdr);
+    REBUILD_CHECK(hipMemsetAsync(s.hdr, 0, (size_t)((uint8_t*)s.ref - (uint8_t*)s.hdr) + 4 * (size_t)D, stream));   // (the header and the marks behind it)
+    REBUILD_CHECK(hipMemcpyAsync(s.table, a.sources, sizeof(GatherSource) * (size_t)K, hipMemcpyHostToDevice, stream));
+    gather_mark<<<strided_grid(a.primitiveCount), kGaBlock, 0, stream>>>(s.table, K, a.selection, a.primitiveCount, s.ref, s.hdr);
     REBUILD_CHECK(hipGetLastError());
     unsigned long long stagingBytes = 0, totalUnits = 0;
     if (D) {
-        gather_prepare<<<per_item_grid((uint64_t)D + 1u), kGaBlock, 0, stream>>>(table, K, D, ref, (uint32_t*)(base + L.item), slot, units, (unsigned long long*)(base + L.srcAddr),
-                                                                                (unsigned long long*)(base + L.digest), (uint32_t*)(base + L.umask), hdr);
+        gather_prepare<<<per_item_grid((uint64_t)D + 1u), kGaBlock, 0, stream>>>(s.table, K, D, s.ref, s.t.item, s.t.slotStart, s.t.units, s.srcAddr, s.t.digest, s.t.umask, s.hdr);
         REBUILD_CHECK(hipGetLastError());
-        size_t tb = L.tempBytes;   // (in place: every element is read before it is written)
-        REBUILD_CHECK(rocprim::exclusive_scan(base + L.temp, tb, slot, slot, 0ull, (size_t)D + 1, rocprim::plus<unsigned long long>(), stream));
-        tb = L.tempBytes;
-        REBUILD_CHECK(rocprim::exclusive_scan(base + L.temp, tb, units, units, 0ull, (size_t)D + 1, rocprim::plus<unsigned long long>(), stream));
-        REBUILD_CHECK(hipMemcpyAsync(&stagingBytes, slot + D, sizeof stagingBytes, hipMemcpyDeviceToHost, stream));
-        REBUILD_CHECK(hipMemcpyAsync(&totalUnits, units + D, sizeof totalUnits, hipMemcpyDeviceToHost, stream));
+        REBUILD_CHECK(rebuild_scan(s.t, D, &stagingBytes, &totalUnits, stream));
     }
     GatherHeader h;
-    REBUILD_CHECK(hipMemcpyAsync(&h, hdr, sizeof h, hipMemcpyDeviceToHost, stream));
+    REBUILD_CHECK(hipMemcpyAsync(&h, s.hdr, sizeof h, hipMemcpyDeviceToHost, stream));
     REBUILD_CHECK(hipStreamSynchronize(stream));
     out->stagingBytes = stagingBytes; out->units = totalUnits; out->skipped = h.skipped; out->referenced = h.referenced;
     return hipSuccess;
@@ -268,26 +223,21 @@ hipError_t gather_plan(const GatherArgs& a, void* head, GatherPlan* out, hipStre
 
 hipError_t gather_stage(const GatherArgs& a, void* head, void* staging, const GatherPlan& plan, RebuildCounts* out, hipStream_t stream)
 {
-    const GatherLayout L = gather_layout(a);
-    uint8_t* base = (uint8_t*)head;
-    const RebuildInputs in = tail_inputs(a, L, base, staging);
+    const GatherScratch s = gather_scratch(a, head);
     if (plan.units) {
-        gather_units<<<(uint32_t)(plan.units < kRebuildMaxGrid ? plan.units : kRebuildMaxGrid), kGaBlock, 0, stream>>>(a.descTotal, in.item, (const unsigned long long*)(base + L.srcAddr),
-                                                                                                                     (const unsigned long long*)(base + L.units), in.slotStart, (uint8_t*)staging,
-                                                                                                                     (unsigned long long*)(base + L.digest), (uint32_t*)(base + L.umask));
+        gather_units<<<(uint32_t)(plan.units < kRebuildMaxGrid ? plan.units : kRebuildMaxGrid), kGaBlock, 0, stream>>>(a.descTotal, s.t.item, s.srcAddr, s.t.units, s.t.slotStart,
+                                                                                                                     (uint8_t*)staging, s.t.digest, s.t.umask);
         REBUILD_CHECK(hipGetLastError());
     }
-    return rebuild_count(in, out, stream);
+    return rebuild_count(tail_inputs(s.t, a.descTotal, a.flags, staging), out, stream);
 }
 
-hipError_t gather_emit(const GatherArgs& a, void* head, const void* staging, const RebuildCounts& counts, const GatherOutputs& o, hipStream_t stream)
+hipError_t gather_emit(const GatherArgs& a, void* head, const void* staging, const RebuildCounts& counts, const RebuildOutputs& o, hipStream_t stream)
 {
-    const GatherLayout L = gather_layout(a);
-    uint8_t* base = (uint8_t*)head;
-    const RebuildInputs in = tail_inputs(a, L, base, staging);
+    const GatherScratch s = gather_scratch(a, head);
+    const RebuildInputs in = tail_inputs(s.t, a.descTotal, a.flags, staging);
     REBUILD_CHECK(rebuild_emit(in, counts, o.arrayData, o.descs, stream));
-    gather_index<<<strided_grid(a.primitiveCount), kGaBlock, 0, stream>>>((const GatherSource*)(base + L.table), a.sourceCount, a.selection, a.primitiveCount, in.item,
-                                                                          rebuild_tables(in), o.index);
+    gather_index<<<strided_grid(a.primitiveCount), kGaBlock, 0, stream>>>(s.table, a.sourceCount, a.selection, a.primitiveCount, in.item, rebuild_tables(in), (int32_t*)o.index);
     REBUILD_CHECK(hipGetLastError());
     return rebuild_histograms(in, o.hist, stream);
 }

@@ -1324,12 +1324,70 @@ bool usable_device()
     (void)hipGetLastError();
     return false;
 }
+// the baker of such an entry; null: the handle is not a baker's (INVALID_ARGUMENT, with nobody to tell)
+Baker* baker_for_device_results(ommBaker baker) { return baker != 0 && (tag_of(baker) == kCpuBaker || tag_of(baker) == kGpuBaker) ? untag<Baker>(baker) : nullptr; }
+// the sources of ommxCombineMicromaps and ommxGatherMicromaps: the entry's checks, in the documented order (descName: the entry's desc struct, null when unset)
+ommResult check_result_array(const Logger& log, const ommCpuBakeResultDesc* const* results, uint32_t count, const char* descName, bool haveDesc, const char* limitName,
+                             uint32_t limit, bool haveOutput)
+{
+    char buf[160];
+    if (results == nullptr) return log.invalid("[Invalid Arg] - deviceResults was not set");
+    if (!haveDesc) { snprintf(buf, sizeof buf, "[Invalid Arg] - %s was not set", descName); return log.invalid(buf); }
+    if (count == 0 || count > limit) { snprintf(buf, sizeof buf, "[Invalid Arg] - resultCount must be 1..%s (%u)", limitName, limit); return log.invalid(buf); }
+    for (uint32_t k = 0; k < count; ++k)
+        if (results[k] == nullptr) return log.invalid("[Invalid Arg] - an element of deviceResults was not set");
+    if (!haveOutput) return log.invalid("[Invalid Arg] - neither outResult nor outInfo was set");
+    return ommResult_SUCCESS;
+}
+ommResult check_source_formats(const Logger& log, const ommCpuBakeResultDesc* const* results, uint32_t count)
+{
+    for (uint32_t k = 0; k < count; ++k)
+        if (!is_index_format(results[k]->indexFormat)) return log.invalid("[Invalid Arg] - a source's indexFormat is not an index format");
+    return ommResult_SUCCESS;
+}
+ommResult check_source_arrays(const Logger& log, const ommCpuBakeResultDesc* const* results, uint32_t count)
+{
+    for (uint32_t k = 0; k < count; ++k)
+        if (has_null_array(*results[k])) return log.invalid("[Invalid Arg] - a source has a null array with a non-zero count");
+    return ommResult_SUCCESS;
+}
+// One call that derives a new device-resident result: the handle, and the skeleton around the operation's own stages (run).
 struct DerivedResult {
-    Baker& b; hipStream_t stream; const char* noun;   // noun: the new result in a message ("coarsened", "combined", "gathered")
+    Baker& b; hipStream_t stream;
+    const char *noun, *work;                          // in a message: the new result ("coarsened", "combined", "gathered"), the operation ("coarsening", "combine", "gather")
     DeviceBakeResult* res = nullptr;                  // stays null when the caller wants the info only
     uint32_t hist[2 * kRebuildHist];                  // array | index by (level, format - 1): the operation's last stage fills it
-    DerivedResult(Baker& b_, hipStream_t stream_, const char* noun_) : b(b_), stream(stream_), noun(noun_) { memset(hist, 0, sizeof hist); }
-    ommResult failure(const char* format) { char buf[160]; snprintf(buf, sizeof buf, format, noun); return b.log.failure(buf); }
+    DerivedResult(Baker& b_, hipStream_t stream_, const char* noun_, const char* work_) : b(b_), stream(stream_), noun(noun_), work(work_) { memset(hist, 0, sizeof hist); }
+    ommResult failure(const char* format, const char* word) { char buf[160]; snprintf(buf, sizeof buf, format, word); return b.log.failure(buf); }
+    ommResult failure(const char* format) { return failure(format, noun); }
+    // scratch of the operation; false: it could not be had, and no_memory() is the answer
+    bool acquire(PoolBlock& block, size_t bytes) { return block.acquire(b.devPool.get(), bytes); }
+    ommResult no_memory() { return give_up(failure("[Failure] - out of device memory for the %s scratch", work)); }
+    // after a failed launch: the scratch goes back only when nothing can still touch it
+    ommResult failed() { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); return give_up(failure("[Failure] - the %s kernels could not run", work)); }
+    // The skeleton.  stages(): the operation on the baker's device, there is at least one primitive -- it acquires its scratch (acquire / no_memory),
+    // runs its stages up to the counts of the tail (failed) and ends in emit().
+    template <class Stages> ommResult run(ommxDeviceBakeResult* outResult, uint32_t numTris, ommIndexFormat indexFormat, Stages&& stages)
+    {
+        const ommResult made = outResult ? create(numTris, indexFormat) : ommResult_SUCCESS;
+        if (made != ommResult_SUCCESS) return made;
+        if (numTris) {
+            if (!usable_device()) return give_up(b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)"));
+            const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
+            const ommResult done = stages();
+            if (done != ommResult_SUCCESS) return done;
+        }
+        finish(outResult);
+        return ommResult_SUCCESS;
+    }
+    // judges the output's size; with a handle, allocates its arrays and has the operation's last stage fill them
+    template <class Emit> ommResult emit(const RebuildCounts& n, Emit&& fill)
+    {
+        const ommResult sized = allocate(n);
+        if (sized != ommResult_SUCCESS || !res) return sized;
+        RebuildOutputs o; o.arrayData = res->R.arrayData; o.descs = res->R.descs; o.index = res->R.index; o.hist = hist;
+        return fill(o) == hipSuccess ? ommResult_SUCCESS : failed();
+    }
     ommResult create(uint32_t numTris, ommIndexFormat indexFormat)
     {
         res = b.mem.make<DeviceBakeResult>();
@@ -3133,10 +3191,8 @@ ommResult stats_device(Baker& b, const ommCpuBakeResultDesc& r, const float* are
 OMM_MI355X_API ommResult ommxDebugGetStatsDevice(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const float* deviceTriangleAreas,
                                                  const ommxDeviceStatsOutputs* outputs, ommDebugStats* out, uint32_t* outSkippedPrimitives, void* hipStream)
 {
-    if (baker == 0) return ommResult_INVALID_ARGUMENT;
-    if (tag_of(baker) != kCpuBaker && tag_of(baker) != kGpuBaker) return ommResult_INVALID_ARGUMENT;
-    if (deviceResult == nullptr || out == nullptr) return ommResult_INVALID_ARGUMENT;
-    Baker* b = untag<Baker>(baker);
+    Baker* b = baker_for_device_results(baker);
+    if (!b || deviceResult == nullptr || out == nullptr) return ommResult_INVALID_ARGUMENT;
     return guarded(&b->log, [&] { return stats_device(*b, *deviceResult, deviceTriangleAreas, outputs, out, outSkippedPrimitives, (hipStream_t)hipStream); });
 }
 
@@ -3197,9 +3253,8 @@ ommResult extract_geometry(Baker& b, const ommCpuBakeResultDesc& r, const ommxMi
 OMM_MI355X_API ommResult ommxExtractMicroGeometry(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxMicroGeometryDesc* desc,
                                                   const ommxMicroGeometryOutputs* outputs, uint64_t outCounts[4], uint32_t* outSkippedPrimitives, void* hipStream)
 {
-    if (baker == 0) return ommResult_INVALID_ARGUMENT;
-    if (tag_of(baker) != kCpuBaker && tag_of(baker) != kGpuBaker) return ommResult_INVALID_ARGUMENT;
-    Baker* b = untag<Baker>(baker);
+    Baker* b = baker_for_device_results(baker);
+    if (!b) return ommResult_INVALID_ARGUMENT;
     if (deviceResult == nullptr) return b->log.invalid("[Invalid Arg] - deviceResult was not set");
     if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxMicroGeometryDesc was not set");
     if (outCounts == nullptr) return b->log.invalid("[Invalid Arg] - outCounts was not set");
@@ -3217,44 +3272,30 @@ ommResult coarsen_device(Baker& b, const ommCpuBakeResultDesc& r, const ommxCoar
     if (c.reserved[0] || c.reserved[1] || c.reserved[2]) return b.log.invalid("[Invalid Arg] - ommxCoarsenDesc.reserved must be 0");
     if (has_null_array(r)) return b.log.invalid("[Invalid Arg] - deviceResult has a null array with a non-zero count");
     ommxCoarsenInfo info; memset(&info, 0, sizeof info);
-    DerivedResult out(b, stream, "coarsened");
-    const ommResult made = outResult ? out.create(r.indexCount, r.indexFormat) : ommResult_SUCCESS;
-    if (made != ommResult_SUCCESS) return made;
-    if (r.indexCount) {
-        if (!usable_device()) return out.give_up(b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)"));
-        const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
+    DerivedResult out(b, stream, "coarsened", "coarsening");
+    const ommResult done = out.run(outResult, r.indexCount, r.indexFormat, [&] {
         CoarsenArgs a; a.result = r; a.maxLevel = c.maxSubdivisionLevel < kRebuildLevels - 1u ? c.maxSubdivisionLevel : kRebuildLevels - 1u; a.mixedState = c.mixedState; a.flags = c.flags;
-        PoolBlock head(b.devPool.get(), coarsen_head_bytes(a)), staging;
-        if (!head.p) return out.give_up(b.log.failure("[Failure] - out of device memory for the coarsening scratch"));
-        // (after a failed launch the scratch goes back only when nothing can still touch it)
-        const auto failed = [&] { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); return out.give_up(b.log.failure("[Failure] - the coarsening kernels could not run")); };
+        PoolBlock head, staging;
+        if (!out.acquire(head, coarsen_head_bytes(a))) return out.no_memory();
         CoarsenPlan plan;
-        if (coarsen_plan(a, head.p, &plan, stream) != hipSuccess) return failed();
-        if (plan.stagingBytes && !staging.acquire(b.devPool.get(), (size_t)plan.stagingBytes)) return out.give_up(b.log.failure("[Failure] - out of device memory for the coarsening scratch"));
+        if (coarsen_plan(a, head.p, &plan, stream) != hipSuccess) return out.failed();
+        if (plan.stagingBytes && !out.acquire(staging, (size_t)plan.stagingBytes)) return out.no_memory();
         RebuildCounts n;
-        if (coarsen_reduce(a, head.p, staging.p, plan, &n, stream) != hipSuccess) return failed();
-        const ommResult sized = out.allocate(n);
-        if (sized != ommResult_SUCCESS) return sized;
+        if (coarsen_reduce(a, head.p, staging.p, plan, &n, stream) != hipSuccess) return out.failed();
         info.arrayDataSize = n.arrayBytes; info.descArrayCount = n.descCount; info.referencedBlocks = plan.referenced; info.coarsenedBlocks = plan.coarsened;
         info.uniformBlocks = n.uniform; info.duplicateBlocks = n.duplicate; info.skippedPrimitives = plan.skipped;
-        if (out.res) {
-            const DeviceResult& R = out.res->R;
-            CoarsenOutputs o; o.arrayData = R.arrayData; o.descs = R.descs; o.index = R.index; o.hist = out.hist;
-            if (coarsen_emit(a, head.p, staging.p, n, o, stream) != hipSuccess) return failed();
-        }
-    }
-    out.finish(outResult);
-    if (outInfo) *outInfo = info;
-    return ommResult_SUCCESS;
+        return out.emit(n, [&](const RebuildOutputs& o) { return coarsen_emit(a, head.p, staging.p, n, o, stream); });
+    });
+    if (done == ommResult_SUCCESS && outInfo) *outInfo = info;
+    return done;
 }
 }
 
 OMM_MI355X_API ommResult ommxCoarsenMicromap(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxCoarsenDesc* desc,
                                              ommxDeviceBakeResult* outResult, ommxCoarsenInfo* outInfo, void* hipStream)
 {
-    if (baker == 0) return ommResult_INVALID_ARGUMENT;
-    if (tag_of(baker) != kCpuBaker && tag_of(baker) != kGpuBaker) return ommResult_INVALID_ARGUMENT;
-    Baker* b = untag<Baker>(baker);
+    Baker* b = baker_for_device_results(baker);
+    if (!b) return ommResult_INVALID_ARGUMENT;
     if (deviceResult == nullptr) return b->log.invalid("[Invalid Arg] - deviceResult was not set");
     if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxCoarsenDesc was not set");
     if (outResult == nullptr && outInfo == nullptr) return b->log.invalid("[Invalid Arg] - neither outResult nor outInfo was set");
@@ -3272,72 +3313,49 @@ ommResult combine_device(Baker& b, const ommCpuBakeResultDesc* const* results, u
     if (c.mixedState != 2 && c.mixedState != 3) return b.log.invalid("[Invalid Arg] - ommxCombineDesc.mixedState must be 2 (UnknownTransparent) or 3 (UnknownOpaque)");
     if (c.flags != 0) return b.log.invalid("[Invalid Arg] - ommxCombineDesc.flags must be 0");
     if (c.reserved[0] || c.reserved[1] || c.reserved[2]) return b.log.invalid("[Invalid Arg] - ommxCombineDesc.reserved must be 0");
-    for (uint32_t k = 0; k < count; ++k)
-        if (!is_index_format(results[k]->indexFormat)) return b.log.invalid("[Invalid Arg] - a source's indexFormat is not an index format");
+    ommResult checked = check_source_formats(b.log, results, count);
+    if (checked != ommResult_SUCCESS) return checked;
     const uint32_t indexCount = results[0]->indexCount;
     for (uint32_t k = 1; k < count; ++k)
         if (results[k]->indexCount != indexCount) return b.log.invalid("[Invalid Arg] - the sources' indexCount values differ: they must describe the same primitives");
-    for (uint32_t k = 0; k < count; ++k)
-        if (has_null_array(*results[k])) return b.log.invalid("[Invalid Arg] - a source has a null array with a non-zero count");
+    checked = check_source_arrays(b.log, results, count);
+    if (checked != ommResult_SUCCESS) return checked;
     ommxCombineInfo info; memset(&info, 0, sizeof info);
-    DerivedResult out(b, stream, "combined");
-    const ommResult made = outResult ? out.create(indexCount, ommIndexFormat_UINT_32) : ommResult_SUCCESS;
-    if (made != ommResult_SUCCESS) return made;
-    if (indexCount) {
-        if (!usable_device()) return out.give_up(b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)"));
-        const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
+    DerivedResult out(b, stream, "combined", "combine");
+    const ommResult done = out.run(outResult, indexCount, ommIndexFormat_UINT_32, [&] {
         CombineArgs a; memset(&a, 0, sizeof a);
-        for (uint32_t k = 0; k < count; ++k) {
-            const ommCpuBakeResultDesc& r = *results[k];
-            CombineSource& s = a.source[k];
-            s.arrayData = (const uint8_t*)r.arrayData; s.descs = r.descArray; s.index = r.indexBuffer;
-            s.arrayDataSize = r.arrayDataSize; s.descCount = r.descArrayCount; s.indexFormat = (int32_t)r.indexFormat;
-        }
+        for (uint32_t k = 0; k < count; ++k) a.source[k] = view_of(*results[k]);
         a.sourceCount = count; a.indexCount = indexCount; a.format = c.format; a.mixedState = c.mixedState;
-        const auto no_memory = [&] { return out.give_up(b.log.failure("[Failure] - out of device memory for the combine scratch")); };
-        PoolBlock head(b.devPool.get(), combine_head_bytes(a)), perTuple, staging;
-        if (!head.p) return no_memory();
-        // (after a failed launch the scratch goes back only when nothing can still touch it)
-        const auto failed = [&] { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); return out.give_up(b.log.failure("[Failure] - the combine kernels could not run")); };
+        PoolBlock head, perTuple, staging;
+        if (!out.acquire(head, combine_head_bytes(a))) return out.no_memory();
         CombineTuples t;
-        if (combine_tuples(a, head.p, &t, stream) != hipSuccess) return failed();
+        if (combine_tuples(a, head.p, &t, stream) != hipSuccess) return out.failed();
         info.combinedTuples = t.tuples; info.skippedPrimitives = t.skipped;
         RebuildCounts n; memset(&n, 0, sizeof n);
         if (t.tuples) {
-            if (!perTuple.acquire(b.devPool.get(), combine_tuple_bytes(a, t.tuples))) return no_memory();
+            if (!out.acquire(perTuple, combine_tuple_bytes(a, t.tuples))) return out.no_memory();
             CombinePlan plan;
-            if (combine_plan(a, head.p, perTuple.p, t, &plan, stream) != hipSuccess) return failed();
-            if (!staging.acquire(b.devPool.get(), (size_t)plan.stagingBytes)) return no_memory();
-            if (combine_join(a, perTuple.p, staging.p, t, plan, &n, stream) != hipSuccess) return failed();
+            if (combine_plan(a, head.p, perTuple.p, t, &plan, stream) != hipSuccess) return out.failed();
+            if (!out.acquire(staging, (size_t)plan.stagingBytes)) return out.no_memory();
+            if (combine_join(a, perTuple.p, staging.p, t, plan, &n, stream) != hipSuccess) return out.failed();
             info.refinedTuples = plan.refined; info.uniformBlocks = n.uniform; info.duplicateBlocks = n.duplicate;
         }
-        const ommResult sized = out.allocate(n);
-        if (sized != ommResult_SUCCESS) return sized;
         info.arrayDataSize = n.arrayBytes; info.descArrayCount = n.descCount;
-        if (out.res) {
-            const DeviceResult& R = out.res->R;
-            CombineOutputs o; o.arrayData = R.arrayData; o.descs = R.descs; o.index = (int32_t*)R.index; o.hist = out.hist;
-            if (combine_emit(a, head.p, perTuple.p, staging.p, t, n, o, stream) != hipSuccess) return failed();
-        }
-    }
-    out.finish(outResult);
-    if (outInfo) *outInfo = info;
-    return ommResult_SUCCESS;
+        return out.emit(n, [&](const RebuildOutputs& o) { return combine_emit(a, head.p, perTuple.p, staging.p, t, n, o, stream); });
+    });
+    if (done == ommResult_SUCCESS && outInfo) *outInfo = info;
+    return done;
 }
 }
 
 OMM_MI355X_API ommResult ommxCombineMicromaps(ommBaker baker, const ommCpuBakeResultDesc* const* deviceResults, uint32_t resultCount, const ommxCombineDesc* desc,
                                               ommxDeviceBakeResult* outResult, ommxCombineInfo* outInfo, void* hipStream)
 {
-    if (baker == 0) return ommResult_INVALID_ARGUMENT;
-    if (tag_of(baker) != kCpuBaker && tag_of(baker) != kGpuBaker) return ommResult_INVALID_ARGUMENT;
-    Baker* b = untag<Baker>(baker);
-    if (deviceResults == nullptr) return b->log.invalid("[Invalid Arg] - deviceResults was not set");
-    if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxCombineDesc was not set");
-    if (resultCount == 0 || resultCount > OMMX_COMBINE_MAX_SOURCES) return b->log.invalid("[Invalid Arg] - resultCount must be 1..OMMX_COMBINE_MAX_SOURCES (16)");
-    for (uint32_t k = 0; k < resultCount; ++k)
-        if (deviceResults[k] == nullptr) return b->log.invalid("[Invalid Arg] - an element of deviceResults was not set");
-    if (outResult == nullptr && outInfo == nullptr) return b->log.invalid("[Invalid Arg] - neither outResult nor outInfo was set");
+    Baker* b = baker_for_device_results(baker);
+    if (!b) return ommResult_INVALID_ARGUMENT;
+    const ommResult checked = check_result_array(b->log, deviceResults, resultCount, "ommxCombineDesc", desc != nullptr, "OMMX_COMBINE_MAX_SOURCES", OMMX_COMBINE_MAX_SOURCES,
+                                                 outResult != nullptr || outInfo != nullptr);
+    if (checked != ommResult_SUCCESS) return checked;
     return guarded(&b->log, [&] { return combine_device(*b, deviceResults, resultCount, *desc, outResult, outInfo, (hipStream_t)hipStream); });
 }
 
@@ -3351,69 +3369,48 @@ ommResult gather_device(Baker& b, const ommCpuBakeResultDesc* const* results, ui
     if ((g.flags & ~(uint32_t)(ommxGatherFlags_DisableSpecialIndices | ommxGatherFlags_DisableDuplicateDetection)) != 0) return b.log.invalid("[Invalid Arg] - ommxGatherDesc.flags has unknown bits");
     if (g.reserved != 0) return b.log.invalid("[Invalid Arg] - ommxGatherDesc.reserved must be 0");
     if (g.selection == nullptr && g.selectionCount != 0) return b.log.invalid("[Invalid Arg] - ommxGatherDesc.selection was not set but selectionCount is not 0");
-    for (uint32_t k = 0; k < count; ++k)
-        if (!is_index_format(results[k]->indexFormat)) return b.log.invalid("[Invalid Arg] - a source's indexFormat is not an index format");
-    for (uint32_t k = 0; k < count; ++k)
-        if (has_null_array(*results[k])) return b.log.invalid("[Invalid Arg] - a source has a null array with a non-zero count");
+    ommResult checked = check_source_formats(b.log, results, count);
+    if (checked == ommResult_SUCCESS) checked = check_source_arrays(b.log, results, count);
+    if (checked != ommResult_SUCCESS) return checked;
     std::vector<GatherSource> table(count);
     uint64_t prims = 0, descs = 0;
     for (uint32_t k = 0; k < count; ++k) {
-        const ommCpuBakeResultDesc& r = *results[k];
         GatherSource& s = table[k];
-        s.arrayData = (const uint8_t*)r.arrayData; s.descs = r.descArray; s.index = r.indexBuffer;
-        s.arrayDataSize = r.arrayDataSize; s.descCount = r.descArrayCount; s.indexCount = r.indexCount; s.indexFormat = (int32_t)r.indexFormat;
+        s.view = view_of(*results[k]);
         s.primBase = (uint32_t)prims; s.descBase = (uint32_t)descs;   // (a sum that does not fit is refused below, before the table is used)
-        prims += r.indexCount; descs += r.descArrayCount;
+        prims += s.view.indexCount; descs += s.view.descCount;
     }
     if (g.selection == nullptr && prims > 0xFFFFFFFFull) return b.log.invalid("[Invalid Arg] - the sources' indexCount values add up to more than 2^32 - 1 primitives");
     if (descs > 0xFFFFFFFFull) return b.log.invalid("[Invalid Arg] - the sources' descArrayCount values add up to more than 2^32 - 1 descriptors");
     const uint32_t primitiveCount = g.selection ? g.selectionCount : (uint32_t)prims;
     ommxGatherInfo info; memset(&info, 0, sizeof info);
-    DerivedResult out(b, stream, "gathered");
-    const ommResult made = outResult ? out.create(primitiveCount, ommIndexFormat_UINT_32) : ommResult_SUCCESS;
-    if (made != ommResult_SUCCESS) return made;
-    if (primitiveCount) {
-        if (!usable_device()) return out.give_up(b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)"));
-        const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
+    DerivedResult out(b, stream, "gathered", "gather");
+    const ommResult done = out.run(outResult, primitiveCount, ommIndexFormat_UINT_32, [&] {
         GatherArgs a; a.sources = table.data(); a.sourceCount = count; a.selection = g.selection; a.primitiveCount = primitiveCount; a.descTotal = (uint32_t)descs; a.flags = g.flags;
-        const auto no_memory = [&] { return out.give_up(b.log.failure("[Failure] - out of device memory for the gather scratch")); };
-        PoolBlock head(b.devPool.get(), gather_head_bytes(a)), staging;
-        if (!head.p) return no_memory();
-        // (after a failed launch the scratch goes back only when nothing can still touch it)
-        const auto failed = [&] { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); return out.give_up(b.log.failure("[Failure] - the gather kernels could not run")); };
+        PoolBlock head, staging;
+        if (!out.acquire(head, gather_head_bytes(a))) return out.no_memory();
         GatherPlan plan;
-        if (gather_plan(a, head.p, &plan, stream) != hipSuccess) return failed();
-        if (plan.stagingBytes && !staging.acquire(b.devPool.get(), (size_t)plan.stagingBytes)) return no_memory();
+        if (gather_plan(a, head.p, &plan, stream) != hipSuccess) return out.failed();
+        if (plan.stagingBytes && !out.acquire(staging, (size_t)plan.stagingBytes)) return out.no_memory();
         RebuildCounts n;
-        if (gather_stage(a, head.p, staging.p, plan, &n, stream) != hipSuccess) return failed();
-        const ommResult sized = out.allocate(n);
-        if (sized != ommResult_SUCCESS) return sized;
+        if (gather_stage(a, head.p, staging.p, plan, &n, stream) != hipSuccess) return out.failed();
         info.arrayDataSize = n.arrayBytes; info.descArrayCount = n.descCount; info.primitiveCount = primitiveCount; info.referencedBlocks = plan.referenced;
         info.uniformBlocks = n.uniform; info.duplicateBlocks = n.duplicate; info.skippedPrimitives = plan.skipped;
-        if (out.res) {
-            const DeviceResult& R = out.res->R;
-            GatherOutputs o; o.arrayData = R.arrayData; o.descs = R.descs; o.index = (int32_t*)R.index; o.hist = out.hist;
-            if (gather_emit(a, head.p, staging.p, n, o, stream) != hipSuccess) return failed();
-        }
-    }
-    out.finish(outResult);
-    if (outInfo) *outInfo = info;
-    return ommResult_SUCCESS;
+        return out.emit(n, [&](const RebuildOutputs& o) { return gather_emit(a, head.p, staging.p, n, o, stream); });
+    });
+    if (done == ommResult_SUCCESS && outInfo) *outInfo = info;
+    return done;
 }
 }
 
 OMM_MI355X_API ommResult ommxGatherMicromaps(ommBaker baker, const ommCpuBakeResultDesc* const* deviceResults, uint32_t resultCount, const ommxGatherDesc* desc,
                                              ommxDeviceBakeResult* outResult, ommxGatherInfo* outInfo, void* hipStream)
 {
-    if (baker == 0) return ommResult_INVALID_ARGUMENT;
-    if (tag_of(baker) != kCpuBaker && tag_of(baker) != kGpuBaker) return ommResult_INVALID_ARGUMENT;
-    Baker* b = untag<Baker>(baker);
-    if (deviceResults == nullptr) return b->log.invalid("[Invalid Arg] - deviceResults was not set");
-    if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxGatherDesc was not set");
-    if (resultCount == 0 || resultCount > OMMX_GATHER_MAX_SOURCES) return b->log.invalid("[Invalid Arg] - resultCount must be 1..OMMX_GATHER_MAX_SOURCES (4096)");
-    for (uint32_t k = 0; k < resultCount; ++k)
-        if (deviceResults[k] == nullptr) return b->log.invalid("[Invalid Arg] - an element of deviceResults was not set");
-    if (outResult == nullptr && outInfo == nullptr) return b->log.invalid("[Invalid Arg] - neither outResult nor outInfo was set");
+    Baker* b = baker_for_device_results(baker);
+    if (!b) return ommResult_INVALID_ARGUMENT;
+    const ommResult checked = check_result_array(b->log, deviceResults, resultCount, "ommxGatherDesc", desc != nullptr, "OMMX_GATHER_MAX_SOURCES", OMMX_GATHER_MAX_SOURCES,
+                                                 outResult != nullptr || outInfo != nullptr);
+    if (checked != ommResult_SUCCESS) return checked;
     return guarded(&b->log, [&] { return gather_device(*b, deviceResults, resultCount, *desc, outResult, outInfo, (hipStream_t)hipStream); });
 }
 

@@ -1,6 +1,7 @@
-// rebuild_kernels.hip -- staged blocks with a digest and a uniformity mask become a result: the tail of a bake, for ommxCoarsenMicromap and
-// ommxCombineMicromaps (rebuild_kernels.h says what an item is and what the caller brings).
+// rebuild_kernels.hip -- staged blocks with a digest and a uniformity mask become a result: the tail of a bake, for ommxCoarsenMicromap,
+// ommxCombineMicromaps and ommxGatherMicromaps (rebuild_kernels.h says what an item is and what the caller brings).
 //
+//   (two scans)       for the caller, before it stages: sizes of slots and numbers of work units become offsets (rebuild_scan)
 //   rebuild_classify  one lane per item: uniform blocks become special indices; the others enter the hash table (hash_build.h) under (digest, level, format)
 //   rebuild_resolve   one lane per item: the lowest item under the same key is the candidate; equal level, format and bytes make it the representative
 //   (radix sort)      representatives by size class descending, stable, hence by item ascending within a class
@@ -166,6 +167,24 @@ Place place_of(const RebuildCounts& c)
 } // namespace
 
 size_t rebuild_bytes(uint32_t items, uint32_t flags) { return carve(0, items, flags).bytes; }
+
+TailArrays rebuild_arrays(CarveCursor& c, uint32_t items, uint32_t flags)
+{
+    size_t tempBytes = 0;
+    if (items) (void)rocprim::exclusive_scan(nullptr, tempBytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, 0ull, (size_t)items + 1, rocprim::plus<unsigned long long>());
+    return carve_tail_arrays(c, items, tempBytes, rebuild_bytes(items, flags));
+}
+
+hipError_t rebuild_scan(const TailArrays& t, uint32_t items, unsigned long long* stagingBytes, unsigned long long* totalUnits, hipStream_t stream)
+{
+    size_t tb = t.tempBytes;   // (in place: every element is read before it is written)
+    REBUILD_CHECK(rocprim::exclusive_scan(t.temp, tb, t.slotStart, t.slotStart, 0ull, (size_t)items + 1, rocprim::plus<unsigned long long>(), stream));
+    tb = t.tempBytes;
+    REBUILD_CHECK(rocprim::exclusive_scan(t.temp, tb, t.units, t.units, 0ull, (size_t)items + 1, rocprim::plus<unsigned long long>(), stream));
+    REBUILD_CHECK(hipMemcpyAsync(stagingBytes, t.slotStart + items, sizeof *stagingBytes, hipMemcpyDeviceToHost, stream));
+    if (totalUnits) REBUILD_CHECK(hipMemcpyAsync(totalUnits, t.units + items, sizeof *totalUnits, hipMemcpyDeviceToHost, stream));
+    return hipSuccess;
+}
 
 RebuildTables rebuild_tables(const RebuildInputs& in)
 {

@@ -1,7 +1,9 @@
 // result_read.h -- reading a caller's result on the device: an index entry of any index format, a descriptor, and the bounds rule that decides
-// whether a descriptor may be read through.  Used by the statistics, the micro-geometry, ommxCoarsenMicromap and ommxCombineMicromaps.  The rule is
-// that of ommx_opacity_state in include/omm_mi355x_lookup.h (a public header that stands alone); the bounds tables of the coarsen, combine and
-// statistics GPU tests hold the two statements together.
+// whether a descriptor may be read through -- used by the statistics, the micro-geometry, ommxCoarsenMicromap, ommxCombineMicromaps and
+// ommxGatherMicromaps -- and, for the operations that derive a new result, ResultView (a source as a kernel sees it) and the selection rule: what
+// a primitive of a source selects.  The bounds rule is that of ommx_opacity_state in include/omm_mi355x_lookup.h (a public header that stands alone);
+// the bounds tables of the coarsen, combine, gather and statistics GPU tests hold the two statements together.  The selection rule stands once, here,
+// for the mark and index kernels of the coarsening and the gather; combine_entries states it again, around the descriptor it has to keep.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -41,5 +43,45 @@ __device__ __forceinline__ bool desc_ok(const ommCpuOpacityMicromapDesc d, uint3
     return (uint64_t)d.offset + *bytes <= (uint64_t)arrayDataSize;
 }
 __device__ __forceinline__ bool desc_ok(const ommCpuOpacityMicromapDesc d, uint32_t arrayDataSize) { uint64_t bytes; return desc_ok(d, arrayDataSize, &bytes); }
+
+// A source result as the kernels of a derived result read it: arrays in device memory, indexFormat already checked.
+struct ResultView {
+    const uint8_t* arrayData; const ommCpuOpacityMicromapDesc* descs; const void* index;
+    uint32_t arrayDataSize, descCount, indexCount; int32_t indexFormat;
+};
+__host__ __device__ inline ResultView view_of(const ommCpuBakeResultDesc& r)
+{
+    ResultView v;
+    v.arrayData = (const uint8_t*)r.arrayData; v.descs = r.descArray; v.index = r.indexBuffer;
+    v.arrayDataSize = r.arrayDataSize; v.descCount = r.descArrayCount; v.indexCount = r.indexCount; v.indexFormat = (int32_t)r.indexFormat;
+    return v;
+}
+
+// The selection rule: what primitive p of a source selects.
+//   -1 .. -4   a special entry, which passes through
+//   e >= 0     descriptor e: it is in range and passes the bounds rule
+//   kSkipped   nothing: the primitive is skipped
+// named_entry is the part that needs no descriptor (e >= 0: descriptor e is in range).  Behind the mark pass an operation has one word per descriptor,
+// non-zero for a descriptor that a primitive selected; it stands for the bounds rule there, so that no descriptor is read a second time
+// (index_back in rebuild_kernels.h).
+constexpr int32_t kSkipped = -5;
+__device__ __forceinline__ int32_t named_entry(const ResultView& s, uint64_t p)
+{
+    const int32_t e = index_entry(s.index, s.indexFormat, p);
+    if (e < 0) return e >= -4 ? e : kSkipped;
+    return (uint32_t)e < s.descCount ? e : kSkipped;
+}
+__device__ __forceinline__ int32_t select_entry(const ResultView& s, uint64_t p)
+{
+    const int32_t e = named_entry(s, p);
+    return e >= 0 && !desc_ok(load_desc(s.descs + e), s.arrayDataSize) ? kSkipped : e;
+}
+// the mark pass: the descriptor that p selects is marked in marks[descCount]; -> 1 where p is skipped
+__device__ __forceinline__ uint32_t mark_selected(const ResultView& s, uint64_t p, uint32_t* __restrict__ marks)
+{
+    const int32_t e = select_entry(s, p);
+    if (e >= 0) atomicOr(&marks[e], 1u);
+    return e == kSkipped ? 1u : 0u;
+}
 
 } // namespace ommx

@@ -7,8 +7,9 @@ import numpy as np
 import ommtest as ot
 import lookup_util as lu
 import stats_util as su
+import rebuild_util as ru
+from rebuild_util import NONE, NO_SPECIAL, NO_DEDUP, representatives  # noqa: F401  (the callers' names for them)
 
-NONE, NO_SPECIAL, NO_DEDUP = 0, 1, 2
 INFO_FIELDS = ("arrayDataSize", "descArrayCount", "referencedBlocks", "coarsenedBlocks", "uniformBlocks", "duplicateBlocks", "skippedPrimitives")
 RAW_DESC = np.dtype([("o", "<u4"), ("l", "<u2"), ("f", "<u2")])
 
@@ -76,16 +77,10 @@ def _valid(desc, size):
     return l <= 12 and f in (1, 2) and o + su.block_bytes(l, f) <= size
 
 
-def representatives(merge, order, items):
-    """a merge rule other than "equal level, format and bytes" (tests/rebuild_cases.py): merge([(level, format, bytes)] in item order) answers each
-    item's representative as a position in that list -> {item: representative item}"""
-    return {d: order[int(c)] for d, c in zip(order, merge(items))}
-
-
 def restate_coarsen(array_data, descs, index, index_format, max_level, mixed=3, flags=0, array_data_size=None, unpacked=None, merge=None):
     """What ommxCoarsenMicromap answers, from host copies (array_data uint8, descs (D, 3) rows of (offset, level, format), index signed) -> dict:
     array (uint8), descs (E, 3) int64, index (in the format's dtype), array_hist / index_hist ({(level, format): count}), info ({field: int}).
-    unpacked: a dict that keeps the unpacked states of the source blocks between calls on the same arrays; merge: see representatives()"""
+    unpacked: a dict that keeps the unpacked states of the source blocks between calls on the same arrays; merge: see rebuild_util.representatives()"""
     size = len(array_data) if array_data_size is None else array_data_size
     descs = np.asarray(descs, np.int64).reshape(-1, 3)
     e = np.asarray(index).astype(np.int64)
@@ -117,37 +112,15 @@ def restate_coarsen(array_data, descs, index, index_format, max_level, mixed=3, 
             entry[d] = -(int(out[0]) + 1)
         else:
             blocks[d] = lu.pack(out, f)
-    rep, seen = {}, {}
-    for d in sorted(blocks):
-        key = (target_of[d], blocks[d].tobytes())
-        if not flags & NO_DEDUP and key in seen:
-            rep[d] = seen[key]
-            info["duplicateBlocks"] += 1
-        else:
-            rep[d] = seen[key] = d
-    if merge is not None and not flags & NO_DEDUP:
-        rep = representatives(merge, sorted(blocks), [target_of[d] + (blocks[d],) for d in sorted(blocks)])
-        info["duplicateBlocks"] = sum(d != r for d, r in rep.items())
-    emitted = sorted((d for d in blocks if rep[d] == d), key=lambda d: (-len(blocks[d]), d))
-    place = {d: j for j, d in enumerate(emitted)}
-    out_descs, at = [], 0
-    for d in emitted:
-        out_descs.append((at, target_of[d][0], target_of[d][1]))
-        at += len(blocks[d])
-    array = np.concatenate([blocks[d] for d in emitted]) if emitted else np.zeros(0, np.uint8)
-    array_hist, index_hist = {}, {}
-    for d in emitted:
-        array_hist[target_of[d]] = array_hist.get(target_of[d], 0) + 1
+    tail = ru.restate_tail(target_of, blocks, entry, flags, merge)
     new_entry = np.zeros(D, np.int64)
-    for d in target_of:
-        new_entry[d] = entry[d] if d in entry else place[rep[d]]
+    for d, v in tail["entry"].items():
+        new_entry[d] = v
     out_e[selects] = new_entry[e[selects]]
     uses = np.bincount(e[selects], minlength=D) if D else np.zeros(0, np.int64)
-    for d in blocks:
-        index_hist[target_of[d]] = index_hist.get(target_of[d], 0) + int(uses[d])
-    info["arrayDataSize"], info["descArrayCount"] = len(array), len(emitted)
-    return dict(array=array, descs=np.array(out_descs, np.int64).reshape(-1, 3), index=out_e.astype(su.INDEX_DTYPE[index_format]),
-                array_hist=array_hist, index_hist=index_hist, info=info)
+    info["duplicateBlocks"], info["arrayDataSize"], info["descArrayCount"] = tail["duplicates"], len(tail["array"]), len(tail["emitted"])
+    return dict(array=tail["array"], descs=tail["descs"], index=out_e.astype(su.INDEX_DTYPE[index_format]), array_hist=tail["array_hist"],
+                index_hist=ru.index_histogram(target_of, blocks, uses), info=info)
 
 
 def brute_coarsen(blocks, index, max_level, mixed=3, flags=0):

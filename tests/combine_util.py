@@ -8,6 +8,7 @@ import ommtest as ot
 import lookup_util as lu
 import stats_util as su
 import coarsen_util as cu
+import rebuild_util as ru
 
 MAX_SOURCES = 16
 INFO_FIELDS = ("arrayDataSize", "descArrayCount", "combinedTuples", "refinedTuples", "uniformBlocks", "duplicateBlocks", "skippedPrimitives")
@@ -76,7 +77,7 @@ def restate_combine(sources, fmt, mixed=3, unpacked=None, merge=None):
     """What ommxCombineMicromaps answers.  sources: [(array_data uint8, descs (D, 3) rows of (offset, level, format), index, arrayDataSize or None)] ->
     dict: array (uint8), descs (E, 3) int64, index (int32), array_hist / index_hist ({(level, format): count}), info ({field: int}).
     unpacked: a dict that keeps the unpacked states of source blocks between calls on the same sources (keyed by id of the array); merge: see
-    coarsen_util.representatives()"""
+    rebuild_util.representatives()"""
     K = len(sources)
     T = len(sources[0][2])
     entries = np.stack([np.asarray(s[2]).astype(np.int64) for s in sources], 1) if T else np.zeros((0, K), np.int64)
@@ -106,7 +107,7 @@ def restate_combine(sources, fmt, mixed=3, unpacked=None, merge=None):
     rank = np.empty(len(order), np.int64)
     rank[order] = np.arange(len(order))
     info["combinedTuples"] = len(order)
-    blocks, entry, level_of = {}, {}, {}                     # tuple (by rank) -> output bytes; -> special entry; -> level
+    blocks, entry, kind = {}, {}, {}                         # tuple (by rank) -> output bytes; -> special entry; -> (level, format)
     for t, u in enumerate(order.tolist()):
         tup = tuples[u]
         levels = [int(tables[k][e, 1]) for k, e in enumerate(tup) if e >= 0]
@@ -126,43 +127,21 @@ def restate_combine(sources, fmt, mixed=3, unpacked=None, merge=None):
                     unpacked[key] = states
             rows.append(np.repeat(states, 4 ** (top - l)))
         out = join_states(np.stack(rows), fmt, mixed)
-        level_of[t] = top
+        kind[t] = (top, fmt)
         if (out == out[0]).all():
             info["uniformBlocks"] += 1
             entry[t] = -(int(out[0]) + 1)
         else:
             blocks[t] = lu.pack(out, fmt)
-    rep, seen = {}, {}
-    for t in sorted(blocks):
-        key = (level_of[t], blocks[t].tobytes())
-        if key in seen:
-            rep[t] = seen[key]
-            info["duplicateBlocks"] += 1
-        else:
-            rep[t] = seen[key] = t
-    if merge is not None:
-        rep = cu.representatives(merge, sorted(blocks), [(level_of[t], fmt, blocks[t]) for t in sorted(blocks)])
-        info["duplicateBlocks"] = sum(t != r for t, r in rep.items())
-    emitted = sorted((t for t in blocks if rep[t] == t), key=lambda t: (-len(blocks[t]), t))
-    place = {t: j for j, t in enumerate(emitted)}
-    out_descs, at = [], 0
-    for t in emitted:
-        out_descs.append((at, level_of[t], fmt))
-        at += len(blocks[t])
-    array = np.concatenate([blocks[t] for t in emitted]) if emitted else np.zeros(0, np.uint8)
-    array_hist, index_hist = {}, {}
-    for t in emitted:
-        array_hist[(level_of[t], fmt)] = array_hist.get((level_of[t], fmt), 0) + 1
+    tail = ru.restate_tail(kind, blocks, entry, 0, merge)
+    uses = {}
     if len(order):
-        new_entry = np.array([entry[t] if t in entry else place[rep[t]] for t in range(len(order))], np.int64)
         of_prim = rank[inverse.reshape(-1)]
-        out_e[prims] = new_entry[of_prim]
+        out_e[prims] = np.array([tail["entry"][t] for t in range(len(order))], np.int64)[of_prim]
         uses = np.bincount(of_prim, minlength=len(order))
-        for t in blocks:
-            index_hist[(level_of[t], fmt)] = index_hist.get((level_of[t], fmt), 0) + int(uses[t])
-    info["arrayDataSize"], info["descArrayCount"] = len(array), len(emitted)
-    return dict(array=array, descs=np.array(out_descs, np.int64).reshape(-1, 3), index=out_e.astype(np.int32), array_hist=array_hist, index_hist=index_hist,
-                info=info)
+    info["duplicateBlocks"], info["arrayDataSize"], info["descArrayCount"] = tail["duplicates"], len(tail["array"]), len(tail["emitted"])
+    return dict(array=tail["array"], descs=tail["descs"], index=out_e.astype(np.int32), array_hist=tail["array_hist"],
+                index_hist=ru.index_histogram(kind, blocks, uses), info=info)
 
 
 def brute_combine(sources, fmt, mixed=3):

@@ -9,9 +9,10 @@ import lookup_util as lu
 import stats_util as su
 import coarsen_util as cu
 import combine_util as mu
+import rebuild_util as ru
+from rebuild_util import NONE, NO_SPECIAL, NO_DEDUP  # noqa: F401  (the callers' names for them)
 
 MAX_SOURCES = 4096
-NONE, NO_SPECIAL, NO_DEDUP = 0, 1, 2
 INFO_FIELDS = ("arrayDataSize", "descArrayCount", "primitiveCount", "referencedBlocks", "uniformBlocks", "duplicateBlocks", "skippedPrimitives")
 REF = np.dtype([("source", "<u4"), ("primitive", "<u4")])
 
@@ -56,7 +57,7 @@ def restate_gather(sources, selection=None, flags=0, unpacked=None, merge=None):
     """What ommxGatherMicromaps answers.  sources: [(array_data uint8, descs (D, 3) rows of (offset, level, format), index, arrayDataSize or None)];
     selection: None or (N, 2) rows of (source, primitive) -> dict: array (uint8), descs (E, 3) int64, index (int32), array_hist / index_hist
     ({(level, format): count}), info ({field: int}).  unpacked: a dict that keeps the packed bytes of source blocks between calls on the same sources;
-    merge: see coarsen_util.representatives()"""
+    merge: see rebuild_util.representatives()"""
     K = len(sources)
     counts = np.array([len(s[2]) for s in sources], np.int64)
     tables = [np.asarray(s[1], np.int64).reshape(-1, 3) for s in sources]
@@ -109,40 +110,15 @@ def restate_gather(sources, selection=None, flags=0, unpacked=None, merge=None):
             entry[it] = -(uniform_state + 1)
         else:
             blocks[it] = packed
-    rep, seen = {}, {}
-    for it in sorted(blocks):
-        key = (kind[it], blocks[it].tobytes())
-        if not flags & NO_DEDUP and key in seen:
-            rep[it] = seen[key]
-            info["duplicateBlocks"] += 1
-        else:
-            rep[it] = seen[key] = it
-    if merge is not None and not flags & NO_DEDUP:
-        rep = cu.representatives(merge, sorted(blocks), [kind[it] + (blocks[it],) for it in sorted(blocks)])
-        info["duplicateBlocks"] = sum(it != r for it, r in rep.items())
-    emitted = sorted((it for it in blocks if rep[it] == it), key=lambda it: (-len(blocks[it]), it))
-    place = {it: j for j, it in enumerate(emitted)}
-    out_descs, at = [], 0
-    for it in emitted:
-        out_descs.append((at, kind[it][0], kind[it][1]))
-        at += len(blocks[it])
-    array = np.concatenate([blocks[it] for it in emitted]) if emitted else np.zeros(0, np.uint8)
-    array_hist, index_hist = {}, {}
-    for it in emitted:
-        array_hist[kind[it]] = array_hist.get(kind[it], 0) + 1
-    chosen = item_of >= 0
+    tail = ru.restate_tail(kind, blocks, entry, flags, merge)
+    chosen, items, uses = item_of >= 0, sorted(kind), {}
     if chosen.any():
-        items = sorted(kind)
-        new_entry = np.array([entry[it] if it in entry else place[rep[it]] for it in items], np.int64)
         at_item = np.searchsorted(items, item_of[chosen])
-        out_e[chosen] = new_entry[at_item]
-        uses = np.bincount(at_item, minlength=len(items))
-        for j, it in enumerate(items):
-            if it in blocks:
-                index_hist[kind[it]] = index_hist.get(kind[it], 0) + int(uses[j])
-    info["arrayDataSize"], info["descArrayCount"] = len(array), len(emitted)
-    return dict(array=array, descs=np.array(out_descs, np.int64).reshape(-1, 3), index=out_e.astype(np.int32), array_hist=array_hist, index_hist=index_hist,
-                info=info)
+        out_e[chosen] = np.array([tail["entry"][it] for it in items], np.int64)[at_item]
+        uses = dict(zip(items, np.bincount(at_item, minlength=len(items))))
+    info["duplicateBlocks"], info["arrayDataSize"], info["descArrayCount"] = tail["duplicates"], len(tail["array"]), len(tail["emitted"])
+    return dict(array=tail["array"], descs=tail["descs"], index=out_e.astype(np.int32), array_hist=tail["array_hist"],
+                index_hist=ru.index_histogram(kind, blocks, uses), info=info)
 
 
 def _uniform_state(packed, level, bits):
