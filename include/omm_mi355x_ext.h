@@ -355,8 +355,8 @@ OMM_MI355X_API ommResult ommxExpandMicroNodes(const ommxMicroNode* nodes, uint64
 
 /* ---- a coarser micromap from a finer one: cap a device-resident result's subdivision level ----
  * ommxCoarsenMicromap    makes a new device-resident result in which no block is finer than maxSubdivisionLevel, from the bits of the source alone:
- *                        no texture, no UVs, no classification.  For a lower level of detail (distant instances, a cheaper BLAS) or a memory budget
- *                        tighter than the bake's answer.  `deviceResult` is a HOST struct over DEVICE arrays as for ommxLookupOpacity /
+ *                        no texture, no UVs, no classification.  For a lower level of detail (distant instances, a cheaper BLAS); for a memory
+ *                        budget see ommxFitMicromap, which caps block by block.  `deviceResult` is a HOST struct over DEVICE arrays as for ommxLookupOpacity /
  *                        ommxDebugGetStatsDevice / ommxExtractMicroGeometry; the source is not modified.  The output is an ordinary
  *                        ommxDeviceBakeResult: ommxGetDeviceBakeResultDesc reads it, the lookup, resolve, stats and geometry entries accept it,
  *                        ommxDestroyDeviceBakeResult destroys it; its memory comes from the baker's device pool.  It carries no triangle areas
@@ -396,8 +396,8 @@ OMM_MI355X_API ommResult ommxExpandMicroNodes(const ommxMicroNode* nodes, uint64
  *   histograms           descArrayHistogram counts output descriptors per (level, format); indexHistogram counts primitives with an entry >= 0
  *                        per (level, format) of the selected block.  Zero counts are omitted.
  *   info                 see ommxCoarsenInfo.  With default flags referencedBlocks == descArrayCount + uniformBlocks + duplicateBlocks.  With
- *                        outResult == NULL the same numbers are computed and no output arrays are allocated or written -- for a budget search:
- *                        ask for a few levels, then build one.
+ *                        outResult == NULL the same numbers are computed and no output arrays are allocated or written -- to learn the size of
+ *                        a level before building it.
  *   stream, memory       the kernels run on `hipStream` (null = the null stream), which the call synchronises before it returns.  Scratch comes
  *                        from the baker's device pool and is back there when the call returns.  *outResult is written on SUCCESS only.
  *   result codes         judged before the device is touched, each INVALID_ARGUMENT with a log line of its own: a null baker, deviceResult or
@@ -427,6 +427,95 @@ typedef struct ommxCoarsenInfo {
 } ommxCoarsenInfo;
 OMM_MI355X_API ommResult ommxCoarsenMicromap(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxCoarsenDesc* desc,
                                              ommxDeviceBakeResult* outResult /* NULL: info only */, ommxCoarsenInfo* outInfo /* or NULL */, void* hipStream);
+
+/* ---- a micromap under a byte budget: per-block levels from what every block would keep ----
+ * Three entries, each usable on its own; ommxFitMicromap is the first followed by a plan on the host followed by the second.  All take `deviceResult`
+ * as ommxCoarsenMicromap does (a HOST struct over DEVICE arrays, not modified), select blocks by its "source blocks" rule, run their kernels on
+ * `hipStream` (null = the null stream), which the call synchronises before it returns, and take their scratch from the baker's device pool.  The
+ * outputs are pure functions of the inputs: every counter is an integer, no float is ever summed, two calls return the same bytes.  This is NOT the
+ * bake's maxArrayDataSize (ommCpuBakeInputDesc), whose serial host algorithm and answers stay as they are; the rule here is its own, stated below.
+ *
+ * ommxProfileMicromapLevels   for every source descriptor d and every level t, what block d would keep if it were coarsened to level t.
+ *   rows of zeros        for a descriptor d that no primitive selects, or that fails the bounds rule, every output row of d is zero.
+ *   counts               for a selected block of level L and t in 0..L: knownCounts[d][t] is the number of level-t micro-triangles j whose covered
+ *                        source states [j * 4^(L-t), (j+1) * 4^(L-t)) are all known (state < 2) and all of one side; knownOpaqueCounts[d][t] counts
+ *                        those whose side is 1.  For t > L both are 0.  The states of a 2-state block are 0 or 1, so a group of such a block is known
+ *                        exactly when it is not mixed.  Unused bits of a one-byte block are ignored.  The counts do not depend on a mixedState: a mixed
+ *                        group is unknown under either value.  At t = L the two numbers are T + O and O of ommxDebugGetStatsDevice's stateCounts[d].
+ *                        knownCounts[d][t-1] * 4 <= knownCounts[d][t]: a known parent has four known children.
+ *   referenceCounts      referenceCounts[d] is the number of primitives that select d.
+ *   weights              devicePrimitiveWeights: indexCount floats in DEVICE memory (ommxGetDeviceBakeResultTriangleAreas, or the caller's world-space
+ *                        areas), read on `hipStream`.  A weight that is not a finite positive number counts as 0.  M is the largest weight left, over
+ *                        all indexCount primitives.  M == 0: every q_i = 0 and weightExponent = 0.  Otherwise M = m * 2^e with 1 <= m < 2,
+ *                        weightExponent = e and q_i = (uint64_t)floor((double)w_i * 2^(31-e)), exact in fp64 and below 2^32.  blockWeights[d] is the
+ *                        sum of q_i over the primitives that select d, in 64-bit integers; it cannot overflow.  With devicePrimitiveWeights == NULL
+ *                        every q_i = 1 and weightExponent = 0, so blockWeights[d] == referenceCounts[d].
+ *   outputs              DEVICE memory, every member optional; blockWeights 8-byte aligned, the others 4-byte aligned.
+ *   result codes         judged before the device is touched, each INVALID_ARGUMENT with a log line of its own: a null baker or deviceResult, outputs
+ *                        and outInfo both null, a baker of unknown type, an unknown indexFormat, null arrays with non-zero counts.  indexCount == 0 ->
+ *                        SUCCESS without a launch: the info is all zeros and no output array is written.  Without a usable device, or when device
+ *                        memory runs out -> FAILURE with a log line.
+ *
+ * ommxCoarsenMicromapLevels   ommxCoarsenMicromap with a cap per source block: everything is as there, except that block d of level L_d becomes a block
+ *                        of level T_d = min(L_d, desc->maxSubdivisionLevel, deviceBlockLevels[d]).  deviceBlockLevels: descArrayCount bytes in DEVICE
+ *                        memory, read on `hipStream`; a value of 12 or more means no limit from that source; entries of descriptors that are unselected
+ *                        or invalid have no effect.  With deviceBlockLevels == NULL the output is byte for byte ommxCoarsenMicromap's.
+ *                        coarsenedBlocks counts the blocks with L_d > T_d.
+ *
+ * ommxFitMicromap        a new device-resident result of at most desc->maxArrayDataSize bytes of arrayData, every block at the level the plan gives it.
+ *   the plan             every selected block d has its level L_d, its format's bits b_d (1 or 2), its weight W_d = blockWeights[d] and its two profile
+ *                        rows, all as ommxProfileMicromapLevels gives them for devicePrimitiveWeights.
+ *                          size(d,t)  = 0 if special indices are enabled and either t == 0, or knownCounts[d][t] == 4^t with knownOpaqueCounts[d][t]
+ *                                       equal to 0 or 4^t (the block is promoted); otherwise max(1, 4^t * b_d / 8).
+ *                          value(d,t) = W_d * knownCounts[d][t] * 4^(12-t), an unsigned 128-bit integer: weight times known share.
+ *                        Start: t_d = min(L_d, maxSubdivisionLevel), total = sum of size(d, t_d) = unfittedArrayDataSize.  A block is a candidate while
+ *                        t_d > 0 and ds = size(d, t_d) - size(d, t_d - 1) > 0; its loss is dv = value(d, t_d) - value(d, t_d - 1) >= 0.  While
+ *                        total > maxArrayDataSize: the candidate with the smallest dv / ds -- compared by cross-multiplication in 128 bits (every product
+ *                        is below 2^114), ties to the lower descriptor index -- goes down one level (t_d -= 1, total -= ds, steps += 1).  The sequence of
+ *                        steps does not depend on the budget, which only says where it stops: the levels are monotone in the budget.  Duplicates and
+ *                        blocks uniform in an unknown state are not anticipated, so the output's arrayDataSize can only come out at or below
+ *                        plannedArrayDataSize.  The plan runs on the host, on 116 bytes per source descriptor read back from the profile.
+ *   infeasible           no candidate left and total still above the budget (possible only with DisableSpecialIndices): FAILURE with a log line;
+ *                        nothing is written, *outResult included.
+ *   the output           byte for byte ommxCoarsenMicromapLevels(source, the plan's levels, { 12, mixedState, flags }).  outDeviceBlockLevels[d]
+ *                        (DEVICE memory, descArrayCount bytes) is the level of block d, or 0xFF for a descriptor that is unselected or invalid.
+ *   result codes         as ommxCoarsenMicromap, with ommxFitDesc in the place of ommxCoarsenDesc; refused only when outDeviceBlockLevels, outResult
+ *                        and outInfo are all null.  indexCount == 0 -> SUCCESS without a launch: the info is all zeros, *outResult is an empty result,
+ *                        outDeviceBlockLevels is not written. */
+#define OMMX_PROFILE_LEVELS 13
+typedef struct ommxLevelProfileOutputs {   /* DEVICE memory, every member optional */
+    uint32_t* knownCounts;        /* [descArrayCount][OMMX_PROFILE_LEVELS] */
+    uint32_t* knownOpaqueCounts;  /* [descArrayCount][OMMX_PROFILE_LEVELS] */
+    uint32_t* referenceCounts;    /* [descArrayCount] */
+    uint64_t* blockWeights;       /* [descArrayCount] */
+} ommxLevelProfileOutputs;
+typedef struct ommxLevelProfileInfo {
+    uint32_t referencedBlocks;     /* valid source descriptors that at least one primitive selects */
+    uint32_t skippedPrimitives;
+    int32_t  weightExponent;       /* e of "weights" */
+    uint32_t reserved;             /* 0 */
+} ommxLevelProfileInfo;
+OMM_MI355X_API ommResult ommxProfileMicromapLevels(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const float* devicePrimitiveWeights /* indexCount floats or NULL */,
+                                                   const ommxLevelProfileOutputs* outputs /* or NULL */, ommxLevelProfileInfo* outInfo /* or NULL */, void* hipStream);
+OMM_MI355X_API ommResult ommxCoarsenMicromapLevels(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const uint8_t* deviceBlockLevels /* [descArrayCount] or NULL */,
+                                                   const ommxCoarsenDesc* desc, ommxDeviceBakeResult* outResult /* NULL: info only */, ommxCoarsenInfo* outInfo /* or NULL */,
+                                                   void* hipStream);
+typedef struct ommxFitDesc {
+    uint64_t     maxArrayDataSize;         /* the output's arrayDataSize is at most this */
+    const float* devicePrimitiveWeights;   /* as in ommxProfileMicromapLevels; NULL: every primitive counts 1 */
+    uint32_t     maxSubdivisionLevel;      /* a global cap applied first; >= 12: none */
+    uint8_t      mixedState;               /* 2 or 3, as ommxCoarsenDesc::mixedState */
+    uint8_t      reserved[3];              /* must be 0 */
+    uint32_t     flags;                    /* ommxCoarsenFlags */
+} ommxFitDesc;
+typedef struct ommxFitInfo {
+    ommxCoarsenInfo result;                /* what ommxCoarsenMicromapLevels reports for the chosen levels */
+    uint64_t unfittedArrayDataSize;        /* the plan's size before its first step */
+    uint64_t plannedArrayDataSize;         /* the plan's size after its last step: <= maxArrayDataSize, >= result.arrayDataSize */
+    uint64_t steps;                        /* single-level steps taken */
+} ommxFitInfo;
+OMM_MI355X_API ommResult ommxFitMicromap(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxFitDesc* desc, uint8_t* outDeviceBlockLevels /* [descArrayCount] or NULL */,
+                                         ommxDeviceBakeResult* outResult /* NULL: info only */, ommxFitInfo* outInfo /* or NULL */, void* hipStream);
 
 /* ---- one conservative micromap from several results over the same primitives ----
  * ommxCombineMicromaps   makes a new device-resident result that is safe wherever EVERY source is: a micro-triangle is known only where all sources

@@ -11,13 +11,14 @@ namespace ommx {
 struct CoarsenArgs {
     ommCpuBakeResultDesc result;   // host struct, arrays in device memory; indexFormat already checked
     uint32_t maxLevel;             // clamped to 12
+    const uint8_t* blockLevels;    // [descArrayCount] device memory: a cap per source descriptor (>= 12: none), or null (ommxCoarsenMicromap)
     uint32_t mixedState;           // 2 or 3
     uint32_t flags;                // ommxCoarsenFlags
 };
 struct CoarsenPlan {               // after the index buffer has been read
     uint64_t stagingBytes;         // the arena the reduced blocks are written to before their order is known
     uint32_t skipped, deepBlocks;  // skipped primitives; blocks that need a second reduction pass
-    uint32_t referenced, coarsened;   // selected blocks; those above maxLevel
+    uint32_t referenced, coarsened;   // selected blocks; those above their target
 };
 
 size_t coarsen_head_bytes(const CoarsenArgs& a);

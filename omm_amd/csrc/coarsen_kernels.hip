@@ -1,4 +1,4 @@
-// coarsen_kernels.hip -- ommxCoarsenMicromap (include/omm_mi355x_ext.h has the definition): the blocks of a device-resident result reduced to a
+// coarsen_kernels.hip -- ommxCoarsenMicromap and ommxCoarsenMicromapLevels (include/omm_mi355x_ext.h has the definition): the blocks of a device-resident result reduced to a
 // maximum subdivision level, then the tail of a bake on what is left (rebuild_kernels.hip) -- uniform blocks to special indices, equal blocks
 // merged, blocks ordered by size, descriptors and histograms rebuilt -- and the index buffer.
 //
@@ -38,11 +38,13 @@ struct BlockPlan {
     uint32_t level, bits, target, firstPass;   // firstPass: levels taken off by coarsen_units
     bool deep;                                 // coarsen_deep takes off the rest
 };
-__device__ __forceinline__ BlockPlan plan_block(const ommCpuOpacityMicromapDesc d, uint32_t maxLevel)
+// blockLevels: a cap per source descriptor (ommxCoarsenMicromapLevels), or null
+__device__ __forceinline__ BlockPlan plan_block(const ommCpuOpacityMicromapDesc d, uint32_t maxLevel, const uint8_t* __restrict__ blockLevels, uint64_t index)
 {
     BlockPlan p;
     p.level = d.subdivisionLevel; p.bits = d.format;
     p.target = p.level < maxLevel ? p.level : maxLevel;
+    if (blockLevels) { const uint32_t own = blockLevels[index]; p.target = own < p.target ? own : p.target; }
     const uint32_t k = p.level - p.target;
     const bool several = p.level > kCoUnitLevel;
     p.firstPass = several && k > kCoFirstPassLevels ? kCoFirstPassLevels : k;
@@ -64,7 +66,7 @@ __global__ __launch_bounds__(kCoBlock) void coarsen_mark(ommCpuBakeResultDesc r,
 }
 
 // B. one lane per descriptor and one for the scans' closing element
-__global__ __launch_bounds__(kCoBlock) void coarsen_prepare(ommCpuBakeResultDesc r, uint32_t maxLevel, const uint32_t* __restrict__ ref, uint32_t* __restrict__ item,
+__global__ __launch_bounds__(kCoBlock) void coarsen_prepare(ommCpuBakeResultDesc r, uint32_t maxLevel, const uint8_t* __restrict__ blockLevels, const uint32_t* __restrict__ ref, uint32_t* __restrict__ item,
                                                             unsigned long long* __restrict__ slot, unsigned long long* __restrict__ units,
                                                             unsigned long long* __restrict__ digest, uint32_t* __restrict__ umask, uint32_t* __restrict__ deepList,
                                                             CoarsenHeader* __restrict__ hdr)
@@ -77,7 +79,7 @@ __global__ __launch_bounds__(kCoBlock) void coarsen_prepare(ommCpuBakeResultDesc
         if (d < r.descArrayCount) {
             uint32_t w = 0u;
             if (ref[d]) {
-                const BlockPlan p = plan_block(load_desc(r.descArray + d), maxLevel);
+                const BlockPlan p = plan_block(load_desc(r.descArray + d), maxLevel, blockLevels, d);
                 bytes = block_bytes(p.level - p.firstPass, p.bits);
                 bytes = (bytes + kRebuildSlotAlign - 1u) & ~(unsigned long long)(kRebuildSlotAlign - 1u);
                 n = p.level > kCoUnitLevel ? 1ull << (2u * (p.level - kCoUnitLevel)) : 1ull;
@@ -156,7 +158,7 @@ __device__ __forceinline__ void reduce_unit(const uint8_t* src, uint32_t unitLev
 }
 
 // C. one unit per workgroup and turn
-__global__ __launch_bounds__(kCoBlock) void coarsen_units(ommCpuBakeResultDesc r, uint32_t maxLevel, uint32_t mixedState, const unsigned long long* __restrict__ unitStart,
+__global__ __launch_bounds__(kCoBlock) void coarsen_units(ommCpuBakeResultDesc r, uint32_t maxLevel, const uint8_t* __restrict__ blockLevels, uint32_t mixedState, const unsigned long long* __restrict__ unitStart,
                                                           const unsigned long long* __restrict__ slotStart, uint8_t* __restrict__ staging,
                                                           unsigned long long* __restrict__ digest, uint32_t* __restrict__ umask)
 {
@@ -167,7 +169,7 @@ __global__ __launch_bounds__(kCoBlock) void coarsen_units(ommCpuBakeResultDesc r
     for (unsigned long long u = blockIdx.x; u < total; u += gridDim.x) {
         const uint32_t d = owner_of_segment(unitStart, r.descArrayCount, u);
         const ommCpuOpacityMicromapDesc desc = load_desc(r.descArray + d);   // (has units, so a primitive selects it and it passed the bounds rule)
-        const BlockPlan p = plan_block(desc, maxLevel);
+        const BlockPlan p = plan_block(desc, maxLevel, blockLevels, d);
         const uint64_t unit = u - unitStart[d];
         const uint32_t unitLevel = p.level < kCoUnitLevel ? p.level : kCoUnitLevel;
         const uint8_t* src = (const uint8_t*)r.arrayData + desc.offset + unit * (uint64_t)(kCoUnitFields / 8u * p.bits);
@@ -177,7 +179,7 @@ __global__ __launch_bounds__(kCoBlock) void coarsen_units(ommCpuBakeResultDesc r
 }
 
 // C'. blocks above level 8 that lose more than five levels: the rest, in place in the staging slot (at most 4^7 fields: one unit)
-__global__ __launch_bounds__(kCoBlock) void coarsen_deep(ommCpuBakeResultDesc r, uint32_t maxLevel, uint32_t mixedState, const uint32_t* __restrict__ deepList,
+__global__ __launch_bounds__(kCoBlock) void coarsen_deep(ommCpuBakeResultDesc r, uint32_t maxLevel, const uint8_t* __restrict__ blockLevels, uint32_t mixedState, const uint32_t* __restrict__ deepList,
                                                          const unsigned long long* __restrict__ slotStart, uint8_t* __restrict__ staging,
                                                          unsigned long long* __restrict__ digest, uint32_t* __restrict__ umask)
 {
@@ -185,7 +187,7 @@ __global__ __launch_bounds__(kCoBlock) void coarsen_deep(ommCpuBakeResultDesc r,
     __shared__ uint64_t s_digest[kCoWaves];
     __shared__ uint32_t s_umask[kCoWaves];
     const uint32_t d = deepList[blockIdx.x];
-    const BlockPlan p = plan_block(load_desc(r.descArray + d), maxLevel);
+    const BlockPlan p = plan_block(load_desc(r.descArray + d), maxLevel, blockLevels, d);
     uint8_t* at = staging + slotStart[d];
     const uint32_t level = p.level - p.firstPass;
     reduce_unit(at, level, p.bits, level - p.target, mixedState, at, 0ull, true, digest + d, umask + d, s_planes, s_digest, s_umask);
@@ -230,7 +232,7 @@ hipError_t coarsen_plan(const CoarsenArgs& a, void* head, CoarsenPlan* out, hipS
     REBUILD_CHECK(hipGetLastError());
     unsigned long long stagingBytes = 0;
     if (D) {
-        coarsen_prepare<<<per_item_grid((uint64_t)D + 1u), kCoBlock, 0, stream>>>(r, a.maxLevel, s.ref, s.t.item, s.t.slotStart, s.t.units, s.t.digest, s.t.umask, s.deepList, s.hdr);
+        coarsen_prepare<<<per_item_grid((uint64_t)D + 1u), kCoBlock, 0, stream>>>(r, a.maxLevel, a.blockLevels, s.ref, s.t.item, s.t.slotStart, s.t.units, s.t.digest, s.t.umask, s.deepList, s.hdr);
         REBUILD_CHECK(hipGetLastError());
         REBUILD_CHECK(rebuild_scan(s.t, D, &stagingBytes, nullptr, stream));   // (the units' sum is not read back: coarsen_reduce sizes its grid from a bound)
     }
@@ -249,11 +251,11 @@ hipError_t coarsen_reduce(const CoarsenArgs& a, void* head, void* staging, const
     if (D) {
         // no read-back to size the grid: blocks that do not overlap have at most this many units, and the kernel strides over any more
         const uint64_t bound = (uint64_t)r.arrayDataSize / (kCoUnitFields / 8u) + D;
-        coarsen_units<<<(uint32_t)(bound < kRebuildMaxGrid ? bound : kRebuildMaxGrid), kCoBlock, 0, stream>>>(r, a.maxLevel, a.mixedState, s.t.units, s.t.slotStart, (uint8_t*)staging,
+        coarsen_units<<<(uint32_t)(bound < kRebuildMaxGrid ? bound : kRebuildMaxGrid), kCoBlock, 0, stream>>>(r, a.maxLevel, a.blockLevels, a.mixedState, s.t.units, s.t.slotStart, (uint8_t*)staging,
                                                                                                             s.t.digest, s.t.umask);
         REBUILD_CHECK(hipGetLastError());
         if (plan.deepBlocks) {
-            coarsen_deep<<<plan.deepBlocks, kCoBlock, 0, stream>>>(r, a.maxLevel, a.mixedState, s.deepList, s.t.slotStart, (uint8_t*)staging, s.t.digest, s.t.umask);
+            coarsen_deep<<<plan.deepBlocks, kCoBlock, 0, stream>>>(r, a.maxLevel, a.blockLevels, a.mixedState, s.deepList, s.t.slotStart, (uint8_t*)staging, s.t.digest, s.t.umask);
             REBUILD_CHECK(hipGetLastError());
         }
     }

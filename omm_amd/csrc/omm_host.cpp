@@ -15,6 +15,7 @@
 #include "geometry_kernels.h"
 #include "geometry_cut.h"
 #include "coarsen_kernels.h"
+#include "fit_kernels.h"
 #include "combine_kernels.h"
 #include "gather_kernels.h"
 #include "texture_kernels.h"
@@ -3261,45 +3262,185 @@ OMM_MI355X_API ommResult ommxExtractMicroGeometry(ommBaker baker, const ommCpuBa
     return guarded(&b->log, [&] { return extract_geometry(*b, *deviceResult, *desc, outputs, outCounts, outSkippedPrimitives, (hipStream_t)hipStream); });
 }
 
-// A device-resident result capped at a subdivision level (include/omm_mi355x_ext.h; kernels in coarsen_kernels.hip): read the index buffer, size the
-// staging arena, reduce and compare, judge the output's size on the host, then allocate the new result's arrays and fill them.
+// A device-resident result capped at a subdivision level, for all blocks alike or block by block (include/omm_mi355x_ext.h; kernels in
+// coarsen_kernels.hip): read the index buffer, size the staging arena, reduce and compare, judge the output's size on the host, then allocate the new
+// result's arrays and fill them.
 namespace {
-ommResult coarsen_device(Baker& b, const ommCpuBakeResultDesc& r, const ommxCoarsenDesc& c, ommxDeviceBakeResult* outResult, ommxCoarsenInfo* outInfo, hipStream_t stream)
+// the checks of a coarsening's desc that the three entries share (what: the struct's name)
+ommResult check_coarsen_desc(const Logger& log, const ommCpuBakeResultDesc& r, const char* what, uint8_t mixedState, uint32_t flags, const uint8_t reserved[3])
 {
-    if (!is_index_format(r.indexFormat)) return b.log.invalid("[Invalid Arg] - deviceResult.indexFormat is not an index format");
-    if (c.mixedState != 2 && c.mixedState != 3) return b.log.invalid("[Invalid Arg] - ommxCoarsenDesc.mixedState must be 2 (UnknownTransparent) or 3 (UnknownOpaque)");
-    if ((c.flags & ~(uint32_t)(ommxCoarsenFlags_DisableSpecialIndices | ommxCoarsenFlags_DisableDuplicateDetection)) != 0) return b.log.invalid("[Invalid Arg] - ommxCoarsenDesc.flags has unknown bits");
-    if (c.reserved[0] || c.reserved[1] || c.reserved[2]) return b.log.invalid("[Invalid Arg] - ommxCoarsenDesc.reserved must be 0");
-    if (has_null_array(r)) return b.log.invalid("[Invalid Arg] - deviceResult has a null array with a non-zero count");
+    char buf[160];
+    if (!is_index_format(r.indexFormat)) return log.invalid("[Invalid Arg] - deviceResult.indexFormat is not an index format");
+    if (mixedState != 2 && mixedState != 3) { snprintf(buf, sizeof buf, "[Invalid Arg] - %s.mixedState must be 2 (UnknownTransparent) or 3 (UnknownOpaque)", what); return log.invalid(buf); }
+    if ((flags & ~(uint32_t)(ommxCoarsenFlags_DisableSpecialIndices | ommxCoarsenFlags_DisableDuplicateDetection)) != 0) { snprintf(buf, sizeof buf, "[Invalid Arg] - %s.flags has unknown bits", what); return log.invalid(buf); }
+    if (reserved[0] || reserved[1] || reserved[2]) { snprintf(buf, sizeof buf, "[Invalid Arg] - %s.reserved must be 0", what); return log.invalid(buf); }
+    if (has_null_array(r)) return log.invalid("[Invalid Arg] - deviceResult has a null array with a non-zero count");
+    return ommResult_SUCCESS;
+}
+CoarsenArgs coarsen_args(const ommCpuBakeResultDesc& r, uint32_t maxLevel, const uint8_t* blockLevels, uint32_t mixedState, uint32_t flags)
+{
+    CoarsenArgs a; a.result = r; a.maxLevel = maxLevel < kRebuildLevels - 1u ? maxLevel : kRebuildLevels - 1u; a.blockLevels = blockLevels; a.mixedState = mixedState; a.flags = flags;
+    return a;
+}
+// the stages of a coarsening inside DerivedResult::run
+ommResult coarsen_stages(DerivedResult& out, const CoarsenArgs& a, ommxCoarsenInfo* info)
+{
+    PoolBlock head, staging;
+    if (!out.acquire(head, coarsen_head_bytes(a))) return out.no_memory();
+    CoarsenPlan plan;
+    if (coarsen_plan(a, head.p, &plan, out.stream) != hipSuccess) return out.failed();
+    if (plan.stagingBytes && !out.acquire(staging, (size_t)plan.stagingBytes)) return out.no_memory();
+    RebuildCounts n;
+    if (coarsen_reduce(a, head.p, staging.p, plan, &n, out.stream) != hipSuccess) return out.failed();
+    info->arrayDataSize = n.arrayBytes; info->descArrayCount = n.descCount; info->referencedBlocks = plan.referenced; info->coarsenedBlocks = plan.coarsened;
+    info->uniformBlocks = n.uniform; info->duplicateBlocks = n.duplicate; info->skippedPrimitives = plan.skipped;
+    return out.emit(n, [&](const RebuildOutputs& o) { return coarsen_emit(a, head.p, staging.p, n, o, out.stream); });
+}
+ommResult coarsen_device(Baker& b, const ommCpuBakeResultDesc& r, const uint8_t* blockLevels, const ommxCoarsenDesc& c, ommxDeviceBakeResult* outResult, ommxCoarsenInfo* outInfo,
+                         hipStream_t stream)
+{
+    const ommResult ok = check_coarsen_desc(b.log, r, "ommxCoarsenDesc", c.mixedState, c.flags, c.reserved);
+    if (ok != ommResult_SUCCESS) return ok;
     ommxCoarsenInfo info; memset(&info, 0, sizeof info);
     DerivedResult out(b, stream, "coarsened", "coarsening");
-    const ommResult done = out.run(outResult, r.indexCount, r.indexFormat, [&] {
-        CoarsenArgs a; a.result = r; a.maxLevel = c.maxSubdivisionLevel < kRebuildLevels - 1u ? c.maxSubdivisionLevel : kRebuildLevels - 1u; a.mixedState = c.mixedState; a.flags = c.flags;
-        PoolBlock head, staging;
-        if (!out.acquire(head, coarsen_head_bytes(a))) return out.no_memory();
-        CoarsenPlan plan;
-        if (coarsen_plan(a, head.p, &plan, stream) != hipSuccess) return out.failed();
-        if (plan.stagingBytes && !out.acquire(staging, (size_t)plan.stagingBytes)) return out.no_memory();
-        RebuildCounts n;
-        if (coarsen_reduce(a, head.p, staging.p, plan, &n, stream) != hipSuccess) return out.failed();
-        info.arrayDataSize = n.arrayBytes; info.descArrayCount = n.descCount; info.referencedBlocks = plan.referenced; info.coarsenedBlocks = plan.coarsened;
-        info.uniformBlocks = n.uniform; info.duplicateBlocks = n.duplicate; info.skippedPrimitives = plan.skipped;
-        return out.emit(n, [&](const RebuildOutputs& o) { return coarsen_emit(a, head.p, staging.p, n, o, stream); });
-    });
+    const CoarsenArgs a = coarsen_args(r, c.maxSubdivisionLevel, blockLevels, c.mixedState, c.flags);
+    const ommResult done = out.run(outResult, r.indexCount, r.indexFormat, [&] { return coarsen_stages(out, a, &info); });
     if (done == ommResult_SUCCESS && outInfo) *outInfo = info;
     return done;
 }
-}
-
-OMM_MI355X_API ommResult ommxCoarsenMicromap(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxCoarsenDesc* desc,
-                                             ommxDeviceBakeResult* outResult, ommxCoarsenInfo* outInfo, void* hipStream)
+ommResult coarsen_entry(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const uint8_t* blockLevels, const ommxCoarsenDesc* desc, ommxDeviceBakeResult* outResult,
+                        ommxCoarsenInfo* outInfo, void* hipStream)
 {
     Baker* b = baker_for_device_results(baker);
     if (!b) return ommResult_INVALID_ARGUMENT;
     if (deviceResult == nullptr) return b->log.invalid("[Invalid Arg] - deviceResult was not set");
     if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxCoarsenDesc was not set");
     if (outResult == nullptr && outInfo == nullptr) return b->log.invalid("[Invalid Arg] - neither outResult nor outInfo was set");
-    return guarded(&b->log, [&] { return coarsen_device(*b, *deviceResult, *desc, outResult, outInfo, (hipStream_t)hipStream); });
+    return guarded(&b->log, [&] { return coarsen_device(*b, *deviceResult, blockLevels, *desc, outResult, outInfo, (hipStream_t)hipStream); });
+}
+}
+
+OMM_MI355X_API ommResult ommxCoarsenMicromap(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxCoarsenDesc* desc,
+                                             ommxDeviceBakeResult* outResult, ommxCoarsenInfo* outInfo, void* hipStream)
+{
+    return coarsen_entry(baker, deviceResult, nullptr, desc, outResult, outInfo, hipStream);
+}
+
+OMM_MI355X_API ommResult ommxCoarsenMicromapLevels(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const uint8_t* deviceBlockLevels, const ommxCoarsenDesc* desc,
+                                                   ommxDeviceBakeResult* outResult, ommxCoarsenInfo* outInfo, void* hipStream)
+{
+    return coarsen_entry(baker, deviceResult, deviceBlockLevels, desc, outResult, outInfo, hipStream);
+}
+
+// What every block of a device-resident result would keep at every coarser level, and a result fitted to a byte budget from those rows
+// (include/omm_mi355x_ext.h; kernels in fit_kernels.hip, the planner in fit_plan.h).
+namespace {
+// one profile in flight: its scratch, its arrays
+struct ProfileRun {
+    PoolBlock head, roots; ProfileArgs a; ProfilePlan plan;
+    // false: out of device memory (*launched false) or a failed launch (*launched true)
+    bool run(Baker& b, const ProfileArgs& args, hipStream_t stream, bool* launched)
+    {
+        *launched = false;
+        if (!head.acquire(b.devPool.get(), profile_head_bytes(args))) return false;
+        a = profile_arrays(args, head.p);
+        *launched = true;
+        if (profile_plan(args, head.p, &plan, stream) != hipSuccess) return false;
+        *launched = false;
+        if (plan.units && !roots.acquire(b.devPool.get(), (size_t)plan.units)) return false;
+        *launched = true;
+        return profile_count_blocks(args, head.p, roots.p, plan, stream) == hipSuccess;
+    }
+};
+ProfileArgs profile_args(const ommCpuBakeResultDesc& r, const float* weights, const ommxLevelProfileOutputs* o, bool wantShape)
+{
+    ProfileArgs a; a.result = r; a.weights = weights;
+    a.known = o ? o->knownCounts : nullptr; a.opaque = o ? o->knownOpaqueCounts : nullptr; a.refs = o ? o->referenceCounts : nullptr;
+    a.blockWeights = o ? (unsigned long long*)o->blockWeights : nullptr; a.shape = nullptr; a.wantShape = wantShape;
+    return a;
+}
+ommResult profile_device(Baker& b, const ommCpuBakeResultDesc& r, const float* weights, const ommxLevelProfileOutputs* outputs, ommxLevelProfileInfo* outInfo, hipStream_t stream)
+{
+    if (!is_index_format(r.indexFormat)) return b.log.invalid("[Invalid Arg] - deviceResult.indexFormat is not an index format");
+    if (has_null_array(r)) return b.log.invalid("[Invalid Arg] - deviceResult has a null array with a non-zero count");
+    ommxLevelProfileInfo info; memset(&info, 0, sizeof info);
+    if (r.indexCount) {
+        if (!usable_device()) return b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)");
+        const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
+        ProfileRun p; bool launched;
+        if (!p.run(b, profile_args(r, weights, outputs, false), stream, &launched)) {
+            if (!launched) return b.log.failure("[Failure] - out of device memory for the profile scratch");
+            (void)hipGetLastError(); (void)hipStreamSynchronize(stream);   // (the scratch goes back only when nothing can still touch it)
+            return b.log.failure("[Failure] - the profile kernels could not run");
+        }
+        info.referencedBlocks = p.plan.referenced; info.skippedPrimitives = p.plan.skipped; info.weightExponent = p.plan.weightExponent;
+    }
+    if (outInfo) *outInfo = info;
+    return ommResult_SUCCESS;
+}
+
+ommResult fit_device(Baker& b, const ommCpuBakeResultDesc& r, const ommxFitDesc& f, uint8_t* outLevels, ommxDeviceBakeResult* outResult, ommxFitInfo* outInfo, hipStream_t stream)
+{
+    const ommResult ok = check_coarsen_desc(b.log, r, "ommxFitDesc", f.mixedState, f.flags, f.reserved);
+    if (ok != ommResult_SUCCESS) return ok;
+    ommxFitInfo info; memset(&info, 0, sizeof info);
+    DerivedResult out(b, stream, "fitted", "fit");
+    const ommResult done = out.run(outResult, r.indexCount, r.indexFormat, [&] {
+        const size_t D = r.descArrayCount;
+        PoolBlock levelsBlock;
+        if (!out.acquire(levelsBlock, D ? D : 1)) return out.no_memory();
+        std::vector<uint8_t> levels(D);
+        {
+            // the profile, its rows read back as the planner's table, the plan
+            ProfileRun p; bool launched;
+            if (!p.run(b, profile_args(r, f.devicePrimitiveWeights, nullptr, true), stream, &launched)) return launched ? out.failed() : out.no_memory();
+            std::vector<uint32_t> shape(D), known(D * kFitLevels), opaque(D * kFitLevels); std::vector<uint64_t> weight(D);
+            if (D) {
+                const bool copied = HIP_OK(hipMemcpyAsync(shape.data(), p.a.shape, 4 * D, hipMemcpyDeviceToHost, stream))
+                                 && HIP_OK(hipMemcpyAsync(known.data(), p.a.known, 4 * D * kFitLevels, hipMemcpyDeviceToHost, stream))
+                                 && HIP_OK(hipMemcpyAsync(opaque.data(), p.a.opaque, 4 * D * kFitLevels, hipMemcpyDeviceToHost, stream))
+                                 && HIP_OK(hipMemcpyAsync(weight.data(), p.a.blockWeights, 8 * D, hipMemcpyDeviceToHost, stream))
+                                 && HIP_OK(hipStreamSynchronize(stream));
+                if (!copied) return out.failed();
+            }
+            FitTable T; T.count = (uint32_t)D; T.shape = shape.data(); T.known = known.data(); T.opaque = opaque.data(); T.weight = weight.data();
+            const FitPlan plan = fit_plan(T, f.maxSubdivisionLevel, !(f.flags & ommxCoarsenFlags_DisableSpecialIndices), f.maxArrayDataSize, levels.data());
+            if (!plan.feasible) return out.give_up(b.log.failure("[Failure] - ommxFitDesc.maxArrayDataSize is below what the blocks occupy at their coarsest level (possible only with DisableSpecialIndices); nothing was written"));
+            info.unfittedArrayDataSize = plan.unfitted; info.plannedArrayDataSize = plan.planned; info.steps = plan.steps;
+        }
+        if (D) {
+            const bool copied = HIP_OK(hipMemcpyAsync(levelsBlock.p, levels.data(), D, hipMemcpyHostToDevice, stream))
+                             && (!outLevels || HIP_OK(hipMemcpyAsync(outLevels, levelsBlock.p, D, hipMemcpyDeviceToDevice, stream)));
+            if (!copied) return out.failed();
+        }
+        // (the plan's levels hold the global cap already; the host vector outlives the upload: every stage below ends with the stream idle)
+        const CoarsenArgs a = coarsen_args(r, kRebuildLevels - 1u, D ? (const uint8_t*)levelsBlock.p : nullptr, f.mixedState, f.flags);
+        return coarsen_stages(out, a, &info.result);
+    });
+    if (done == ommResult_SUCCESS && outInfo) *outInfo = info;
+    return done;
+}
+}
+
+OMM_MI355X_API ommResult ommxProfileMicromapLevels(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const float* devicePrimitiveWeights,
+                                                   const ommxLevelProfileOutputs* outputs, ommxLevelProfileInfo* outInfo, void* hipStream)
+{
+    Baker* b = baker_for_device_results(baker);
+    if (!b) return ommResult_INVALID_ARGUMENT;
+    if (deviceResult == nullptr) return b->log.invalid("[Invalid Arg] - deviceResult was not set");
+    if (outputs == nullptr && outInfo == nullptr) return b->log.invalid("[Invalid Arg] - neither outputs nor outInfo was set");
+    return guarded(&b->log, [&] { return profile_device(*b, *deviceResult, devicePrimitiveWeights, outputs, outInfo, (hipStream_t)hipStream); });
+}
+
+OMM_MI355X_API ommResult ommxFitMicromap(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxFitDesc* desc, uint8_t* outDeviceBlockLevels,
+                                         ommxDeviceBakeResult* outResult, ommxFitInfo* outInfo, void* hipStream)
+{
+    Baker* b = baker_for_device_results(baker);
+    if (!b) return ommResult_INVALID_ARGUMENT;
+    if (deviceResult == nullptr) return b->log.invalid("[Invalid Arg] - deviceResult was not set");
+    if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxFitDesc was not set");
+    if (outResult == nullptr && outInfo == nullptr && outDeviceBlockLevels == nullptr) return b->log.invalid("[Invalid Arg] - none of outDeviceBlockLevels, outResult and outInfo was set");
+    return guarded(&b->log, [&] { return fit_device(*b, *deviceResult, *desc, outDeviceBlockLevels, outResult, outInfo, (hipStream_t)hipStream); });
 }
 
 // One conservative result from several device-resident results over the same primitives (include/omm_mi355x_ext.h; kernels in combine_kernels.hip): find
