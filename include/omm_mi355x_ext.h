@@ -663,6 +663,73 @@ OMM_MI355X_API ommResult ommxGatherMicromaps(ommBaker baker, const ommCpuBakeRes
                                              const ommxGatherDesc* desc, ommxDeviceBakeResult* outResult /* NULL: info only */,
                                              ommxGatherInfo* outInfo /* or NULL */, void* hipStream);
 
+/* ---- a micromap for triangles whose vertices were re-ordered ----
+ * ommxReorientMicromap   makes a new device-resident result for the SAME primitives with the three vertices of each triangle in another order.  A
+ *                        micromap is addressed by the barycentrics of a hit, and those follow the order of a triangle's vertices in the index buffer:
+ *                        a vertex-cache optimiser or meshlet builder that rotates (a, b, c) to (b, c, a), a strip-to-list conversion that flips every
+ *                        second triangle, a mirrored instance drawn with flipped winding all need the bits in another order -- a pure permutation of
+ *                        what is already in HBM, where a second bake would need the texture and the UVs.  ommxGatherMicromaps moves whole
+ *                        primitives; this entry re-orders inside them; chained (gather, then re-orient) they follow an index buffer that was
+ *                        both reordered and rotated.  Nothing is downloaded.
+ *   orientation codes    orientation o means: new vertex k is old vertex perm_o[k].
+ *                            0 (0,1,2) identity      1 (1,2,0) rotation      2 (2,0,1) rotation
+ *                            3 (0,2,1) reflection    4 (2,1,0) reflection    5 (1,0,2) reflection  (the winding flips)
+ *                        1 and 2 are inverses of each other; 3, 4 and 5 are their own.  Primitive p has desc->deviceOrientations[p], or
+ *                        desc->orientation when deviceOrientations is NULL.
+ *   the state            all in integers.  Output micro-triangle j' of a block of level L has the discrete barycentrics (iu', iv', iw') of the
+ *                        forward decode in ommx_micro_vertices (omm_mi355x_lookup.h), before its upright / inverted adjustment.  With
+ *                        t' = (iw', iu', iv') and t[perm_o[k]] = t'[k], the source micro-triangle j is the index that the digit loop of
+ *                        ommx_micro_index gives for (iu, iv, iw) = (t[1], t[2], t[0]); output state j' = source state j; level and format are
+ *                        unchanged.  ommx_reorient_index(j', L, o) in omm_mi355x_lookup.h is j.  For hits, with b' = (1-u'-v', u', v') and
+ *                        b[perm_o[k]] = b'[k]:  ommx_opacity_state(out, i, u', v') == ommx_opacity_state(src, i, b[1], b[2]) for every point strictly
+ *                        inside a micro-triangle.  At level 1 the source indices of output indices 0..3 are  o=0: 0 1 2 3   1: 2 1 3 0   2: 3 1 0 2
+ *                        3: 0 1 3 2   4: 3 1 2 0   5: 2 1 0 3.
+ *   selection, skipping  e = index entry p of deviceResult.  A primitive whose orientation byte is above 5 is SKIPPED, whatever its entry.  Otherwise
+ *                        the selection rule of ommxGatherMicromaps: an entry -1..-4 passes through unchanged under every orientation and flag; an
+ *                        entry >= 0 selects descArray[e] by the bounds rule of omm_mi355x_lookup.h; anything else is SKIPPED.  For a skipped primitive
+ *                        nothing is read through a descriptor, its output entry is -4, and it counts once in skippedPrimitives.
+ *   items                every distinct accepted pair (e, o) is one item, its rank (e, o) in lexicographic order: a descriptor used under several
+ *                        orientations yields several blocks.  A block that is symmetric under o equals its other item and merges with it as any
+ *                        duplicate does.
+ *   blocks               may start at any byte offset; no byte outside [offset, offset + size) is read; the unused bits of a one-byte block are
+ *                        ignored on input and zero on output.
+ *   uniform blocks, duplicates, order, offsets, histograms      as in ommxGatherMicromaps, with the rank above.
+ *   index buffer         indexCount entries, always ommIndexFormat_UINT_32 (the output can have up to six times the source's descriptors).
+ *   purity               two calls return the same bytes.  With deviceOrientations == NULL and orientation == 0, arrayData, descArray, both histograms
+ *                        and the index VALUES equal those of ommxCoarsenMicromap with maxSubdivisionLevel = 12 and the same flags.
+ *   outResult            an ordinary ommxDeviceBakeResult from the baker's device pool, accepted by every entry that takes a result, this one
+ *                        included.  It carries no triangle areas: the primitives are unchanged, so the SOURCE's areas
+ *                        (ommxGetDeviceBakeResultTriangleAreas) remain valid weights for it, e.g. for ommxFitMicromap.
+ *   info                 see ommxReorientInfo.  With default flags referencedBlocks == descArrayCount + uniformBlocks + duplicateBlocks.  With
+ *                        outResult == NULL the same numbers are computed and no output arrays are allocated.
+ *   stream, memory       the kernels run on `hipStream` (null = the null stream), which the call synchronises before it returns; the orientations
+ *                        are read there.  Scratch comes from the baker's device pool (with deviceOrientations it is sized for six items per source
+ *                        descriptor) and is back there when the call returns.  *outResult is written on SUCCESS only.
+ *   result codes         judged before the device is touched, in this order, each INVALID_ARGUMENT with a log line of its own: a null baker, a baker
+ *                        of unknown type (these two without a line: there is nobody to tell), null deviceResult, null desc, outResult and outInfo
+ *                        both null, unknown flag bits, non-zero reserved, orientation above 5 with deviceOrientations NULL, an unknown indexFormat,
+ *                        null arrays with non-zero counts, deviceOrientations set and descArrayCount above (2^32 - 1) / 6.  indexCount == 0 ->
+ *                        SUCCESS without a launch: the info is all zeros and *outResult is an empty result that can be destroyed.  Without a usable
+ *                        device, or when device memory runs out -> FAILURE with a log line. */
+typedef struct ommxReorientDesc {
+    const uint8_t* deviceOrientations;  /* DEVICE memory, indexCount bytes, read on hipStream; NULL: `orientation` for every primitive */
+    uint8_t  orientation;               /* used when deviceOrientations is NULL; must be 0..5 (checked on the host) */
+    uint8_t  reserved[3];               /* must be 0 */
+    uint32_t flags;                     /* ommxCoarsenFlags values: DisableSpecialIndices, DisableDuplicateDetection */
+} ommxReorientDesc;
+typedef struct ommxReorientInfo {
+    uint64_t arrayDataSize;      /* of the output */
+    uint32_t descArrayCount;     /* of the output */
+    uint32_t referencedBlocks;   /* distinct accepted (descriptor, orientation) pairs */
+    uint32_t reorientedBlocks;   /* of those: orientation != 0 */
+    uint32_t uniformBlocks;      /* of those: every state equal (promoted to a special index unless disabled) */
+    uint32_t duplicateBlocks;    /* of those: merged into another block */
+    uint32_t skippedPrimitives;
+} ommxReorientInfo;
+OMM_MI355X_API ommResult ommxReorientMicromap(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxReorientDesc* desc,
+                                              ommxDeviceBakeResult* outResult /* NULL: info only */, ommxReorientInfo* outInfo /* or NULL */,
+                                              void* hipStream);
+
 /* ---- an alpha texture from an image that is already in device memory ----
  * ommxCreateTextureDevice  ommCpuCreateTexture for texels that live in HBM: ONE channel of an interleaved (or packed single-channel) image is read where
  *                        it is; nothing is downloaded, restaged or uploaded.  The result is an ordinary ommCpuTexture, byte for byte the texture

@@ -128,6 +128,51 @@ OMMX_LOOKUP_FN void ommx_micro_vertices(uint32_t index, uint32_t level, float uv
     uv[0] = u; uv[1] = v; uv[2] = u + d; uv[3] = v; uv[4] = u; uv[5] = v + d;
 }
 
+/* perm_o[k] of ommxReorientMicromap's orientation codes (omm_mi355x_ext.h), two bits each at bit 6o + 2k: new vertex k is old vertex perm_o[k].
+ *     o = 0 (0,1,2)   1 (1,2,0)   2 (2,0,1)   3 (0,2,1)   4 (2,1,0)   5 (1,0,2) */
+#define OMMX_REORIENT_PERMS 0x846612264ull
+
+/* A triangle's vertices re-ordered by orientation `o`: the micro-triangle of the OLD order that micro-triangle `index` of the NEW order covers,
+ * at `level`.  All in integers:
+ *   1. (iu', iv', iw') = the forward decode of `index` (the discrete barycentrics of ommx_micro_vertices before its upright / inverted adjustment);
+ *   2. t' = (iw', iu', iv'): the weights of new vertices 0, 1, 2;  t[perm_o[k]] = t'[k]: those of the old vertices;
+ *   3. the answer is what the digit loop of ommx_micro_index gives for (iu, iv, iw) = (t[1], t[2], t[0]).
+ * For a hit (u', v') in the new order, with b' = (1-u'-v', u', v') and b[perm_o[k]] = b'[k]:
+ *     ommx_micro_index(b[1], b[2], level) == ommx_reorient_index(ommx_micro_index(u', v', level), level, o)
+ * for every point strictly inside a micro-triangle.  For fixed level and o it is a bijection of 0 .. 4^level - 1, and it is hierarchical: the answer
+ * for 4j + c at level + 1, shifted right by two, is the answer for j at level.  Orientations 1 and 2 undo each other; 3, 4 and 5 undo themselves.
+ *  - levels above 12 are treated as 12 and an index >= 4^level is reduced modulo 4^level, as in ommx_micro_vertices;
+ *  - an orientation above 5 returns `index` as it came. */
+OMMX_LOOKUP_FN uint32_t ommx_reorient_index(uint32_t index, uint32_t level, uint32_t orientation)
+{
+    if (orientation > 5u) return index;
+    if (level > OMMX_LOOKUP_MAX_LEVEL) level = OMMX_LOOKUP_MAX_LEVEL;
+    if (level == 0u) return 0u;
+    index &= (1u << (2u * level)) - 1u;
+    const uint32_t b0 = ommx_even_bits(index), b1 = ommx_even_bits(index >> 1);
+    const uint32_t fx = ommx_prefix_xor(b0), fy = ommx_prefix_xor(b0 & ~b1);
+    const uint32_t t = fy ^ b1, mask = (1u << level) - 1u;
+    /* the weights of the new vertices 0, 1, 2 ... */
+    const uint32_t t0 = ((~fx & ~t) | (b0 & ~t) | (~b0 & fx & t)) & mask;
+    const uint32_t t1 = ((fx & ~t) | (b0 & ~t) | (~b0 & ~fx & t)) & mask;
+    const uint32_t t2 = (fy ^ b0) & mask;
+    /* ... each handed to the old vertex it is (selects, no indexed array: this is device code too) */
+    const uint32_t perm = (uint32_t)(OMMX_REORIENT_PERMS >> (6u * orientation)) & 63u;
+    const uint32_t p0 = perm & 3u, p1 = (perm >> 2) & 3u;
+    const uint32_t iw = p0 == 0u ? t0 : p1 == 0u ? t1 : t2;
+    const uint32_t iu = p0 == 1u ? t0 : p1 == 1u ? t1 : t2;
+    const uint32_t iv = p0 == 2u ? t0 : p1 == 2u ? t1 : t2;
+    uint32_t source = 0u, x = 0u, y = 0u;
+    for (uint32_t i = level; i-- > 0u;) {
+        const uint32_t key = x | (y << 1) | (((iu >> i) & 1u) << 2) | (((iv >> i) & 1u) << 3) | (((iw >> i) & 1u) << 4);
+        const uint32_t digit = (uint32_t)(OMMX_BIRD_DIGIT_TABLE >> (2u * key)) & 3u;
+        source = (source << 2) | digit;
+        x ^= digit & 1u;
+        y ^= digit == 1u ? 1u : 0u;
+    }
+    return source;
+}
+
 /* The state the result stores for triangle `prim` at the hit (u, v): 0..3 (ommOpacityState) or OMMX_OPACITY_INVALID.
  *  - entry e = result->indexBuffer[prim], signed 8-, 16- or 32-bit after result->indexFormat;
  *  - e in -1..-4 is a special index: state -(e + 1);

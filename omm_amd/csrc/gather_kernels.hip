@@ -7,7 +7,7 @@
 //                     index entry in the source's width, the bounds rule; the selected descriptor is marked, a primitive that fails is counted
 //   gather_prepare    one lane per descriptor of the concatenated descriptor arrays: for a marked one its word for the tail (level and format,
 //                     unchanged), the address of its block, the size of its staging slot and its number of work units
-//   gather_units      THE copy: one workgroup per unit of 16 KiB of one block and turn, 16 bytes per lane and step.  The block lies at any byte
+//   gather_units      THE copy (copy_unit in gather_unit.h): one workgroup per unit of 16 KiB of one block and turn, 16 bytes per lane and step.  The block lies at any byte
 //                     address (gather_copy.h): an aligned one is a plain vector copy, any other reads aligned vectors and shifts two neighbours
 //                     into place, with the block's first and last partial vector read byte by byte -- no byte outside the block is read.  The
 //                     writers sum the digest of the words and AND their uniformity masks (result_words.h): one integer atomic each per workgroup.
@@ -19,7 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include "gather_kernels.h"
-#include "gather_copy.h"
+#include "gather_unit.h"
 #include "result_read.h"
 #include "result_words.h"
 #include "wave_search.h"
@@ -29,8 +29,6 @@ namespace {
 
 constexpr uint32_t kGaBlock = kRebuildBlock;
 constexpr uint32_t kGaWaves = kGaBlock / 64;
-constexpr uint32_t kGaUnitBytes = 16384;             // a workgroup's unit: four 16-byte vectors per lane
-constexpr uint32_t kGaUnitVectors = kGaUnitBytes / 16;
 
 struct GatherHeader { uint32_t skipped, referenced; };
 
@@ -96,7 +94,7 @@ __global__ __launch_bounds__(kGaBlock) void gather_prepare(const GatherSource* _
                 const GatherSource s = table[row_of(sources, d, [table](uint32_t r) { return (uint64_t)table[r].descBase; })];
                 const ommCpuOpacityMicromapDesc desc = load_desc(s.view.descs + (d - s.descBase));   // (marked: it passed the bounds rule)
                 bytes = block_bytes(desc.subdivisionLevel, desc.format);
-                n = bytes > kGaUnitBytes ? bytes / kGaUnitBytes : 1ull;
+                n = unit_count(bytes);
                 srcAddr[d] = (unsigned long long)(uintptr_t)(s.view.arrayData + desc.offset);
                 bytes = (bytes + kRebuildSlotAlign - 1u) & ~(unsigned long long)(kRebuildSlotAlign - 1u);
                 digest[d] = 0ull; umask[d] = 0xFu;
@@ -117,49 +115,14 @@ __global__ __launch_bounds__(kGaBlock) void gather_units(uint32_t descTotal, con
 {
     __shared__ uint64_t s_digest[kGaWaves];
     __shared__ uint32_t s_umask[kGaWaves];
-    const uint32_t t = threadIdx.x;
     const unsigned long long total = unitStart[descTotal];
     for (unsigned long long u = blockIdx.x; u < total; u += gridDim.x) {
         const uint32_t d = owner_of_segment(unitStart, descTotal, u);
         const uint32_t w = item[d], level = item_level(w), bits = item_bits(w);
-        const uint64_t bytes = block_bytes(level, bits);
         const uint8_t* block = (const uint8_t*)(uintptr_t)srcAddr[d];
         uint8_t* dst = staging + slotStart[d];
         UnitOut o; o.dst = dst; o.fieldBase = 0ull; o.outFields = 0u; o.bits = bits; o.digest = 0ull; o.umask = 0xFu;
-        if (bytes < 16u) {
-            if (t == 0u) {
-                const uint64_t word = gather_small(block, (uint32_t)bytes, level, bits);
-                if (bytes == 8u) *(uint64_t*)dst = word;
-                else for (uint32_t b = 0; b < (uint32_t)bytes; ++b) dst[b] = (uint8_t)(word >> (8u * b));
-                const uint32_t used = bits << (2u * level);
-                o.digest = word_digest(word, 0u); o.umask = coarsen_word_uniform(word, used < 64u ? used : 64u, bits);
-            }
-        } else {
-            const uint64_t first = (u - unitStart[d]) * kGaUnitVectors;                 // the unit's first vector within the block
-            const uint32_t count = bytes < kGaUnitBytes ? (uint32_t)(bytes / 16u) : kGaUnitVectors;
-            WordsVec* out = (WordsVec*)dst + first;
-            if (gather_shift(block) == 0u) {
-                const WordsVec* in = (const WordsVec*)block + first;
-                #pragma unroll 4
-                for (uint32_t v = t; v < count; v += kGaBlock) {
-                    const WordsVec x = in[v];
-                    out[v] = x;
-                    const uint64_t word = 2u * (first + v);
-                    o.digest += word_digest(x[0], word) + word_digest(x[1], word + 1u);
-                    o.umask &= coarsen_word_uniform(x[0], 64u, bits) & coarsen_word_uniform(x[1], 64u, bits);
-                }
-            } else {
-                #pragma unroll 4
-                for (uint32_t v = t; v < count; v += kGaBlock) {
-                    const GatherWords x = gather_vector(block, bytes, first + v);
-                    WordsVec y; y[0] = x.w0; y[1] = x.w1;
-                    out[v] = y;
-                    const uint64_t word = 2u * (first + v);
-                    o.digest += word_digest(x.w0, word) + word_digest(x.w1, word + 1u);
-                    o.umask &= coarsen_word_uniform(x.w0, 64u, bits) & coarsen_word_uniform(x.w1, 64u, bits);
-                }
-            }
-        }
+        copy_unit<kGaBlock>(block, level, bits, u - unitStart[d], o);
         unit_close<kGaWaves>(o, s_digest, s_umask, digest + d, umask + d);
         __syncthreads();   // (the LDS words are the next unit's too)
     }

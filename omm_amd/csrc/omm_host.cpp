@@ -18,6 +18,7 @@
 #include "fit_kernels.h"
 #include "combine_kernels.h"
 #include "gather_kernels.h"
+#include "reorient_kernels.h"
 #include "texture_kernels.h"
 #include "block_kernels.h"
 #include "bc7_kernels.h"
@@ -1338,6 +1339,17 @@ ommResult check_result_array(const Logger& log, const ommCpuBakeResultDesc* cons
     for (uint32_t k = 0; k < count; ++k)
         if (results[k] == nullptr) return log.invalid("[Invalid Arg] - an element of deviceResults was not set");
     if (!haveOutput) return log.invalid("[Invalid Arg] - neither outResult nor outInfo was set");
+    return ommResult_SUCCESS;
+}
+// the one source of ommxCoarsenMicromap, ommxCoarsenMicromapLevels and ommxReorientMicromap: the entry's first checks, in the documented order; *b <- the baker
+ommResult check_one_result(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const char* descName, bool haveDesc, bool haveOutput, Baker** b)
+{
+    char buf[160];
+    *b = baker_for_device_results(baker);
+    if (!*b) return ommResult_INVALID_ARGUMENT;
+    if (deviceResult == nullptr) return (*b)->log.invalid("[Invalid Arg] - deviceResult was not set");
+    if (!haveDesc) { snprintf(buf, sizeof buf, "[Invalid Arg] - %s was not set", descName); return (*b)->log.invalid(buf); }
+    if (!haveOutput) return (*b)->log.invalid("[Invalid Arg] - neither outResult nor outInfo was set");
     return ommResult_SUCCESS;
 }
 ommResult check_source_formats(const Logger& log, const ommCpuBakeResultDesc* const* results, uint32_t count)
@@ -3311,11 +3323,9 @@ ommResult coarsen_device(Baker& b, const ommCpuBakeResultDesc& r, const uint8_t*
 ommResult coarsen_entry(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const uint8_t* blockLevels, const ommxCoarsenDesc* desc, ommxDeviceBakeResult* outResult,
                         ommxCoarsenInfo* outInfo, void* hipStream)
 {
-    Baker* b = baker_for_device_results(baker);
-    if (!b) return ommResult_INVALID_ARGUMENT;
-    if (deviceResult == nullptr) return b->log.invalid("[Invalid Arg] - deviceResult was not set");
-    if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxCoarsenDesc was not set");
-    if (outResult == nullptr && outInfo == nullptr) return b->log.invalid("[Invalid Arg] - neither outResult nor outInfo was set");
+    Baker* b;
+    const ommResult checked = check_one_result(baker, deviceResult, "ommxCoarsenDesc", desc != nullptr, outResult != nullptr || outInfo != nullptr, &b);
+    if (checked != ommResult_SUCCESS) return checked;
     return guarded(&b->log, [&] { return coarsen_device(*b, *deviceResult, blockLevels, *desc, outResult, outInfo, (hipStream_t)hipStream); });
 }
 }
@@ -3553,6 +3563,47 @@ OMM_MI355X_API ommResult ommxGatherMicromaps(ommBaker baker, const ommCpuBakeRes
                                                  outResult != nullptr || outInfo != nullptr);
     if (checked != ommResult_SUCCESS) return checked;
     return guarded(&b->log, [&] { return gather_device(*b, deviceResults, resultCount, *desc, outResult, outInfo, (hipStream_t)hipStream); });
+}
+
+// A result for the same primitives with their vertices re-ordered (include/omm_mi355x_ext.h; kernels in reorient_kernels.hip): mark the (descriptor,
+// orientation) pairs the primitives reach and size the staging arena, permute and compare, judge the output's size on the host, then allocate the new
+// result's arrays and fill them.
+namespace {
+ommResult reorient_device(Baker& b, const ommCpuBakeResultDesc& r, const ommxReorientDesc& d, ommxDeviceBakeResult* outResult, ommxReorientInfo* outInfo, hipStream_t stream)
+{
+    if ((d.flags & ~(uint32_t)(ommxCoarsenFlags_DisableSpecialIndices | ommxCoarsenFlags_DisableDuplicateDetection)) != 0) return b.log.invalid("[Invalid Arg] - ommxReorientDesc.flags has unknown bits");
+    if (d.reserved[0] || d.reserved[1] || d.reserved[2]) return b.log.invalid("[Invalid Arg] - ommxReorientDesc.reserved must be 0");
+    if (d.deviceOrientations == nullptr && d.orientation > 5) return b.log.invalid("[Invalid Arg] - ommxReorientDesc.orientation must be 0..5 when deviceOrientations is not set");
+    if (!is_index_format(r.indexFormat)) return b.log.invalid("[Invalid Arg] - deviceResult.indexFormat is not an index format");
+    if (has_null_array(r)) return b.log.invalid("[Invalid Arg] - deviceResult has a null array with a non-zero count");
+    if (d.deviceOrientations != nullptr && r.descArrayCount > 0xFFFFFFFFu / 6u) return b.log.invalid("[Invalid Arg] - deviceResult.descArrayCount is above (2^32 - 1) / 6: six items per descriptor do not fit");
+    ommxReorientInfo info; memset(&info, 0, sizeof info);
+    DerivedResult out(b, stream, "re-oriented", "re-orientation");
+    const ommResult done = out.run(outResult, r.indexCount, ommIndexFormat_UINT_32, [&] {
+        ReorientArgs a; a.source = view_of(r); a.orientations = d.deviceOrientations; a.orientation = d.orientation; a.flags = d.flags;
+        PoolBlock head, staging;
+        if (!out.acquire(head, reorient_head_bytes(a))) return out.no_memory();
+        ReorientPlan plan;
+        if (reorient_plan(a, head.p, &plan, stream) != hipSuccess) return out.failed();
+        if (plan.stagingBytes && !out.acquire(staging, (size_t)plan.stagingBytes)) return out.no_memory();
+        RebuildCounts n;
+        if (reorient_stage(a, head.p, staging.p, plan, &n, stream) != hipSuccess) return out.failed();
+        info.arrayDataSize = n.arrayBytes; info.descArrayCount = n.descCount; info.referencedBlocks = plan.referenced; info.reorientedBlocks = plan.reoriented;
+        info.uniformBlocks = n.uniform; info.duplicateBlocks = n.duplicate; info.skippedPrimitives = plan.skipped;
+        return out.emit(n, [&](const RebuildOutputs& o) { return reorient_emit(a, head.p, staging.p, n, o, stream); });
+    });
+    if (done == ommResult_SUCCESS && outInfo) *outInfo = info;
+    return done;
+}
+}
+
+OMM_MI355X_API ommResult ommxReorientMicromap(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxReorientDesc* desc, ommxDeviceBakeResult* outResult,
+                                              ommxReorientInfo* outInfo, void* hipStream)
+{
+    Baker* b;
+    const ommResult checked = check_one_result(baker, deviceResult, "ommxReorientDesc", desc != nullptr, outResult != nullptr || outInfo != nullptr, &b);
+    if (checked != ommResult_SUCCESS) return checked;
+    return guarded(&b->log, [&] { return reorient_device(*b, *deviceResult, *desc, outResult, outInfo, (hipStream_t)hipStream); });
 }
 
 // Any-hit resolution of hits against a device-resident result (include/omm_mi355x_ext.h; kernels in lookup_kernels.hip).  The desc is checked as

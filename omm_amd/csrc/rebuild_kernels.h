@@ -1,8 +1,9 @@
 // rebuild_kernels.h -- the tail of an operation that derives a new device-resident result from staged blocks (rebuild_kernels.hip): uniform blocks
 // become special indices, equal blocks are merged, the others are ordered by size, then descriptors and arrayData are written.  An item is whatever
 // the caller staged a block for: a source descriptor of ommxCoarsenMicromap, a tuple of ommxCombineMicromaps, a (source, descriptor) pair of
-// ommxGatherMicromaps.  The caller stages the blocks, sums their digests and uniformity masks (result_words.h) and writes one word per item, into
-// arrays that are laid out here (rebuild_arrays.h); its index kernel takes each output entry from the tables of the tail (index_back).
+// ommxGatherMicromaps, a (descriptor, orientation) pair of ommxReorientMicromap.  The caller stages the blocks, sums their digests and uniformity
+// masks (result_words.h) and writes one word per item, into arrays that are laid out here (rebuild_arrays.h); its index kernel takes each output
+// entry from the tables of the tail (index_back).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/omm_mi355x_ext.h"
