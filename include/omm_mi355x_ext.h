@@ -730,6 +730,83 @@ OMM_MI355X_API ommResult ommxReorientMicromap(ommBaker baker, const ommCpuBakeRe
                                               ommxDeviceBakeResult* outResult /* NULL: info only */, ommxReorientInfo* outInfo /* or NULL */,
                                               void* hipStream);
 
+/* ---- what two results say about the same primitives: a state-by-state difference ----
+ * ommxCompareMicromaps   reads two device-resident results over the same primitives side by side and counts, per primitive, how many micro-triangles
+ *                        are in state sa in A and in state sb in B: a 4 x 4 confusion matrix, a relation byte and exact totals.  For checking what a
+ *                        derived result promises about its source -- ommxCoarsenMicromap and ommxFitMicromap ("known only where all of it was known"),
+ *                        ommxCombineMicromaps ("safe wherever every source is"), ommxGatherMicromaps ("the same bits"), ommxReorientMicromap (o, then
+ *                        its inverse) -- for "what did I lose, and where" after fitting or rebaking at a lower level, and for the hard question "is
+ *                        there a micro-triangle that A calls opaque and B calls transparent".  Nothing is downloaded and nothing is modified: one
+ *                        streaming pass over bits that are already in device memory.
+ *   sources              deviceResultA and deviceResultB are HOST structs over DEVICE arrays as for ommxCombineMicromaps.  They have the same
+ *                        indexCount; index formats (8, 16 and 32 bits) may differ; A == B is allowed.
+ *   pair of primitive i  (e_a, e_b), the two index entries.  The skip rule of ommxCombineMicromaps applies: if either entry is below -4 or at or
+ *                        beyond descArrayCount, names a level above 12, a format other than 1 or 2, or a block outside arrayDataSize, the primitive is
+ *                        SKIPPED: nothing is read through either descriptor, its relation is OMMX_RELATION_SKIPPED (0x80), its level 0xFF, its
+ *                        confusion zero, and it adds to nothing but skippedPrimitives.
+ *   the level            T is the maximum level over the blocks of the pair.  A special index -1..-4 is the one state -(e + 1) at level 0.
+ *                        Micro-triangle j of level T reads micro-triangle j >> 2(T - L) of a block of level L (the bird curve is hierarchical).  Two
+ *                        special entries give T = 0 and one field.
+ *   the states           states are 0..3; a 2-state block gives 0 or 1.  Under ommxCompareFlags_Force2State every state s of both sides becomes
+ *                        s & 1 (ommx_force_2state) before it is counted: only the diagonal and CONFLICT can then occur.
+ *   blocks               may start at any byte address; no byte outside [offset, offset + size) of a block is read; the unused bits of a one-byte
+ *                        block are ignored.
+ *   confusion            confusion[i][sa][sb] is the number of level-T micro-triangles whose state is sa in A and sb in B.  Its 16 entries sum to
+ *                        4^T exactly.
+ *   relation             the OR of one bit for every non-zero cell off the diagonal: both states below 2 and different: CONFLICT; sa >= 2 > sb:
+ *                        A_WEAKER; sa < 2 <= sb: B_WEAKER; both at or above 2 and different: HINT.  0: the two sides say the same everywhere.
+ *                        "A is safe wherever B is" is exactly (relation & (OMMX_RELATION_CONFLICT | OMMX_RELATION_B_WEAKER)) == 0 for every
+ *                        primitive: wherever A knows a state, B knows the same one, so A claims nothing that B does not.
+ *   totals               totals[sa][sb] is the sum over the primitives that were not skipped of confusion[i][sa][sb] * 4^(12 - T_i): in units of
+ *                        4^-12 of a primitive, so that levels are commensurable.  They are exact 64-bit integers (at most 2^32 * 2^24); the 16
+ *                        totals sum to (indexCount - skippedPrimitives) * 4^12.  No float is summed anywhere.  Every primitive weighs the same:
+ *                        weighting by area is left to the caller, who has the per-primitive matrices for it (and, for a bake's own result, the areas
+ *                        of ommxGetDeviceBakeResultTriangleAreas).
+ *   purity               two calls return the same bytes.  Exchanging A and B transposes every matrix and the totals and swaps the A_WEAKER and
+ *                        B_WEAKER bits and counts.  No answer depends on how pairs are found: the pass streams each distinct pair once and
+ *                        comparedPairs counts them (two pairs whose 64-bit hashes collide are both streamed, the later one once per primitive and
+ *                        counted so; every matrix is still the pair's own).
+ *   outputs              DEVICE memory, every member optional, written for every primitive, skipped ones included.
+ *   stream, memory       the kernels run on `hipStream` (null = the null stream), which the call synchronises before it returns.  Scratch comes
+ *                        from the baker's device pool and is back there when the call returns.  *outInfo is written on SUCCESS only.
+ *   result codes         judged before the device is touched, in this order, each INVALID_ARGUMENT with a log line of its own: a null baker, a baker
+ *                        of unknown type (these two without a line: there is nobody to tell), null deviceResultA, null deviceResultB, null desc,
+ *                        outputs and outInfo both null, unknown flag bits, non-zero reserved, an unknown indexFormat in either source, indexCount
+ *                        values that differ, null arrays with non-zero counts as in ommxCombineMicromaps, a confusion pointer that is not 16-byte
+ *                        aligned.  indexCount == 0 -> SUCCESS without a launch: the info is all zeros with firstConflictPrimitive = 0xFFFFFFFF, and
+ *                        no output is written.  Without a usable device, or when device memory runs out -> FAILURE with a log line. */
+#define OMMX_RELATION_CONFLICT  0x01u  /* some micro-triangle is known in both and the sides differ (T vs O) */
+#define OMMX_RELATION_A_WEAKER  0x02u  /* some micro-triangle is unknown in A (2, 3) and known in B (0, 1) */
+#define OMMX_RELATION_B_WEAKER  0x04u  /* some micro-triangle is known in A and unknown in B */
+#define OMMX_RELATION_HINT      0x08u  /* some micro-triangle is unknown in both with different hints (UT vs UO) */
+#define OMMX_RELATION_SKIPPED   0x80u  /* the primitive was skipped (alone in its byte) */
+typedef enum ommxCompareFlags {
+    ommxCompareFlags_None        = 0,
+    ommxCompareFlags_Force2State = 1
+} ommxCompareFlags;
+typedef struct ommxCompareDesc {
+    uint32_t flags;         /* ommxCompareFlags */
+    uint32_t reserved;      /* must be 0 */
+} ommxCompareDesc;
+typedef struct ommxCompareOutputs {      /* DEVICE memory, every member optional */
+    uint8_t*  relations;    /* [indexCount] */
+    uint8_t*  levels;       /* [indexCount]: T of the primitive's pair; 0xFF for a skipped primitive */
+    uint32_t* confusion;    /* [indexCount][4][4], 16-byte aligned: [stateA][stateB] at level T; zeros for a skipped primitive */
+} ommxCompareOutputs;
+typedef struct ommxCompareInfo {
+    uint64_t totals[4][4];             /* sum over the primitives that were not skipped of confusion[i] * 4^(12 - T_i) */
+    uint32_t identicalPrimitives;      /* relation == 0 */
+    uint32_t conflictPrimitives, aWeakerPrimitives, bWeakerPrimitives, hintPrimitives;   /* primitives with that bit */
+    uint32_t skippedPrimitives;
+    uint32_t comparedPairs;            /* distinct (entryA, entryB) with at least one block, each streamed once */
+    uint32_t refinedPairs;             /* of those: the two blocks differ in level, or one side is a special index */
+    uint32_t firstConflictPrimitive;   /* lowest primitive with CONFLICT; 0xFFFFFFFF when there is none */
+    uint32_t reserved;                 /* 0 */
+} ommxCompareInfo;
+OMM_MI355X_API ommResult ommxCompareMicromaps(ommBaker baker, const ommCpuBakeResultDesc* deviceResultA, const ommCpuBakeResultDesc* deviceResultB,
+                                              const ommxCompareDesc* desc, const ommxCompareOutputs* outputs /* or NULL */,
+                                              ommxCompareInfo* outInfo /* or NULL */, void* hipStream);
+
 /* ---- an alpha texture from an image that is already in device memory ----
  * ommxCreateTextureDevice  ommCpuCreateTexture for texels that live in HBM: ONE channel of an interleaved (or packed single-channel) image is read where
  *                        it is; nothing is downloaded, restaged or uploaded.  The result is an ordinary ommCpuTexture, byte for byte the texture

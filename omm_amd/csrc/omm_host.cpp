@@ -17,6 +17,8 @@
 #include "coarsen_kernels.h"
 #include "fit_kernels.h"
 #include "combine_kernels.h"
+#include "compare_kernels.h"
+#include "compare_count.h"
 #include "gather_kernels.h"
 #include "reorient_kernels.h"
 #include "texture_kernels.h"
@@ -3508,6 +3510,64 @@ OMM_MI355X_API ommResult ommxCombineMicromaps(ommBaker baker, const ommCpuBakeRe
                                                  outResult != nullptr || outInfo != nullptr);
     if (checked != ommResult_SUCCESS) return checked;
     return guarded(&b->log, [&] { return combine_device(*b, deviceResults, resultCount, *desc, outResult, outInfo, (hipStream_t)hipStream); });
+}
+
+// The state-by-state difference of two device-resident results over the same primitives (include/omm_mi355x_ext.h; kernels in compare_kernels.hip): find
+// the distinct pairs of entries, size the per-pair scratch, stream both sides once per pair, then add up on the device and finish the info here.
+namespace {
+ommResult compare_device(Baker& b, const ommCpuBakeResultDesc& ra, const ommCpuBakeResultDesc& rb, const ommxCompareDesc& d, const ommxCompareOutputs* outputs,
+                         ommxCompareInfo* outInfo, hipStream_t stream)
+{
+    if ((d.flags & ~(uint32_t)ommxCompareFlags_Force2State) != 0) return b.log.invalid("[Invalid Arg] - ommxCompareDesc.flags has unknown bits");
+    if (d.reserved != 0) return b.log.invalid("[Invalid Arg] - ommxCompareDesc.reserved must be 0");
+    if (!is_index_format(ra.indexFormat) || !is_index_format(rb.indexFormat)) return b.log.invalid("[Invalid Arg] - a source's indexFormat is not an index format");
+    if (ra.indexCount != rb.indexCount) return b.log.invalid("[Invalid Arg] - the sources' indexCount values differ: they must describe the same primitives");
+    if (has_null_array(ra) || has_null_array(rb)) return b.log.invalid("[Invalid Arg] - a source has a null array with a non-zero count");
+    if (outputs && ((uintptr_t)outputs->confusion & 15u) != 0) return b.log.invalid("[Invalid Arg] - ommxCompareOutputs.confusion is not 16-byte aligned");
+    ommxCompareInfo info; memset(&info, 0, sizeof info);
+    info.firstConflictPrimitive = 0xFFFFFFFFu;
+    if (ra.indexCount != 0) {
+        if (!usable_device()) return b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)");
+        const DeviceScope onBakersDevice(b.device.load());   // (a baker that has no device yet works on the caller's current one)
+        CompareArgs a; memset(&a, 0, sizeof a);
+        a.a = view_of(ra); a.b = view_of(rb); a.indexCount = ra.indexCount; a.force2 = d.flags & (uint32_t)ommxCompareFlags_Force2State;
+        if (outputs) { a.relations = outputs->relations; a.levels = outputs->levels; a.confusion = outputs->confusion; }
+        PoolBlock head, perPair;
+        // after a failed launch: the scratch goes back only when nothing can still touch it
+        const auto failed = [&] { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); return b.log.failure("[Failure] - the compare kernels could not run"); };
+        if (!head.acquire(b.devPool.get(), compare_head_bytes(a))) return b.log.failure("[Failure] - out of device memory for the compare scratch");
+        CombineTuples t;
+        if (compare_pairs(a, head.p, &t, stream) != hipSuccess) return failed();
+        if (t.tuples && !perPair.acquire(b.devPool.get(), compare_pair_bytes(t.tuples))) return b.log.failure("[Failure] - out of device memory for the compare scratch");
+        CompareTotals n;
+        if (compare_count(a, head.p, perPair.p, t, &n, stream) != hipSuccess) return failed();
+        uint32_t byRelation[5] = { n.identical, n.conflict, n.aWeaker, n.bWeaker, n.hint };
+        for (uint32_t c = 0; c < 16; ++c) {   // the primitives with two special entries: one field at level 0 each
+            info.totals[c >> 2][c & 3] = n.totals[c] + ((uint64_t)n.specialCells[c] << 24);
+            const uint32_t r = compare_cell_relation(c >> 2, c & 3);
+            if (r == 0) byRelation[0] += n.specialCells[c];
+            for (uint32_t bit = 0; bit < 4; ++bit)
+                if (r & (1u << bit)) byRelation[1 + bit] += n.specialCells[c];
+        }
+        info.identicalPrimitives = byRelation[0]; info.conflictPrimitives = byRelation[1]; info.aWeakerPrimitives = byRelation[2];
+        info.bWeakerPrimitives = byRelation[3]; info.hintPrimitives = byRelation[4];
+        info.skippedPrimitives = t.skipped; info.comparedPairs = t.tuples; info.refinedPairs = n.refined; info.firstConflictPrimitive = n.firstConflict;
+    }
+    if (outInfo) *outInfo = info;
+    return ommResult_SUCCESS;
+}
+}
+
+OMM_MI355X_API ommResult ommxCompareMicromaps(ommBaker baker, const ommCpuBakeResultDesc* deviceResultA, const ommCpuBakeResultDesc* deviceResultB,
+                                              const ommxCompareDesc* desc, const ommxCompareOutputs* outputs, ommxCompareInfo* outInfo, void* hipStream)
+{
+    Baker* b = baker_for_device_results(baker);
+    if (!b) return ommResult_INVALID_ARGUMENT;
+    if (deviceResultA == nullptr) return b->log.invalid("[Invalid Arg] - deviceResultA was not set");
+    if (deviceResultB == nullptr) return b->log.invalid("[Invalid Arg] - deviceResultB was not set");
+    if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxCompareDesc was not set");
+    if (outputs == nullptr && outInfo == nullptr) return b->log.invalid("[Invalid Arg] - neither outputs nor outInfo was set");
+    return guarded(&b->log, [&] { return compare_device(*b, *deviceResultA, *deviceResultB, *desc, outputs, outInfo, (hipStream_t)hipStream); });
 }
 
 // One result from chosen primitives of several device-resident results (include/omm_mi355x_ext.h; kernels in gather_kernels.hip): build the source table

@@ -1,6 +1,7 @@
 // result_words.h -- the device code shared by the kernels that stage the blocks of a new result (coarsen_units, coarsen_deep, combine_units) and by
 // the tail that turns staged blocks into a result (rebuild_kernels.hip): a lane's fields of a source block as bit planes, whole output words with
-// their digest and uniformity mask, the reduction of those two per workgroup, and a workgroup's counters.
+// their digest and uniformity mask, the reduction of those two per workgroup, and a workgroup's counters.  compare_units (ommxCompareMicromaps)
+// reads its two sides with load_fields and stages nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
