@@ -807,6 +807,105 @@ OMM_MI355X_API ommResult ommxCompareMicromaps(ommBaker baker, const ommCpuBakeRe
                                               const ommxCompareDesc* desc, const ommxCompareOutputs* outputs /* or NULL */,
                                               ommxCompareInfo* outInfo /* or NULL */, void* hipStream);
 
+/* ---- a micromap drawn in texture space: which primitive, which micro-triangle and which state lies over each pixel of a viewport ----
+ * ommxRasterizeMicromap  draws the primitives of a device-resident result over the alpha texture they were baked from, one sample per pixel, and counts
+ *                        per pixel where a known state contradicts the alpha test at that point.  It is the view the SDK's ommDebugSaveAsImages gives
+ *                        (which stays NOT_IMPLEMENTED here: that dump has no exact definition), under a rule of this library's own that is exact, and
+ *                        the answer to "does this result still agree with this texture?" without a second bake.  Inputs and outputs are device memory.
+ *   inputs               `deviceDesc` is the device-resident input desc as ommxResolveHits takes it (a texture of this baker, sampler, cut-off, the two
+ *                        alphaCutoff* states, device texcoords and indices).  `deviceResult` is a HOST struct over DEVICE arrays as for
+ *                        ommxLookupOpacity; a derived result (coarsened, fitted, combined, gathered, re-oriented) is as good as a bake's.
+ *   pixels               pixel (x, y), 0 <= x < width, 0 <= y < height; row 0 is the lowest v.  Its sample point, in fp64 with one rounding per written
+ *                        operation and no contraction:  stepU = ((double)uvMax[0] - (double)uvMin[0]) / (double)width,
+ *                        U = (double)uvMin[0] + ((double)x + 0.5) * stepU; V likewise from uvMin[1], uvMax[1], height and y.
+ *   primitives           [firstPrimitive, firstPrimitive + primitiveCount), the sum taken in 64 bits and cut to deviceDesc->indexCount / 3;
+ *                        primitiveCount 0xFFFFFFFF means "to the end", 0 draws the background only.  The triangle of primitive p is A, B, C in
+ *                        index-buffer order: its three texture coordinates exactly as the bake's setup reads them (UNORM16, FP16, FP32, any stride,
+ *                        8-, 16- and 32-bit indices), widened to fp64.
+ *   coverage             in fp64, in the written order:
+ *                            wA = (Bx-U)*(Cy-V) - (By-V)*(Cx-U)      wB = (Cx-U)*(Ay-V) - (Cy-V)*(Ax-U)      wC = (Ax-U)*(By-V) - (Ay-V)*(Bx-U)
+ *                            area2 = (Bx-Ax)*(Cy-Ay) - (By-Ay)*(Cx-Ax)
+ *                        area2 zero or not finite: the primitive is degenerate, covers nothing and is counted (a NaN or infinite coordinate makes it
+ *                        so).  Otherwise the pixel is covered iff each of wA, wB, wC is zero or has area2's sign: the closed triangle, either
+ *                        winding.  The two triangles at a shared edge compute exactly negated values there, so adjacent triangles leave no gap.
+ *   owner                the LOWEST covering primitive index of the range.  Barycentrics u = (float)(wB / area2), v = (float)(wC / area2): the hit
+ *                        convention (1-u-v) V0 + u V1 + v V2.  state = ommx_opacity_state(deviceResult, owner, u, v) (omm_mi355x_lookup.h); the
+ *                        micro-triangle is ommx_micro_index(u, v, level of the selected block), 0 for a special index.  A primitive at or beyond the
+ *                        result's indexCount, or one that fails that function's bounds rule, has state OMMX_OPACITY_INVALID (0xFF) and micro-triangle
+ *                        0xFFFFFFFF; nothing is read outside the arrays.
+ *   alpha                mip 0 sampled at ((float)U, (float)V) with runtimeSamplerDesc, by the sampler of ommxResolveHits.  alphaTest = alphaCutoff <
+ *                        alpha; c = alphaTest ? alphaCutoffGreater : alphaCutoffLessEqual.  A covered pixel with state s < 2 and (c & 1) != s is a
+ *                        contradiction.  Consequences: a 2-state result contradicts by construction where the bake was unknown (it had to name a known
+ *                        state for a micro-triangle the alpha edge crosses); a fresh 4-state bake is expected to contradict nowhere, since it calls a
+ *                        micro-triangle known only where the alpha test is the same all over it (under the Linear filter up to the sliver finding of
+ *                        DESIGN 5.12).
+ *   picture              integers only.  g = (uint8)(min(max(alpha, 0), 1) * 255.f + 0.5f), NaN gives 0.  An uncovered pixel is (g, g, g, 255).  A
+ *                        covered one is (lut[s] + g + 1) >> 1 per channel with the SDK's colours: Transparent (0, 0, 255), Opaque (0, 255, 0),
+ *                        UnknownTransparent (255, 0, 255), UnknownOpaque (255, 255, 0), invalid (255, 128, 0); MonochromeUnknowns draws
+ *                        UnknownTransparent like UnknownOpaque.  Then, in this order: c -= c >> 3 for an inverted micro-triangle (d < 0 in
+ *                        ommx_micro_vertices; special indices, level 0 and invalid states are upright); c >>= 1 under HighlightReuse for a reused
+ *                        block: the state is valid, the owner's entry e is >= 0 and a lower primitive of the range (and of the result's indexCount) has
+ *                        the same entry.  Alpha is 255.  Contour: unless NoContour is set, a pixel is (255, 0, 0, 255) instead if its alphaTest
+ *                        differs from that of (x + 1, y) or of (x, y + 1), where those exist.
+ *   outputs              DEVICE memory, every member optional, tight rows ([height][width], row 0 first); a member that is set is written for every
+ *                        pixel.  primitiveIds and microTriangles are 4-byte aligned.
+ *   info                 exact counts: coveredPixels; pixelsPerState[s] and invalidPixels (they add up to coveredPixels); alphaAbovePixels (alphaTest
+ *                        of EVERY pixel, covered or not); contradictions; drawnPrimitives (primitives of the range that own at least one pixel);
+ *                        degeneratePrimitives (of the range).  The info is the same whichever outputs are asked for.
+ *   purity               a pure function of its inputs: ownership is an integer minimum, every count an integer sum.  Two calls return the same bytes.
+ *   stream, memory       the kernels run on `hipStream` (null = the null stream), which the call synchronises before it returns.  Scratch comes from
+ *                        the baker's device pool and is back there when the call returns: an owner word per pixel when primitiveIds is not handed in,
+ *                        eighteen bytes per primitive of the range, and a word per descriptor under HighlightReuse.  *outInfo is written on
+ *                        SUCCESS only.
+ *   result codes         judged before the device is touched, in this order, each with a log line of its own: a null baker or a handle that is no
+ *                        baker's (these without a line: there is nobody to tell), null deviceDesc, null deviceResult, null desc, outputs and outInfo
+ *                        both null, unknown flag bits, non-zero reserved bytes, width or height 0 or above OMMX_RASTER_MAX_SIZE, a viewport bound that
+ *                        is not finite or uvMax <= uvMin on an axis, an unknown indexFormat of the result, null arrays of the result with non-zero
+ *                        counts as in ommxCompareMicromaps, primitiveIds or microTriangles not 4-byte aligned -- all INVALID_ARGUMENT; then
+ *                        deviceDesc is judged as ommxResolveHits judges it, with the same codes (a baker of another type, no texture, unknown sampler
+ *                        enums, the checks of a bake's desc, a texture of another baker).  Without a usable device, or when device memory runs out
+ *                        -> FAILURE with a log line.
+ * ommxDebugSaveImagePNG  writes an 8-bit RGBA image in HOST memory (an rgba output after hipMemcpy) as a PNG file: colour type 6, filter byte 0 per row,
+ *                        one zlib stream of stored blocks of at most 65 535 bytes, CRC-32 and Adler-32 computed here; no device, no third-party code.
+ *                        Rows are written in memory order (row 0 of a rasterized picture, the lowest v, is the file's top row).  rowPitchInBytes 0
+ *                        means 4 * width.  Null arguments, a zero size or a pitch below 4 * width -> INVALID_ARGUMENT; a file that cannot be written
+ *                        -> FAILURE. */
+#define OMMX_RASTER_MAX_SIZE 16384u
+typedef enum ommxRasterFlags {
+    ommxRasterFlags_None               = 0,
+    ommxRasterFlags_NoContour          = 1,   /* do not draw the alpha test's contour */
+    ommxRasterFlags_MonochromeUnknowns = 2,   /* UnknownTransparent in UnknownOpaque's colour */
+    ommxRasterFlags_HighlightReuse     = 4    /* halve the colour of blocks that a lower primitive of the range uses too */
+} ommxRasterFlags;
+typedef struct ommxRasterDesc {
+    float    uvMin[2], uvMax[2];              /* the viewport in texture coordinates: finite, uvMin < uvMax on both axes */
+    uint32_t width, height;                   /* 1..OMMX_RASTER_MAX_SIZE each */
+    uint32_t firstPrimitive, primitiveCount;  /* 0xFFFFFFFF: to the end */
+    uint32_t flags;                           /* ommxRasterFlags */
+    uint8_t  reserved[4];                     /* must be 0 */
+} ommxRasterDesc;
+typedef struct ommxRasterOutputs {            /* DEVICE memory, every member optional, [height][width], row 0 = lowest v */
+    uint32_t* primitiveIds;                   /* the owner; 0xFFFFFFFF = no primitive */
+    uint32_t* microTriangles;                 /* index within the block; 0 for a special index; 0xFFFFFFFF = no primitive or an invalid state */
+    uint8_t*  states;                         /* 0..3; 0xFF = invalid (OMMX_OPACITY_INVALID); 0xFE = no primitive */
+    uint8_t*  alphaTest;                      /* 0 / 1, for every pixel */
+    uint8_t*  rgba;                           /* [height][width][4] */
+} ommxRasterOutputs;
+typedef struct ommxRasterInfo {
+    uint64_t coveredPixels;
+    uint64_t pixelsPerState[4];
+    uint64_t invalidPixels;
+    uint64_t alphaAbovePixels;
+    uint64_t contradictions;
+    uint32_t drawnPrimitives;
+    uint32_t degeneratePrimitives;
+} ommxRasterInfo;
+OMM_MI355X_API ommResult ommxRasterizeMicromap(ommBaker baker, const ommCpuBakeInputDesc* deviceDesc, const ommCpuBakeResultDesc* deviceResult,
+                                               const ommxRasterDesc* desc, const ommxRasterOutputs* outputs /* or NULL */,
+                                               ommxRasterInfo* outInfo /* or NULL */, void* hipStream);
+OMM_MI355X_API ommResult ommxDebugSaveImagePNG(const char* path, const void* hostRgba8, uint32_t width, uint32_t height,
+                                               uint32_t rowPitchInBytes /* 0 = 4 * width */);
+
 /* ---- an alpha texture from an image that is already in device memory ----
  * ommxCreateTextureDevice  ommCpuCreateTexture for texels that live in HBM: ONE channel of an interleaved (or packed single-channel) image is read where
  *                        it is; nothing is downloaded, restaged or uploaded.  The result is an ordinary ommCpuTexture, byte for byte the texture

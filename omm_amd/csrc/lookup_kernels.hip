@@ -1,10 +1,10 @@
 // lookup_kernels.hip -- using a baked micromap: the OMM state of a batch of ray hits (lookup_opacity) and the any-hit answer that samples the
 // alpha texture only where the OMM leaves the hit unknown (resolve_hits).  The per-hit decode is include/omm_mi355x_lookup.h, the same code the
-// host entry point ommxLookupOpacityHost runs; texel addressing and the bilinear filter are the classifier's own (classify_device.h), so a
-// resolved hit is sampled the way the bake classified its micro-triangle.
+// host entry point ommxLookupOpacityHost runs; texture coordinates and the sampler are tex_fetch.h (the classifier's own texel addressing and bilinear
+// filter), so a resolved hit is sampled the way the bake classified its micro-triangle.
 #include <hip/hip_runtime.h>
 #include "lookup_kernels.h"
-#include "classify_device.h"
+#include "tex_fetch.h"   // fetch_tex_coord, sample_alpha (shared with raster_kernels.hip)
 #include "../../include/omm_mi355x_lookup.h"
 
 namespace ommx {
@@ -35,44 +35,6 @@ __global__ __launch_bounds__(kLookupBlock) void lookup_opacity(ommCpuBakeResultD
         const ommxHit h = hits[i];
         out[i] = (uint8_t)hit_state(r, h, force2 != 0);
     }
-}
-
-// _Float16 -> float is exact (denormals included): the value glm::unpackHalf2x16 gives the bake's setup
-__device__ __forceinline__ float half_bits(uint32_t h)
-{
-    const uint16_t b = (uint16_t)h;
-    _Float16 f;
-    __builtin_memcpy(&f, &b, 2);
-    return (float)f;
-}
-
-// texture coordinate of vertex `vi`, read as the bake's setup reads it (setup_fetch)
-__device__ __forceinline__ V2 fetch_tex_coord(const ResolveParams& R, uint32_t vi)
-{
-    const uint8_t* base = (const uint8_t*)R.texCoords + (size_t)R.texCoordStride * vi;
-    if (R.texCoordFormat == ommTexCoordFormat_UV32_FLOAT) {
-        if (((uintptr_t)base & 3u) == 0) return mk2(((const float*)base)[0], ((const float*)base)[1]);
-        uint32_t a = 0, b = 0;
-        for (int q = 0; q < 4; ++q) { a |= (uint32_t)base[q] << (8 * q); b |= (uint32_t)base[4 + q] << (8 * q); }
-        return mk2(__uint_as_float(a), __uint_as_float(b));
-    }
-    uint32_t v = 0;
-    for (int q = 0; q < 4; ++q) v |= (uint32_t)base[q] << (8 * q);
-    if (R.texCoordFormat == ommTexCoordFormat_UV16_UNORM)
-        return mk2((float)(v & 0xffffu) * 1.5259021896696421759314870504694e-5f, (float)(v >> 16) * 1.5259021896696421759314870504694e-5f);
-    return mk2(half_bits(v & 0xffffu), half_bits(v >> 16));
-}
-
-// alpha of mip 0 at texture coordinate p with the runtime sampler: Linear = the classifier's bilinear(), Nearest = the texel under p
-template <bool FP32>
-__device__ __forceinline__ float sample_alpha(const ClassifyParams& P, V2 p)
-{
-    const DevMip& m = P.mips[0];
-    TexWindow W; W.tex = nullptr; W.sat = nullptr; W.base = nullptr; W.sx = 0; W.sy = 0; W.w = 0; W.h = 0;   // no LDS window: every fetch reads HBM
-    if (P.filterLinear) return bilinear<FP32, ModeDynamic>(P, m, p, W);
-    const int x = tex_coord(P.addrMode, P.pow2Dispatch, cvt_trunc_x86(__builtin_floorf(p.x * m.fw)), m.w, m.log2w);
-    const int y = tex_coord(P.addrMode, P.pow2Dispatch, cvt_trunc_x86(__builtin_floorf(p.y * m.fh)), m.h, m.log2h);
-    return load_texel_border<FP32>(m, x, y, P.borderAlpha, W);
 }
 
 // out: bit 0 = opaque, bits 1-2 = OMM state, bit 3 = texture sampled; 0xFF = invalid hit

@@ -21,6 +21,8 @@
 #include "compare_count.h"
 #include "gather_kernels.h"
 #include "reorient_kernels.h"
+#include "raster_kernels.h"
+#include "png_store.h"
 #include "texture_kernels.h"
 #include "block_kernels.h"
 #include "bc7_kernels.h"
@@ -3666,43 +3668,133 @@ OMM_MI355X_API ommResult ommxReorientMicromap(ommBaker baker, const ommCpuBakeRe
     return guarded(&b->log, [&] { return reorient_device(*b, *deviceResult, *desc, outResult, outInfo, (hipStream_t)hipStream); });
 }
 
-// Any-hit resolution of hits against a device-resident result (include/omm_mi355x_ext.h; kernels in lookup_kernels.hip).  The desc is checked as
-// ommxBakeDevice checks it, so a desc that could not have produced the result is refused with the same code.
+// What ommxResolveHits and ommxRasterizeMicromap ask of the device-resident input desc, from the texture on: it is checked as ommxBakeDevice checks it, so
+// a desc that could not have produced the result is refused with the same code.  `entry`: the caller's name for the line about another baker's texture.
+namespace {
+ommResult check_consumer_desc(Baker& b, ommBaker baker, const ommCpuBakeInputDesc& desc, const char* entry)
+{
+    if (tag_of(baker) != kCpuBaker) return b.log.invalid("Baker was not created as the right type");
+    if (desc.texture == 0) return b.log.invalid("[Invalid Argument] - ommCpuBakeInputDesc has no texture set");
+    if (sampler_enums_unknown(desc)) return ommResult_FAILURE;
+    ommResult r = validate_desc(b, desc);
+    if (r != ommResult_SUCCESS) return r;
+    r = scope_fences(b, desc, false);
+    if (r != ommResult_SUCCESS) return r;
+    if (untag<Texture>(desc.texture)->owner != &b) {
+        char buf[160]; snprintf(buf, sizeof buf, "[Invalid Argument] - %s: the texture was created by another baker", entry);
+        return b.log.invalid(buf);
+    }
+    return ommResult_SUCCESS;
+}
+// mip 0 of the texture, the sampler and the mesh of a desc that passed check_consumer_desc
+ResolveParams consumer_params(const ommCpuBakeInputDesc& desc)
+{
+    const Texture& tex = *untag<Texture>(desc.texture);
+    ResolveParams rp; memset(&rp, 0, sizeof rp);
+    ClassifyParams& P = rp.tex;
+    P.mips[0] = dev_mip(tex.mips[0]);
+    P.mipCount = 1; P.pow2Dispatch = P.mips[0].pow2;
+    P.texIsFp32 = tex.format == ommCpuTextureFormat_FP32;
+    P.addrMode = desc.runtimeSamplerDesc.addressingMode;
+    P.filterLinear = desc.runtimeSamplerDesc.filter == ommTextureFilterMode_Linear;
+    P.cutoff = desc.alphaCutoff; P.borderAlpha = desc.runtimeSamplerDesc.borderAlpha;
+    P.stateGT = desc.alphaCutoffGreater; P.stateLE = desc.alphaCutoffLessEqual;
+    rp.texCoords = desc.texCoords; rp.texCoordFormat = desc.texCoordFormat;
+    rp.texCoordStride = desc.texCoordStrideInBytes ? desc.texCoordStrideInBytes : (desc.texCoordFormat == ommTexCoordFormat_UV32_FLOAT ? 8u : 4u);
+    rp.indices = desc.indexBuffer; rp.indexFormat = desc.indexFormat; rp.numTris = desc.indexCount / 3u;
+    return rp;
+}
+}
+
+// Any-hit resolution of hits against a device-resident result (include/omm_mi355x_ext.h; kernels in lookup_kernels.hip).
 OMM_MI355X_API ommResult ommxResolveHits(ommBaker baker, const ommCpuBakeInputDesc* desc, const ommCpuBakeResultDesc* result,
                                          const ommxHit* hits, uint32_t count, uint8_t* out, uint32_t flags, void* hipStream)
 {
     if (baker == 0) return ommResult_INVALID_ARGUMENT;
     Baker* b = untag<Baker>(baker);
     if (desc == 0) return b->log.invalid("input desc was not set");
-    if (tag_of(baker) != kCpuBaker) return b->log.invalid("Baker was not created as the right type");
-    if (desc->texture == 0) return b->log.invalid("[Invalid Argument] - ommCpuBakeInputDesc has no texture set");
-    if (sampler_enums_unknown(*desc)) return ommResult_FAILURE;
-    ommResult r = validate_desc(*b, *desc);
+    const ommResult r = check_consumer_desc(*b, baker, *desc, "ommxResolveHits");
     if (r != ommResult_SUCCESS) return r;
-    r = scope_fences(*b, *desc, false);
-    if (r != ommResult_SUCCESS) return r;
-    const Texture& tex = *untag<Texture>(desc->texture);
-    if (tex.owner != b) return b->log.invalid("[Invalid Argument] - ommxResolveHits: the texture was created by another baker");
     if (result == nullptr) return b->log.invalid("[Invalid Argument] - ommxResolveHits: result is not set");
     if ((flags & ~(uint32_t)(ommxLookupFlags_Force2State | ommxLookupFlags_IgnoreMicromap)) != 0) return b->log.invalid("[Invalid Argument] - ommxResolveHits: unknown flags");
     if (count == 0) return ommResult_SUCCESS;
     if (hits == nullptr || out == nullptr) return b->log.invalid("[Invalid Argument] - ommxResolveHits: hits / out are not set");
-    ResolveParams rp; memset(&rp, 0, sizeof rp);
-    ClassifyParams& P = rp.tex;
-    P.mips[0] = dev_mip(tex.mips[0]);
-    P.mipCount = 1; P.pow2Dispatch = P.mips[0].pow2;
-    P.texIsFp32 = tex.format == ommCpuTextureFormat_FP32;
-    P.addrMode = desc->runtimeSamplerDesc.addressingMode;
-    P.filterLinear = desc->runtimeSamplerDesc.filter == ommTextureFilterMode_Linear;
-    P.cutoff = desc->alphaCutoff; P.borderAlpha = desc->runtimeSamplerDesc.borderAlpha;
-    P.stateGT = desc->alphaCutoffGreater; P.stateLE = desc->alphaCutoffLessEqual;
-    rp.texCoords = desc->texCoords; rp.texCoordFormat = desc->texCoordFormat;
-    rp.texCoordStride = desc->texCoordStrideInBytes ? desc->texCoordStrideInBytes : (desc->texCoordFormat == ommTexCoordFormat_UV32_FLOAT ? 8u : 4u);
-    rp.indices = desc->indexBuffer; rp.indexFormat = desc->indexFormat; rp.numTris = desc->indexCount / 3u;
+    const ResolveParams rp = consumer_params(*desc);
     const DeviceScope onBakersDevice(b->bind_device());
     if (launch_resolve_hits(rp, *result, hits, count, out, flags, (hipStream_t)hipStream) != hipSuccess)
         return b->log.failure("[Failure] - ommxResolveHits: kernel launch failed");
     return ommResult_SUCCESS;
+}
+
+// A device-resident result drawn in texture space over its alpha texture (include/omm_mi355x_ext.h; kernels in raster_kernels.hip): the checks in the
+// documented order, the primitive range cut to the mesh, one block of scratch from the pool, the passes, then the info from the device's counts.
+namespace {
+bool finite_f(float x) { return x - x == 0.f; }
+ommResult rasterize_device(Baker& b, ommBaker baker, const ommCpuBakeInputDesc& in, const ommCpuBakeResultDesc& r, const ommxRasterDesc& d, const ommxRasterOutputs* outputs,
+                           ommxRasterInfo* outInfo, hipStream_t stream)
+{
+    if ((d.flags & ~(uint32_t)(ommxRasterFlags_NoContour | ommxRasterFlags_MonochromeUnknowns | ommxRasterFlags_HighlightReuse)) != 0) return b.log.invalid("[Invalid Arg] - ommxRasterDesc.flags has unknown bits");
+    if (d.reserved[0] || d.reserved[1] || d.reserved[2] || d.reserved[3]) return b.log.invalid("[Invalid Arg] - ommxRasterDesc.reserved must be 0");
+    if (d.width == 0 || d.width > OMMX_RASTER_MAX_SIZE || d.height == 0 || d.height > OMMX_RASTER_MAX_SIZE) return b.log.invalid("[Invalid Arg] - ommxRasterDesc.width and height must be 1..OMMX_RASTER_MAX_SIZE (16384)");
+    if (!finite_f(d.uvMin[0]) || !finite_f(d.uvMin[1]) || !finite_f(d.uvMax[0]) || !finite_f(d.uvMax[1]) || !(d.uvMin[0] < d.uvMax[0]) || !(d.uvMin[1] < d.uvMax[1]))
+        return b.log.invalid("[Invalid Arg] - ommxRasterDesc's viewport must be finite with uvMin < uvMax on both axes");
+    if (!is_index_format(r.indexFormat)) return b.log.invalid("[Invalid Arg] - deviceResult.indexFormat is not an index format");
+    if (has_null_array(r)) return b.log.invalid("[Invalid Arg] - deviceResult has a null array with a non-zero count");
+    if (outputs && ((((uintptr_t)outputs->primitiveIds) | ((uintptr_t)outputs->microTriangles)) & 3u) != 0) return b.log.invalid("[Invalid Arg] - ommxRasterOutputs.primitiveIds and microTriangles must be 4-byte aligned");
+    const ommResult checked = check_consumer_desc(b, baker, in, "ommxRasterizeMicromap");
+    if (checked != ommResult_SUCCESS) return checked;
+    if (!usable_device()) return b.log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)");
+    RasterArgs a; memset(&a, 0, sizeof a);
+    a.mesh = consumer_params(in); a.result = r;
+    a.view = raster_view(d.uvMin, d.uvMax, d.width, d.height);
+    const uint64_t tris = a.mesh.numTris;
+    const uint64_t end = d.primitiveCount == 0xFFFFFFFFu ? tris : std::min<uint64_t>((uint64_t)d.firstPrimitive + d.primitiveCount, tris);
+    a.first = d.firstPrimitive; a.count = end > d.firstPrimitive ? (uint32_t)(end - d.firstPrimitive) : 0u;
+    a.flags = d.flags;
+    if (outputs) { a.primitiveIds = outputs->primitiveIds; a.microTriangles = outputs->microTriangles; a.states = outputs->states; a.alphaTest = outputs->alphaTest; a.rgba = outputs->rgba; }
+    const DeviceScope onBakersDevice(b.bind_device());
+    PoolBlock scratch;
+    if (!scratch.acquire(b.devPool.get(), raster_scratch_bytes(a))) return b.log.failure("[Failure] - out of device memory for the rasterization scratch");
+    RasterCounts n;
+    if (raster_run(a, scratch.p, &n, stream) != hipSuccess) {   // the scratch goes back only when nothing can still touch it
+        (void)hipGetLastError(); (void)hipStreamSynchronize(stream);
+        return b.log.failure("[Failure] - the rasterization kernels could not run");
+    }
+    if (outInfo) {
+        ommxRasterInfo info; memset(&info, 0, sizeof info);
+        info.coveredPixels = n.covered;
+        for (int k = 0; k < 4; ++k) info.pixelsPerState[k] = n.perState[k];
+        info.invalidPixels = n.invalid; info.alphaAbovePixels = n.alphaAbove; info.contradictions = n.contradictions;
+        info.drawnPrimitives = (uint32_t)n.drawn; info.degeneratePrimitives = (uint32_t)n.degenerate;
+        *outInfo = info;
+    }
+    return ommResult_SUCCESS;
+}
+}
+
+OMM_MI355X_API ommResult ommxRasterizeMicromap(ommBaker baker, const ommCpuBakeInputDesc* deviceDesc, const ommCpuBakeResultDesc* deviceResult, const ommxRasterDesc* desc,
+                                               const ommxRasterOutputs* outputs, ommxRasterInfo* outInfo, void* hipStream)
+{
+    Baker* b = baker_for_device_results(baker);
+    if (!b) return ommResult_INVALID_ARGUMENT;
+    if (deviceDesc == nullptr) return b->log.invalid("[Invalid Arg] - deviceDesc was not set");
+    if (deviceResult == nullptr) return b->log.invalid("[Invalid Arg] - deviceResult was not set");
+    if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxRasterDesc was not set");
+    if (outputs == nullptr && outInfo == nullptr) return b->log.invalid("[Invalid Arg] - neither outputs nor outInfo was set");
+    return guarded(&b->log, [&] { return rasterize_device(*b, baker, *deviceDesc, *deviceResult, *desc, outputs, outInfo, (hipStream_t)hipStream); });
+}
+
+OMM_MI355X_API ommResult ommxDebugSaveImagePNG(const char* path, const void* hostRgba8, uint32_t width, uint32_t height, uint32_t rowPitchInBytes)
+{
+    if (path == nullptr || hostRgba8 == nullptr || width == 0 || height == 0) return ommResult_INVALID_ARGUMENT;
+    if (rowPitchInBytes != 0 && (uint64_t)rowPitchInBytes < 4ull * width) return ommResult_INVALID_ARGUMENT;
+    FILE* f = fopen(path, "wb");
+    if (!f) return ommResult_FAILURE;
+    const bool stored = png_store_rgba8(f, (const uint8_t*)hostRgba8, width, height, rowPitchInBytes ? (size_t)rowPitchInBytes : (size_t)4 * width);
+    const bool closed = fclose(f) == 0;
+    if (stored && closed) return ommResult_SUCCESS;
+    (void)remove(path);
+    return ommResult_FAILURE;
 }
 
 OMM_MI355X_API ommResult ommxSetBakerKnob(ommBaker baker, ommxBakerKnob knob, uint64_t value)
