@@ -807,6 +807,84 @@ OMM_MI355X_API ommResult ommxCompareMicromaps(ommBaker baker, const ommCpuBakeRe
                                               const ommxCompareDesc* desc, const ommxCompareOutputs* outputs /* or NULL */,
                                               ommxCompareInfo* outInfo /* or NULL */, void* hipStream);
 
+/* ---- a smaller micromap from near-copies: blocks that differ in a few micro-triangles become one, conservatively ----
+ * ommxMergeSimilarMicromaps  makes a new device-resident result in which 4-state blocks that are near-copies of each other share one block: the
+ *                        device-resident counterpart of the SDK's near-duplicate detection (which stays what it is inside ommCpuBake), for any
+ *                        result that is already in device memory -- a bake, the scene-wide array of ommxGatherMicromaps, a combined or a fitted
+ *                        result.  The SDK's rule is a serial greedy walk in a seeded random order; this is a rule of this library's own that is
+ *                        parallel, deterministic and conservative, in integers only.  `deviceResult` is a HOST struct over DEVICE arrays as for
+ *                        ommxCoarsenMicromap; the source is not modified.  The output is an ordinary ommxDeviceBakeResult without triangle areas,
+ *                        accepted by every entry that takes a result.
+ *   items                source selection, the bounds rule, skipping (entry -4, counted once in skippedPrimitives), special indices passing
+ *                        through and dropped unreferenced descriptors are those of ommxCoarsenMicromap ("source blocks").  Every valid source
+ *                        descriptor that a primitive selects is an item; its rank is its source descriptor index.  Items of format OC1_4_State
+ *                        with level >= 1 are CANDIDATES.  All other items pass through with their bits, as ommxCoarsenMicromap at
+ *                        maxSubdivisionLevel 12 leaves them: the 2-state format cannot express "unknown", so a join would not be conservative.
+ *   rounds               there are `rounds` rounds r = 0, 1, ...; all of them always run.  At the start of a round every live candidate i has
+ *                        bits B_i of level L_i.
+ *   positions            pos(L, r, j) = lowbias32(seed + 0x9E3779B9 * ((L << 16) | (r << 8) | j)) & (4^L - 1) for j < samples, all arithmetic
+ *                        modulo 2^32, with lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.  Repeated
+ *                        positions are allowed.
+ *   key                  key_i = (uint64)L_i << 56 | sum over j of state(B_i, pos(L_i, r, j)) << 2j.  The key is exact: no hash decides who
+ *                        meets whom.
+ *   leader               the leader of a key is the live candidate of lowest rank with that key.
+ *   absorption           a candidate i that is not the leader l of its key is absorbed iff d(B_i, B_l) * 4^(12 - L) <= maxDistance, where d is
+ *                        the number of micro-triangles whose 2-bit states differ; both blocks as they were at the start of the round.  i is
+ *                        compared with l only.
+ *   join                 after all decisions of the round, B_l <- join(B_l, every absorbed B_i) with "the state, 4-state" of ommxCoarsenMicromap
+ *                        applied to each micro-triangle across the blocks: sides differ -> mixedState, otherwise side | (any unknown ? 2 : 0).
+ *                        The join is symmetric and associative, so the result does not depend on order.
+ *   after a round        absorbed items are dead for good.  A leader is never absorbed in its own round.  absorbedPerRound[r] counts the items
+ *                        absorbed in round r.
+ *   after the rounds     root(d) is d if d was never absorbed, else the root of its leader.  The primitives of d get the block of root(d).
+ *                        outDeviceBlockRoots[d] = root(d): d itself for an item that passes through or survives, 0xFFFFFFFF for a descriptor
+ *                        that no primitive selects or that fails the bounds rule.  The exact merges of the tail are not reflected there.
+ *   the tail             the surviving blocks go through the tail of ommxCoarsenMicromap: uniform blocks become special indices unless
+ *                        DisableSpecialIndices, equal blocks merge with the lowest source index as representative, blocks are ordered by size
+ *                        descending, then representative ascending, and packed from offset 0.  The index buffer is in the source's indexFormat
+ *                        (the output never has more descriptors than the source).  Histograms as in ommxCoarsenMicromap.
+ *   info                 see ommxMergeInfo.  With default flags referencedBlocks == descArrayCount + absorbedBlocks + uniformBlocks +
+ *                        duplicateBlocks.  With outResult == NULL the same numbers are computed and no output arrays are allocated.
+ *   what follows         for every micro-triangle of every primitive the output state is the source state or an unknown state: with A = the
+ *                        output and B = the source, ommxCompareMicromaps shows neither CONFLICT nor B_WEAKER on any primitive.  Two calls return
+ *                        the same bytes.  With maxDistance == 0 only equal blocks can be absorbed, which the tail would have merged anyway:
+ *                        arrayData, descArray, the index buffer and both histograms equal those of ommxCoarsenMicromap at maxSubdivisionLevel 12
+ *                        with the same flags.  A leader that absorbs many members drifts away from each of them: the loss is bounded per
+ *                        comparison, not per cluster -- the totals of ommxCompareMicromaps and ommxDebugGetStatsDevice show what was lost.
+ *   stream, memory       as ommxCoarsenMicromap: the kernels run on `hipStream`, which the call synchronises before it returns; scratch comes
+ *                        from the baker's device pool; *outResult is written on SUCCESS only.
+ *   result codes         judged before the device is touched, in this order, each INVALID_ARGUMENT with a log line of its own: a null baker, a
+ *                        baker of unknown type (these two without a line), null deviceResult, null desc, outDeviceBlockRoots, outResult and
+ *                        outInfo all null, an unknown indexFormat, maxDistance > 4^12, rounds > 32, samples > 28, a mixedState other than 2 or 3,
+ *                        flag bits other than DisableSpecialIndices, non-zero reserved bytes, null arrays with non-zero counts.
+ *                        indexCount == 0 -> SUCCESS without a launch: the info is all zeros, *outResult is an empty result, the roots are not
+ *                        written.  Without a usable device, or when device memory runs out -> FAILURE with a log line. */
+#define OMMX_MERGE_MAX_ROUNDS  32
+#define OMMX_MERGE_MAX_SAMPLES 28
+typedef struct ommxMergeDesc {
+    uint32_t maxDistance;   /* in units of 4^-12 of a block: a block of level L is absorbed iff d * 4^(12-L) <= maxDistance; at most 4^12 */
+    uint32_t rounds;        /* 1..32; 0 = 8 */
+    uint32_t samples;       /* 1..28 sampled micro-triangles per signature; 0 = 16 */
+    uint32_t seed;
+    uint8_t  mixedState;    /* 2 or 3, as ommxCoarsenDesc::mixedState */
+    uint8_t  reserved[3];   /* must be 0 */
+    uint32_t flags;         /* ommxCoarsenFlags_DisableSpecialIndices only; any other bit -> INVALID_ARGUMENT */
+} ommxMergeDesc;
+typedef struct ommxMergeInfo {
+    uint64_t arrayDataSize;        /* of the output */
+    uint32_t descArrayCount;       /* of the output */
+    uint32_t referencedBlocks;     /* valid source descriptors that a primitive selects */
+    uint32_t candidateBlocks;      /* of those: OC1_4_State and level >= 1 (the only ones that take part) */
+    uint32_t absorbedBlocks;       /* of those: merged into a leader in some round */
+    uint32_t uniformBlocks, duplicateBlocks;   /* of the blocks left after the rounds, as in ommxCoarsenInfo */
+    uint32_t skippedPrimitives;
+    uint32_t absorbedPerRound[OMMX_MERGE_MAX_ROUNDS];
+} ommxMergeInfo;
+OMM_MI355X_API ommResult ommxMergeSimilarMicromaps(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxMergeDesc* desc,
+                                                   uint32_t* outDeviceBlockRoots /* [descArrayCount], DEVICE, or NULL */,
+                                                   ommxDeviceBakeResult* outResult /* NULL: info only */, ommxMergeInfo* outInfo /* or NULL */,
+                                                   void* hipStream);
+
 /* ---- a micromap drawn in texture space: which primitive, which micro-triangle and which state lies over each pixel of a viewport ----
  * ommxRasterizeMicromap  draws the primitives of a device-resident result over the alpha texture they were baked from, one sample per pixel, and counts
  *                        per pixel where a known state contradicts the alpha test at that point.  It is the view the SDK's ommDebugSaveAsImages gives

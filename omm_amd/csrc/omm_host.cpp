@@ -15,6 +15,7 @@
 #include "geometry_kernels.h"
 #include "geometry_cut.h"
 #include "coarsen_kernels.h"
+#include "merge_kernels.h"
 #include "fit_kernels.h"
 #include "combine_kernels.h"
 #include "compare_kernels.h"
@@ -3344,6 +3345,62 @@ OMM_MI355X_API ommResult ommxCoarsenMicromapLevels(ommBaker baker, const ommCpuB
                                                    ommxDeviceBakeResult* outResult, ommxCoarsenInfo* outInfo, void* hipStream)
 {
     return coarsen_entry(baker, deviceResult, deviceBlockLevels, desc, outResult, outInfo, hipStream);
+}
+
+// Near-copies among the 4-state blocks of a device-resident result merged into leaders (include/omm_mi355x_ext.h; kernels in merge_kernels.hip): read
+// the index buffer, size the staging arena, copy, run the rounds in place, then the tail as for a coarsening.
+namespace {
+ommResult check_merge_desc(const Logger& log, const ommCpuBakeResultDesc& r, const ommxMergeDesc& m)
+{
+    if (!is_index_format(r.indexFormat)) return log.invalid("[Invalid Arg] - deviceResult.indexFormat is not an index format");
+    if (m.maxDistance > kMergeUnit) return log.invalid("[Invalid Arg] - ommxMergeDesc.maxDistance must be at most 4^12 (16777216)");
+    if (m.rounds > OMMX_MERGE_MAX_ROUNDS) return log.invalid("[Invalid Arg] - ommxMergeDesc.rounds must be at most OMMX_MERGE_MAX_ROUNDS (32)");
+    if (m.samples > OMMX_MERGE_MAX_SAMPLES) return log.invalid("[Invalid Arg] - ommxMergeDesc.samples must be at most OMMX_MERGE_MAX_SAMPLES (28)");
+    if (m.mixedState != 2 && m.mixedState != 3) return log.invalid("[Invalid Arg] - ommxMergeDesc.mixedState must be 2 (UnknownTransparent) or 3 (UnknownOpaque)");
+    if ((m.flags & ~(uint32_t)ommxCoarsenFlags_DisableSpecialIndices) != 0) return log.invalid("[Invalid Arg] - ommxMergeDesc.flags has bits other than DisableSpecialIndices");
+    if (m.reserved[0] || m.reserved[1] || m.reserved[2]) return log.invalid("[Invalid Arg] - ommxMergeDesc.reserved must be 0");
+    if (has_null_array(r)) return log.invalid("[Invalid Arg] - deviceResult has a null array with a non-zero count");
+    return ommResult_SUCCESS;
+}
+// the stages of a merge inside DerivedResult::run
+ommResult merge_stages(DerivedResult& out, const MergeArgs& a, ommxMergeInfo* info)
+{
+    PoolBlock head, staging;
+    if (!out.acquire(head, merge_head_bytes(a))) return out.no_memory();
+    MergePlan plan;
+    if (merge_plan(a, head.p, &plan, out.stream) != hipSuccess) return out.failed();
+    if (plan.stagingBytes && !out.acquire(staging, (size_t)plan.stagingBytes)) return out.no_memory();
+    RebuildCounts n; MergeRounds rounds;
+    if (merge_stage(a, head.p, staging.p, plan, &rounds, &n, out.stream) != hipSuccess) return out.failed();
+    info->arrayDataSize = n.arrayBytes; info->descArrayCount = n.descCount; info->referencedBlocks = plan.referenced; info->candidateBlocks = plan.candidates;
+    info->absorbedBlocks = rounds.absorbed; info->uniformBlocks = n.uniform; info->duplicateBlocks = n.duplicate; info->skippedPrimitives = plan.skipped;
+    memcpy(info->absorbedPerRound, rounds.perRound, sizeof info->absorbedPerRound);
+    return out.emit(n, [&](const RebuildOutputs& o) { return merge_emit(a, head.p, staging.p, n, o, out.stream); });
+}
+ommResult merge_device(Baker& b, const ommCpuBakeResultDesc& r, const ommxMergeDesc& m, uint32_t* outRoots, ommxDeviceBakeResult* outResult, ommxMergeInfo* outInfo,
+                       hipStream_t stream)
+{
+    const ommResult ok = check_merge_desc(b.log, r, m);
+    if (ok != ommResult_SUCCESS) return ok;
+    ommxMergeInfo info; memset(&info, 0, sizeof info);
+    DerivedResult out(b, stream, "merged", "merge");
+    MergeArgs a; a.result = r; a.maxDistance = m.maxDistance; a.rounds = m.rounds ? m.rounds : 8u; a.samples = m.samples ? m.samples : 16u; a.seed = m.seed;
+    a.mixedState = m.mixedState; a.flags = m.flags; a.roots = outRoots;
+    const ommResult done = out.run(outResult, r.indexCount, r.indexFormat, [&] { return merge_stages(out, a, &info); });
+    if (done == ommResult_SUCCESS && outInfo) *outInfo = info;
+    return done;
+}
+}
+
+OMM_MI355X_API ommResult ommxMergeSimilarMicromaps(ommBaker baker, const ommCpuBakeResultDesc* deviceResult, const ommxMergeDesc* desc, uint32_t* outDeviceBlockRoots,
+                                                   ommxDeviceBakeResult* outResult, ommxMergeInfo* outInfo, void* hipStream)
+{
+    Baker* b = baker_for_device_results(baker);
+    if (!b) return ommResult_INVALID_ARGUMENT;
+    if (deviceResult == nullptr) return b->log.invalid("[Invalid Arg] - deviceResult was not set");
+    if (desc == nullptr) return b->log.invalid("[Invalid Arg] - ommxMergeDesc was not set");
+    if (!outDeviceBlockRoots && !outResult && !outInfo) return b->log.invalid("[Invalid Arg] - none of outDeviceBlockRoots, outResult and outInfo was set");
+    return guarded(&b->log, [&] { return merge_device(*b, *deviceResult, *desc, outDeviceBlockRoots, outResult, outInfo, (hipStream_t)hipStream); });
 }
 
 // What every block of a device-resident result would keep at every coarser level, and a result fitted to a byte budget from those rows
