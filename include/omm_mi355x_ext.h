@@ -112,7 +112,13 @@ typedef enum ommxBakerKnob {
     ommxBakerKnob_ZeroAhead        = 9, /* compressed transfer: 0 / default: while the device bakes, the helper threads zero the idle result block the previous bake of this
                                            baker left (default allocator only), and the expansion does not write codec blocks of zeros again (ommxBakeTimings::prefilledBytes,
                                            expandSkippedBytes); 1: off -- the helper threads only run during the expansion */
-    ommxBakerKnob_MAX_NUM          = 10
+    ommxBakerKnob_PoisonMemory     = 10, /* debugging aid in the spirit of glibc's MALLOC_PERTURB_.  0 / default: off.  (1 << 32) | word: every block the baker's device pool hands
+                                           out (scratch of every device entry, the arrays of every device result, texture uploads), fresh or reused, and every device arena of
+                                           a bake's working set when the bake reserves it, is filled over its whole capacity with the 32-bit `word` before the caller sees
+                                           it (bit 32 only says "on", so a word of 0 can be asked for).  The fill is complete before the call goes on.  Any other non-zero
+                                           value is INVALID_ARGUMENT.  An answer that changes with the word reads device memory nobody wrote.  The pinned host result pool
+                                           is not filled.  See ommxDebugGetPoisonedBytes. */
+    ommxBakerKnob_MAX_NUM          = 11
 } ommxBakerKnob;
 typedef enum ommxResultTransfer {
     ommxResultTransfer_Auto        = 0,
@@ -126,6 +132,10 @@ OMM_MI355X_API ommResult ommxSetBakerKnob(ommBaker baker, ommxBakerKnob knob, ui
 /* Gives every idle pooled block of the baker back to the system now: pinned host blocks, device result blocks, device working sets of finished bakes.  Results
  * that are still alive keep their memory.  Safe to call at any time from any thread; the next bake allocates again. */
 OMM_MI355X_API ommResult ommxTrimBaker(ommBaker baker);
+/* Bytes of device memory filled under ommxBakerKnob_PoisonMemory since the baker was created: blocks of the device pool and arenas of bake working sets (the
+ * shadow bakers of a multi-device ommCpuBake count into their owner's).  Either pointer may be NULL; a baker that never filled anything gives zeros.  Null or
+ * foreign baker -> INVALID_ARGUMENT. */
+OMM_MI355X_API ommResult ommxDebugGetPoisonedBytes(ommBaker baker, uint64_t* devicePoolBytes, uint64_t* workingSetBytes);
 
 /* ---- device-resident bake ----
  * Same contract as ommCpuBake (include/omm_mi355x.h; reference omm.h:574) except for where the bulk data lives:

@@ -123,6 +123,25 @@ struct HostBlockPool {
     void release(uint8_t* p) { if (p) { std::lock_guard<std::mutex> g(mu); idle.push_back(p); } }
     static HostBlockPool& get() { static HostBlockPool* pool = new HostBlockPool(); return *pool; }   // (never destroyed: no HIP calls at process exit)
 };
+// ---- ommxBakerKnob_PoisonMemory: the one fill of the device pool and of the working-set arenas, and its two counters ----
+// One object per baker (the shadow bakers of a multi-device bake share their owner's).  Off (word == 0) costs the hand-out points one relaxed load: fill() is
+// only ever called behind on().  The fill runs on the null stream of the current device and is waited for, so it is complete before any stream of the caller's
+// (the bake streams do not synchronise with the null stream) can touch the memory; what used the memory before has drained by the time it is handed out again.
+struct PoisonFill {
+    std::atomic<uint64_t> word{ 0 };   // 0: off; else bit 32 | the 32-bit fill word
+    std::atomic<uint64_t> poolBytes{ 0 }, workingSetBytes{ 0 };
+    bool on() const { return word.load(std::memory_order_relaxed) != 0; }
+    bool fill(void* p, size_t bytes, bool workingSet) {
+        const uint32_t w = (uint32_t)word.load(std::memory_order_relaxed);
+        bool ok = bytes < 4 || hipMemsetD32Async((hipDeviceptr_t)p, (int)w, bytes / 4, nullptr) == hipSuccess;
+        for (size_t k = 0; ok && k < (bytes & 3); ++k)   // (a capacity that is no multiple of 4: the word's low bytes come first)
+            ok = hipMemsetAsync((uint8_t*)p + (bytes & ~(size_t)3) + k, (int)((w >> (8 * k)) & 0xFFu), 1, nullptr) == hipSuccess;
+        ok = ok && hipStreamSynchronize(nullptr) == hipSuccess;
+        if (!ok) { (void)hipGetLastError(); return false; }
+        (workingSet ? workingSetBytes : poolBytes).fetch_add(bytes, std::memory_order_relaxed);
+        return true;
+    }
+};
 struct DeviceArena {
     uint8_t* base = nullptr; size_t cap = 0, used = 0;
     uint8_t* hostBlock = nullptr; bool hostBlockTried = false;
@@ -132,11 +151,15 @@ struct DeviceArena {
         if (!hostBlockTried) { hostBlockTried = true; hostBlock = HostBlockPool::get().acquire(); }
         return hostBlock;
     }
-    bool reserve(size_t bytes) {
-        if (bytes <= cap) { used = 0; return true; }
-        if (base) { (void)hipFree(base); base = nullptr; cap = 0; }
-        if (hipMalloc((void**)&base, bytes) != hipSuccess) { base = nullptr; (void)hipGetLastError(); return false; }
-        cap = bytes; used = 0; return true;
+    // (every caller reserves an arena once per bake, ahead of the first write of that bake into it: the contents are undefined by contract, kept memory or fresh)
+    bool reserve(size_t bytes, PoisonFill& poison) {
+        if (bytes <= cap) used = 0;
+        else {
+            if (base) { (void)hipFree(base); base = nullptr; cap = 0; }
+            if (hipMalloc((void**)&base, bytes) != hipSuccess) { base = nullptr; (void)hipGetLastError(); return false; }
+            cap = bytes; used = 0;
+        }
+        return !poison.on() || poison.fill(base, cap, true);
     }
     template <class T> T* take(size_t count) {
         const size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
@@ -191,12 +214,22 @@ struct ArenaPool {
 struct DevPool {
     struct Blk { void* p; size_t cap; bool used; bool exempt; };
     std::mutex mu; std::vector<Blk> blks; std::atomic<bool> retain{ true };
+    std::shared_ptr<PoisonFill> poison = std::make_shared<PoisonFill>();   // (the baker's; a shadow baker's pool points at its owner's)
     ~DevPool() { for (auto& b : blks) (void)hipFree(b.p); }
+    // (the block is marked used before it is filled: nobody else can be handed it, and the caller has not seen it yet)
+    void* poisoned(void* p, size_t cap) {
+        if (!poison->on() || poison->fill(p, cap, false)) return p;
+        release(p); return nullptr;
+    }
     void* acquire(size_t bytes) {
         if (bytes == 0) bytes = 1;
         {
-            std::lock_guard<std::mutex> g(mu);
-            for (auto& b : blks) if (!b.used && b.cap >= bytes && b.cap / 2 <= bytes + 4096) { b.used = true; return b.p; }
+            void* p = nullptr; size_t cap = 0;
+            {
+                std::lock_guard<std::mutex> g(mu);
+                for (auto& b : blks) if (!b.used && b.cap >= bytes && b.cap / 2 <= bytes + 4096) { b.used = true; p = b.p; cap = b.cap; break; }
+            }
+            if (p) return poisoned(p, cap);
         }
         void* p = nullptr;
         const size_t cap = (bytes + 4095) & ~(size_t)4095;
@@ -205,9 +238,8 @@ struct DevPool {
             trim(0);                                  // give the idle blocks back and retry once
             if (hipMalloc(&p, cap) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
         }
-        std::lock_guard<std::mutex> g(mu);
-        blks.push_back({ p, cap, true, false });
-        return p;
+        { std::lock_guard<std::mutex> g(mu); blks.push_back({ p, cap, true, false }); }
+        return poisoned(p, cap);
     }
     void release(void* p) {
         if (!p) return;
@@ -855,7 +887,7 @@ struct BakeRun {
         const size_t setupBytes = setup_scratch_bytes(T), tailBytes = tail_scratch_bytes(maxItems, T), streamScratch = so ? stream_scratch_bytes(maxItems) : 0;
         const size_t scratchBytes = std::max(std::max(setupBytes, tailBytes), streamScratch);
         // size and pointers from the same traversal (bake_host.h): first over offsets, then over the arena
-        if (!arena->reserve(carve_bake_tables(0, maxItems, scratchBytes, sh != nullptr, so != nullptr).bytes)) return L.failure("[Failure] - out of device memory for the bake working set");
+        if (!arena->reserve(carve_bake_tables(0, maxItems, scratchBytes, sh != nullptr, so != nullptr).bytes, *baker.devPool->poison)) return L.failure("[Failure] - out of device memory for the bake working set");
         tab = carve_bake_tables((uintptr_t)arena->base, maxItems, scratchBytes, sh != nullptr, so != nullptr);
         R.triAreaScratch = tab.triArea;
         return ommResult_SUCCESS;
@@ -986,7 +1018,7 @@ struct BakeRun {
         // single GPU does (asset-sized cards, 8 ranks: 15.0 -> 12 ms per step), except when the ranks merge their states by summation.
         if (generic_pass_wanted(baker.knob(ommxBakerKnob_GenericPass), microAll, hc.workload) && !streamChunks && !(sh && sh->mergeStates) && !ht && numActive)
             genericCapacity = generic_pass_capacity(hc.stateBytes, storeBits);
-        if (!statesArena->reserve(carve_bake_states(0, hc.stateBytes, queueBytes, streamChunks != 0, genericCapacity).bytes)) return L.failure("[Failure] - out of device memory for the packed micro-triangle states");
+        if (!statesArena->reserve(carve_bake_states(0, hc.stateBytes, queueBytes, streamChunks != 0, genericCapacity).bytes, *baker.devPool->poison)) return L.failure("[Failure] - out of device memory for the packed micro-triangle states");
         st = carve_bake_states((uintptr_t)statesArena->base, hc.stateBytes, queueBytes, streamChunks != 0, genericCapacity);
         e1b = et.mark();
         return ommResult_SUCCESS;
@@ -2635,7 +2667,7 @@ ommResult sharded_tail(ShardedBake* sb)
     //  from the triangle count: a few large blocks, level 10 and up, need more than that, so it comes from this arena)
     c.codecScratchBytes = c.asyncBegin ? pad256(shard_codec_scratch_bytes(c.strideBytes)) : 0;
     const size_t codecBytes = c.asyncBegin ? (size_t)c.compCap * (c.world + 1) + 1024 + c.codecScratchBytes : 0;
-    if (!sb->ses.set->xchg.reserve((size_t)c.strideBytes + 256 + gatherBytes + codecBytes)) return L.failure("[Failure] - out of device memory for the shard contribution");
+    if (!sb->ses.set->xchg.reserve((size_t)c.strideBytes + 256 + gatherBytes + codecBytes, *sb->baker->devPool->poison)) return L.failure("[Failure] - out of device memory for the shard contribution");
     c.dContrib = sb->ses.set->xchg.take<uint8_t>((size_t)c.strideBytes);
     c.dGathered = gatherBytes ? sb->ses.set->xchg.take<uint8_t>(gatherBytes) : nullptr;
     if (codecBytes) { c.dComp = sb->ses.set->xchg.take<uint8_t>((size_t)c.compCap); c.dGatherComp = sb->ses.set->xchg.take<uint8_t>((size_t)c.compCap * c.world); c.dCompSize = sb->ses.set->xchg.take<uint32_t>(1); c.dCodecScratch = sb->ses.set->xchg.take<uint8_t>(c.codecScratchBytes); }
@@ -2738,6 +2770,7 @@ Baker* peer_baker(Baker& b, uint32_t rank, int dev)
         std::unique_ptr<Baker> p(new (std::nothrow) Baker());
         if (!p) return nullptr;
         p->mem = b.mem; p->log = b.log; p->type = b.type;
+        p->devPool->poison = b.devPool->poison;   // (ommxBakerKnob_PoisonMemory: the owner's word, and its fills count into the owner's counters)
         b.peers.push_back(std::move(p));
     }
     Baker* p = b.peers[rank - 1].get();
@@ -3865,6 +3898,7 @@ OMM_MI355X_API ommResult ommxSetBakerKnob(ommBaker baker, ommxBakerKnob knob, ui
     if (knob == ommxBakerKnob_Devices && value > (uint64_t)kMaxRanks) return ommResult_INVALID_ARGUMENT;
     if (knob == ommxBakerKnob_HelperAffinity && value > 1) return ommResult_INVALID_ARGUMENT;
     if (knob == ommxBakerKnob_ZeroAhead && value > 1) return ommResult_INVALID_ARGUMENT;
+    if (knob == ommxBakerKnob_PoisonMemory && value != 0 && (value >> 32) != 1) return ommResult_INVALID_ARGUMENT;   // (off, or bit 32 | a 32-bit word)
     if (knob == ommxBakerKnob_RetainMemory) {
         if (value > 1) return ommResult_INVALID_ARGUMENT;
         Baker* bk = untag<Baker>(baker);
@@ -3872,7 +3906,17 @@ OMM_MI355X_API ommResult ommxSetBakerKnob(ommBaker baker, ommxBakerKnob knob, ui
         bk->hostPool->retain.store(keep); bk->devPool->retain.store(keep); bk->arenas->retain.store(keep);
         if (!keep) { const DeviceScope onBakersDevice(bk->device.load()); bk->hostPool->trim(); bk->devPool->trim(0); bk->arenas->trim(); }
     }
+    if (knob == ommxBakerKnob_PoisonMemory) untag<Baker>(baker)->devPool->poison->word.store(value);
     untag<Baker>(baker)->knobs[knob].store(value);
+    return ommResult_SUCCESS;
+}
+
+OMM_MI355X_API ommResult ommxDebugGetPoisonedBytes(ommBaker baker, uint64_t* devicePoolBytes, uint64_t* workingSetBytes)
+{
+    if (baker == 0 || tag_of(baker) != kCpuBaker) return ommResult_INVALID_ARGUMENT;
+    const PoisonFill& p = *untag<Baker>(baker)->devPool->poison;
+    if (devicePoolBytes) *devicePoolBytes = p.poolBytes.load();
+    if (workingSetBytes) *workingSetBytes = p.workingSetBytes.load();
     return ommResult_SUCCESS;
 }
 

@@ -25,8 +25,14 @@ TEX_UNORM8, TEX_FP32 = 0, 1
 FLAG_THREADS, FLAG_NO_SPECIAL, FLAG_FORCE32, FLAG_NO_DEDUP, FLAG_NEAR_DUP, FLAG_VALIDATION, FLAG_ALLOW8 = (1 << i for i in range(7))
 TEXFLAG_DISABLE_ZORDER = 1
 SPECIAL_FT, SPECIAL_FO, SPECIAL_FUT, SPECIAL_FUO = -1, -2, -3, -4
-KNOB_RESERVED0, KNOB_SHARD_CHUNK_BYTES, KNOB_STREAM_CHUNKS, KNOB_GENERIC_PASS, KNOB_RETAIN_MEMORY, KNOB_RESULT_TRANSFER, KNOB_EXPAND_THREADS, KNOB_DEVICES, KNOB_HELPER_AFFINITY, KNOB_ZERO_AHEAD = range(10)   # ommxBakerKnob
+KNOB_RESERVED0, KNOB_SHARD_CHUNK_BYTES, KNOB_STREAM_CHUNKS, KNOB_GENERIC_PASS, KNOB_RETAIN_MEMORY, KNOB_RESULT_TRANSFER, KNOB_EXPAND_THREADS, KNOB_DEVICES, KNOB_HELPER_AFFINITY, KNOB_ZERO_AHEAD, KNOB_POISON = range(11)   # ommxBakerKnob
 TRANSFER_AUTO, TRANSFER_PLAIN, TRANSFER_STREAMED, TRANSFER_COMPRESSED = range(4)   # ommxResultTransfer
+
+
+def poison(word):
+    """value of KNOB_POISON that fills with the 32-bit `word` (bit 32 says "on", so that a word of 0 can be asked for)"""
+    assert 0 <= word <= 0xFFFFFFFF
+    return (1 << 32) | word
 
 
 class SamplerDesc(C.Structure):
@@ -296,6 +302,14 @@ class Lib:
         self.dll.ommxSetBakerKnob.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
         r = self.dll.ommxSetBakerKnob(baker, knob, value)
         assert r == SUCCESS, r
+
+    def poisoned_bytes(self, baker):
+        """ommxDebugGetPoisonedBytes: (device pool bytes, working-set bytes) filled under KNOB_POISON so far"""
+        self.dll.ommxDebugGetPoisonedBytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        a, b = C.c_uint64(), C.c_uint64()
+        r = self.dll.ommxDebugGetPoisonedBytes(baker, C.byref(a), C.byref(b))
+        assert r == SUCCESS, r
+        return a.value, b.value
 
     def create_texture(self, baker, mips, alpha_cutoff=-1.0, disable_zorder=False, expect=SUCCESS, row_pitch=0):
         """mips: list of 2-D float32 / uint8 arrays (mip 0 first)."""

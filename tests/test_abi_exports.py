@@ -272,6 +272,33 @@ def test_baker_knobs_are_per_baker_state_not_environment():
             assert not any(w.split("@")[0] == "getenv" for w in undefined.split()), o
 
 
+def test_poison_knob_argument_rules_and_its_counters_need_no_gpu():
+    """ommxBakerKnob_PoisonMemory (knob 10) and ommxDebugGetPoisonedBytes: off, or bit 32 | a 32-bit word -- anything else is refused; knob 11 does
+    not exist; a baker that never filled anything reports zeros; either output pointer may be null, the baker may not."""
+    lib = ot.Lib("product")
+    dll = lib.dll
+    dll.ommxSetBakerKnob.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
+    dll.ommxDebugGetPoisonedBytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    assert ot.KNOB_POISON == 10
+    b = lib.create_baker()
+    for word in (0x00000000, 0x00000001, 0xFFFFFFFF, 0xA5A5A5A5):
+        assert ot.poison(word) == (1 << 32) | word
+        assert dll.ommxSetBakerKnob(b, ot.KNOB_POISON, ot.poison(word)) == ot.SUCCESS
+    for bad in (1, 0xA5A5A5A5, 0xFFFFFFFF, 1 << 33, (1 << 33) | (1 << 32) | 5, 1 << 63):
+        assert dll.ommxSetBakerKnob(b, ot.KNOB_POISON, bad) == ot.INVALID_ARGUMENT, hex(bad)
+    assert dll.ommxSetBakerKnob(b, ot.KNOB_POISON, 0) == ot.SUCCESS
+    assert dll.ommxSetBakerKnob(b, 11, 0) == ot.INVALID_ARGUMENT and dll.ommxSetBakerKnob(b, 11, ot.poison(0)) == ot.INVALID_ARGUMENT
+    assert lib.poisoned_bytes(b) == (0, 0)
+    one = C.c_uint64(77)
+    assert dll.ommxDebugGetPoisonedBytes(b, C.byref(one), None) == ot.SUCCESS and one.value == 0
+    one = C.c_uint64(77)
+    assert dll.ommxDebugGetPoisonedBytes(b, None, C.byref(one)) == ot.SUCCESS and one.value == 0
+    assert dll.ommxDebugGetPoisonedBytes(b, None, None) == ot.SUCCESS
+    untouched = C.c_uint64(77)
+    assert dll.ommxDebugGetPoisonedBytes(None, C.byref(untouched), C.byref(untouched)) == ot.INVALID_ARGUMENT and untouched.value == 77
+    lib.destroy_baker(b)
+
+
 def test_timings_struct_of_the_extension_header_matches_its_python_mirror():
     """ommxBakeTimings (include/omm_mi355x_ext.h) only ever grows at its end; ommxGetLastBakeTimingsSized reports the library's size of it, which must be
     the size of bench.py's ctypes mirror (a mirror that lags behind the header would read garbage through the unsized getter)."""

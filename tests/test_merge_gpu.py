@@ -68,9 +68,10 @@ def test_near_copies_at_every_level(dll, hip, baker, level, mixed):
 
 
 # ---- member lists ----
-def _bucket_source(level, members, samples, seed):
+def _bucket_source(level, members, samples, seed, distinct=False):
     """one family per entry of `members`: a base whose sampled fields spell the family's number, and members that differ from it in one field that is
-    not sampled in round 0 -> (blocks in memory order, the family of each block)"""
+    not sampled in round 0 -> (blocks in memory order, the family of each block).  distinct: no two members of a family are equal (draws that repeat
+    an earlier member are drawn again; a family then holds at most 1 + 3 * (4^level - samples) blocks)"""
     at = [gu.pos(seed, level, 0, j) for j in range(samples)]
     assert len(set(at)) == samples
     free = [f for f in range(4 ** level) if f not in at]
@@ -82,10 +83,15 @@ def _bucket_source(level, members, samples, seed):
             base[p] = (k >> (2 * j)) & 3
         blocks.append((base, level, 2))
         family.append(k)
-        for _ in range(m):
+        seen = {base.tobytes()}
+        assert not distinct or m <= 3 * len(free)
+        while len(seen) <= m:
             s = base.copy()
             f = free[int(rng.integers(0, len(free)))]
             s[f] = (s[f] + int(rng.integers(1, 4))) & 3
+            if distinct and s.tobytes() in seen:
+                continue
+            seen.add(s.tobytes() if distinct else len(seen))
             blocks.append((s, level, 2))
             family.append(k)
     return blocks, family

@@ -102,19 +102,15 @@ def outputs_of(im, names=("stateCounts", "referenceCounts", "knownFraction")):
     return o
 
 
-@pytest.mark.parametrize("index_format", [ot.IDX_U8, ot.IDX_U16, ot.IDX_U32])
-def test_hand_built_table(dll, hip, baker, index_format):
-    """well-formed blocks of levels 0 - 3 in both formats at odd offsets, a level-7 block across byte 16384 of the array, a level-9 block of several
-    segments; descriptors that fail the bounds rule (level 13, formats 0 and 3, a block ending one byte past arrayDataSize), which get zero counts and
-    whose primitives are skipped; the four specials, -5 and descArrayCount; blocks referenced 0, 1 and 3 times"""
-    array_data, descs, index, areas = su.table_arrays()
+def table_and_check(dll, hip, baker, index_format, array_data, descs, index, areas, stream=None):
+    """one call with every output on hand-built arrays in an Image, against stats_util.reference_stats: the eight integers, the skipped count, the three
+    arrays byte for byte, the metric within an ulp, and nothing written outside the outputs -> the reference's answer"""
     ref = su.reference_stats(array_data, descs, index, areas)
-    assert ref["skipped"] == 8 and ref["refs"][0] == 3 and ref["refs"][8] == 1 and ref["refs"][7] == 0 and not ref["state_counts"][su.TABLE_WELL_FORMED:].any()
     im, rd, _ = table_image(hip, index_format, array_data, descs, index, areas)
     try:
         st, skipped = ot.DebugStats(), C.c_uint32(12345)
         o = outputs_of(im)
-        assert dll.ommxDebugGetStatsDevice(baker, C.byref(rd), im.ptr("areas"), C.byref(o), C.byref(st), C.byref(skipped), None) == ot.SUCCESS
+        assert dll.ommxDebugGetStatsDevice(baker, C.byref(rd), im.ptr("areas"), C.byref(o), C.byref(st), C.byref(skipped), stream) == ot.SUCCESS
         im.download()
         got = su.int_fields(st)
         print("fields", got, "skipped", skipped.value, "metric %r (reference %r)" % (st.knownAreaMetric, float(ref["metric"])))
@@ -127,6 +123,17 @@ def test_hand_built_table(dll, hip, baker, index_format):
         im.assert_only_outputs_changed()
     finally:
         im.free()
+    return ref
+
+
+@pytest.mark.parametrize("index_format", [ot.IDX_U8, ot.IDX_U16, ot.IDX_U32])
+def test_hand_built_table(dll, hip, baker, index_format):
+    """well-formed blocks of levels 0 - 3 in both formats at odd offsets, a level-7 block across byte 16384 of the array, a level-9 block of several
+    segments; descriptors that fail the bounds rule (level 13, formats 0 and 3, a block ending one byte past arrayDataSize), which get zero counts and
+    whose primitives are skipped; the four specials, -5 and descArrayCount; blocks referenced 0, 1 and 3 times"""
+    array_data, descs, index, areas = su.table_arrays()
+    ref = table_and_check(dll, hip, baker, index_format, array_data, descs, index, areas)
+    assert ref["skipped"] == 8 and ref["refs"][0] == 3 and ref["refs"][8] == 1 and ref["refs"][7] == 0 and not ref["state_counts"][su.TABLE_WELL_FORMED:].any()
 
 
 @pytest.mark.parametrize("references", [300, 600])
