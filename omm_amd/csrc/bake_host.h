@@ -1,11 +1,12 @@
 // bake_host.h -- the host-side rules of a bake that need no device: flag bits, index formats, the raw triangle upload, histogram lists, the result descriptor
 // the carve of the working set, and the decisions and layouts of bake_core's stages that follow from a bake's counters alone (rank ranges, streamed result or
-// not, deferred generic pass, the states arena, the read-back slots).  Plain C++ (no HIP): omm_host.cpp calls each directly, tests/native/bake_host_check.cpp
+// not, deferred generic pass, the states arena, the read-back slots) and of the sharded bake (stride, chunks, exchange arena, host scatter).  Plain C++ (no HIP): omm_host.cpp calls each directly, tests/native/bake_host_check.cpp
 // runs them under sanitizers.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 #include "../../include/omm_mi355x.h"
 
 namespace ommx {
@@ -205,6 +206,73 @@ inline uint32_t interleave_stride(uint32_t cnt)
     auto gcd = [](uint32_t x, uint32_t y) { while (y) { const uint32_t t = x % y; x = y; y = t; } return x; };
     while (gcd(stride, cnt) != 1) ++stride;
     return stride % cnt;
+}
+
+// ---- the sharded bake's rules (omm_host.cpp: "multi-GPU sharded bake") ----
+inline bool rank_in_world(uint32_t rank, uint32_t worldSize) { return worldSize >= 1 && worldSize <= kBakeMaxRanks && rank < worldSize; }
+// bytes between the ranks' contributions in a gathered buffer: the largest of the per-rank totals, padded to 256, never 0
+inline uint64_t contribution_stride(const uint64_t* totals, uint32_t world)
+{
+    uint64_t mx = 0; for (uint32_t r = 0; r < world; ++r) mx = totals[r] > mx ? totals[r] : mx;
+    const uint64_t stride = (mx + 255) & ~255ull;
+    return stride ? stride : 256;
+}
+// The all-gather of the block contributions moves in chunks of <= 64 MiB per rank (at most 8 chunks, multiples of 256 bytes), so that the scatter of one
+// chunk overlaps the transfer of the next.  knob: ommxBakerKnob_ShardChunkBytes overrides the chunk size (tests use tiny chunks to force blocks across
+// chunk boundaries); 0 = unset.
+constexpr uint64_t kShardChunkBytes = 64ull << 20, kShardMaxChunks = 8;
+inline uint64_t shard_chunk_bytes(uint64_t strideBytes, uint64_t knob)
+{
+    const uint64_t want = knob ? knob : kShardChunkBytes;
+    uint64_t chunks = (strideBytes + want - 1) / want; if (chunks > kShardMaxChunks) chunks = kShardMaxChunks; if (chunks < 1) chunks = 1;
+    return ((((strideBytes + chunks - 1) / chunks) + 255) & ~255ull);
+}
+// the chunks [lo, hi) of [0, strideBytes) in order: `for (ShardChunks w(stride, knob); w.next();)`; a block that straddles a boundary is placed in pieces
+struct ShardChunks {
+    uint64_t strideBytes, chunkBytes, lo = 0, hi = 0;
+    ShardChunks(uint64_t strideBytes_, uint64_t knob) : strideBytes(strideBytes_), chunkBytes(shard_chunk_bytes(strideBytes_, knob)) {}
+    bool next() { lo = hi; hi = lo + chunkBytes < strideBytes ? lo + chunkBytes : strideBytes; return lo < hi; }   // false: the first empty chunk
+};
+// The exchange arena of a sharded bake: this rank's contribution, and for the one-call form (async) the gather staging of all ranks' raw chunks, this rank's
+// codec stream of at most half the contribution, the gathered streams, the stream's size word and the codec's count / scan scratch (it grows with the
+// contribution -- a word per 4 KiB of it plus rocPRIM's -- while the bake's own scratch is sized from the triangle count: a few large blocks need more).
+// Sized and carved by ONE traversal, like the tables above; `bytes` includes a slack of 256 bytes (async: 1 KiB) behind the last slot.
+struct ExchangeArena {
+    uint8_t *contrib, *gathered, *comp, *gatherComp; uint32_t* compSize; uint8_t* codecScratch;   // all but contrib: null in the synchronous form
+    size_t compCap, codecScratchBytes;   // of comp (gatherComp: x world), of codecScratch
+    size_t bytes;                        // to reserve, from the base
+};
+inline ExchangeArena carve_exchange_arena(uintptr_t base, uint64_t strideBytes, uint32_t world, bool async, size_t codecScratchWanted)
+{
+    ExchangeArena x = ExchangeArena(); CarveCursor c{ base };
+    x.contrib = c.take<uint8_t>((size_t)strideBytes);
+    if (async) {
+        x.compCap = pad256((size_t)(strideBytes / 2) + 4096); x.codecScratchBytes = pad256(codecScratchWanted);
+        x.gathered = c.take<uint8_t>((size_t)strideBytes * world + 4096);
+        x.comp = c.take<uint8_t>(x.compCap); x.gatherComp = c.take<uint8_t>(x.compCap * world);
+        x.compSize = c.take<uint32_t>(1); x.codecScratch = c.take<uint8_t>(x.codecScratchBytes);
+    }
+    x.bytes = (size_t)(c.at - base) + (async ? 1024 : 256);
+    return x;
+}
+// rank r's share [lo, hi) of the `words` metadata words that N ranks sum through host memory (ommCpuBake over several devices)
+inline void meta_sum_share(size_t words, uint32_t r, uint32_t N, size_t* lo, size_t* hi) { *lo = words * r / N; *hi = words * (r + 1) / N; }
+// what a rank of that bake sends over its link: its codec stream, or -- when the stream did not shrink below `cap`, or holds no more than its `offRaw`
+// bytes of tables -- the blocks of its contribution as they are
+struct RankSend { bool raw; uint64_t bytes; };
+inline RankSend rank_send(uint64_t streamBytes, uint64_t cap, uint64_t offRaw, uint64_t contributionBytes)
+{
+    const bool raw = streamBytes > cap || streamBytes < offRaw;
+    return RankSend{ raw, raw ? contributionBytes : streamBytes };
+}
+// the host scatter's ranges of OMMs for the helper threads: range t = [cut[t], cut[t + 1]), each of at least 2 MiB of blocks but the last; first cut 0, last cut E
+constexpr uint64_t kScatterRangeBytes = 2ull << 20;
+inline std::vector<uint32_t> scatter_cuts(const uint32_t* sizes, uint32_t E)
+{
+    std::vector<uint32_t> cut; cut.push_back(0);
+    uint64_t acc = 0; for (uint32_t j = 0; j < E; ++j) { acc += sizes[j]; if (acc >= kScatterRangeBytes) { cut.push_back(j + 1); acc = 0; } }
+    if (cut.back() != E) cut.push_back(E);
+    return cut;
 }
 
 // ---- the states arena of a bake: packed states of the active items | queue of open tiles | its control words | staging copy of a streamed result |

@@ -640,6 +640,15 @@ bool is_pow2(int x) { return x > 0 && !(x & (x - 1)); }
 
 #define HIP_OK(call) ((call) == hipSuccess)
 
+// HIP events without timing, destroyed with the scope: declared in the scope that holds the last wait on them.  create(count): `count` events in all.
+template <uint32_t N> struct EventList {
+    hipEvent_t ev[N]; uint32_t n = 0;
+    EventList() = default;
+    EventList(const EventList&) = delete; EventList& operator=(const EventList&) = delete;
+    bool create(uint32_t count) { while (n < count && n < N && HIP_OK(hipEventCreateWithFlags(&ev[n], hipEventDisableTiming))) ++n; return n == count; }
+    ~EventList() { for (uint32_t k = 0; k < n; ++k) (void)hipEventDestroy(ev[k]); }
+};
+
 uint32_t device_cu_count() // of the current device; sizes the persistent classification grid
 {
     static std::mutex mu; static int cached[64]; static bool have[64];
@@ -685,8 +694,7 @@ struct ShardCtx {
     bool mergeStates = false;   // host-tail bakes: the packed states are zeroed first so that a SUM all-reduce over them is a merge
     int ev[5] = { -1, -1, -1, -1, -1 };   // HIP event marks of Begin: setup | triage | classify | digest
     // exchange buffers: carved from the session's arenas (tables: tab.meta .. tab.totals; xchg: contribution + gather staging), nothing to free
-    uint8_t *dContrib = nullptr, *dGathered = nullptr;
-    uint8_t *dComp = nullptr, *dGatherComp = nullptr, *dCodecScratch = nullptr; uint32_t* dCompSize = nullptr; uint64_t compCap = 0; size_t codecScratchBytes = 0;   // block exchange codec (RCCL path): own stream, all ranks' streams, own size word, count / scan scratch
+    ExchangeArena x = ExchangeArena();   // contribution | RCCL path: gather staging, block exchange codec (own stream, all ranks' streams, own size word, count / scan scratch)
     uint64_t totals[kMaxRanks]; uint64_t strideBytes = 0;
 };
 
@@ -837,7 +845,7 @@ struct BakeRun;
 // The streamed-result protocol (StreamOut above): the events behind the classification launches, what the hooks behind those launches need, the preview, the
 // loop that sends what each launch placed, and the comparison with the tail's exact layout.  The hooks point into `sc`: it outlives launch_classify.
 struct StreamRun {
-    struct EventList { hipEvent_t ev[2 * kMaxClassifyChunks + 3]; uint32_t n = 0; ~EventList() { for (uint32_t k = 0; k < n; ++k) (void)hipEventDestroy(ev[k]); } } events;   // range placed [K + 1] | fences [K + 2]
+    EventList<2 * kMaxClassifyChunks + 3> events;   // range placed [K + 1] | fences [K + 2]
     StreamCtx sc;
     uint64_t sent = 0;        // bytes of the staging copy that are on their way to the caller's array
     int pv0 = -1, pv1 = -1;   // HIP event marks around the preview
@@ -1183,7 +1191,7 @@ ommResult StreamRun::begin(BakeRun& b)
     ClassifyChunks& cc = b.cc;
     bool oks = HIP_OK(hipMemsetAsync(tab.placed, 0xFF, (size_t)b.maxItems * 8, stream)) && HIP_OK(hipMemsetAsync(tab.cursor, 0, 8, stream)) && HIP_OK(hipMemsetAsync(tab.streamCtl, 0, sizeof(uint32_t) * kStreamCtlWords, stream));
     oks = oks && HIP_OK(run_stream_begin(tab.activeIds, numActive, tab.uv, tab.level, tab.scratch, tab.scratchBytes, stream));
-    for (uint32_t k = 0; oks && k < 2u * streamChunks + 3u; ++k) { oks = HIP_OK(hipEventCreateWithFlags(&events.ev[k], hipEventDisableTiming)); events.n += oks ? 1u : 0u; }
+    oks = oks && events.create(2u * streamChunks + 3u);
     if (!oks) return b.L.failure("[Failure] - could not set up the streamed result");
     sc.stream = stream; sc.place = b.so->placeStream; sc.fences = events.ev + streamChunks + 1u; sc.activeIds = tab.activeIds; sc.numActive = numActive; sc.scratch = tab.scratch; sc.scratchBytes = tab.scratchBytes; sc.digests = tab.digests;
     sc.cursor = tab.cursor; sc.stage = b.st.stage; sc.placed = tab.placed; sc.ctl = tab.streamCtl; sc.hostCursor = b.hCursor; sc.events = events.ev; sc.numEvents = streamChunks + 1u; sc.recorded = 0; sc.ok = true;
@@ -1341,6 +1349,19 @@ struct DeviceBakeResult {
     ommCpuOpacityMicromapUsageCount arrayHist[2 * kNumLevels], indexHist[2 * kNumLevels];
     ommCpuBakeResultDesc desc;
 };
+// The one maker of a DeviceBakeResult handle and its owner until release(): a handle that is given up -- give_up(), or the scope is left -- is destroyed only
+// after `drain` is idle (pooled blocks go back only when the stream is idle).  A null `drain`: the scope has drained the stream by other means.
+struct DeviceResultOwner {
+    Allocator mem; hipStream_t drain; DeviceBakeResult* p;
+    DeviceResultOwner(const Allocator& mem_, hipStream_t drain_, DeviceBakeResult* adopted = nullptr) : mem(mem_), drain(drain_), p(adopted) {}
+    DeviceResultOwner(const DeviceResultOwner&) = delete; DeviceResultOwner& operator=(const DeviceResultOwner&) = delete;
+    ~DeviceResultOwner() { give_up(); }
+    bool make() { p = mem.make<DeviceBakeResult>(); if (p) { p->mem = mem; memset(&p->desc, 0, sizeof p->desc); } return p != nullptr; }
+    void give_up() { if (!p) return; if (drain) (void)hipStreamSynchronize(drain); mem.destroy(p); p = nullptr; }
+    DeviceBakeResult* release() { DeviceBakeResult* r = p; p = nullptr; return r; }
+    DeviceBakeResult* operator->() const { return p; }
+    explicit operator bool() const { return p != nullptr; }
+};
 // histogram lists and descriptor of a device-resident result whose arrays and R.hist are complete (ommxBakeDevice, the sharded bake's phase 3)
 void finish_device_result(DeviceBakeResult* res)
 {
@@ -1405,9 +1426,9 @@ ommResult check_source_arrays(const Logger& log, const ommCpuBakeResultDesc* con
 struct DerivedResult {
     Baker& b; hipStream_t stream;
     const char *noun, *work;                          // in a message: the new result ("coarsened", "combined", "gathered"), the operation ("coarsening", "combine", "gather")
-    DeviceBakeResult* res = nullptr;                  // stays null when the caller wants the info only
+    DeviceResultOwner res;                            // stays null when the caller wants the info only
     uint32_t hist[2 * kRebuildHist];                  // array | index by (level, format - 1): the operation's last stage fills it
-    DerivedResult(Baker& b_, hipStream_t stream_, const char* noun_, const char* work_) : b(b_), stream(stream_), noun(noun_), work(work_) { memset(hist, 0, sizeof hist); }
+    DerivedResult(Baker& b_, hipStream_t stream_, const char* noun_, const char* work_) : b(b_), stream(stream_), noun(noun_), work(work_), res(b_.mem, stream_) { memset(hist, 0, sizeof hist); }
     ommResult failure(const char* format, const char* word) { char buf[160]; snprintf(buf, sizeof buf, format, word); return b.log.failure(buf); }
     ommResult failure(const char* format) { return failure(format, noun); }
     // scratch of the operation; false: it could not be had, and no_memory() is the answer
@@ -1440,14 +1461,11 @@ struct DerivedResult {
     }
     ommResult create(uint32_t numTris, ommIndexFormat indexFormat)
     {
-        res = b.mem.make<DeviceBakeResult>();
-        if (!res) return failure("[Failure] - the memory allocator returned null for the %s result");
-        res->mem = b.mem; memset(&res->desc, 0, sizeof res->desc);
+        if (!res.make()) return failure("[Failure] - the memory allocator returned null for the %s result");
         res->R.pool = b.devPool; res->R.numTris = numTris; res->R.indexFormat = indexFormat;
         return ommResult_SUCCESS;
     }
-    // (pooled blocks of a result that is given up go back only when the stream is idle)
-    ommResult give_up(ommResult code) { if (res) { (void)hipStreamSynchronize(stream); b.mem.destroy(res); res = nullptr; } return code; }
+    ommResult give_up(ommResult code) { res.give_up(); return code; }
     // judges the output's size; with a handle, allocates its three arrays
     ommResult allocate(const RebuildCounts& n)
     {
@@ -1473,7 +1491,7 @@ struct DerivedResult {
             }
         const DeviceResult& R = res->R;
         fill_result_desc(&res->desc, R.arrayData, R.arrayDataSize, R.descs, R.numDescs, R.index, R.numTris, R.indexFormat, res->arrayHist, nAH, res->indexHist, nIH);
-        *outResult = (ommxDeviceBakeResult)res;
+        *outResult = (ommxDeviceBakeResult)res.release();
     }
 };
 
@@ -1597,12 +1615,6 @@ struct HostResultGuard {
     }
     BakeResult* release() { BakeResult* p = r; r = nullptr; return p; }
 };
-// HIP events without timing, destroyed with the scope: declared in the scope that holds the last wait on them
-struct GpuEvents {
-    hipEvent_t ev[CodecSlicePlan::kSlices]; uint32_t n = 0;
-    bool create(uint32_t count) { while (n < count && n < CodecSlicePlan::kSlices && HIP_OK(hipEventCreateWithFlags(&ev[n], hipEventDisableTiming))) ++n; return n == count; }
-    ~GpuEvents() { for (uint32_t k = 0; k < n; ++k) (void)hipEventDestroy(ev[k]); }
-};
 struct ActiveBake { std::atomic<uint32_t>& n; explicit ActiveBake(std::atomic<uint32_t>& c) : n(c) { n.fetch_add(1); } ~ActiveBake() { n.fetch_sub(1); } };   // Baker::activeBakes
 
 // The host arrayData of an ommCpuBake result, and the block that is zeroed ahead for it.
@@ -1695,7 +1707,7 @@ bool copy_small_arrays(BakeResult* res, const ommCpuOpacityMicromapDesc* descs, 
 }
 // With a compressed result the small arrays cross the link on the second stream WHILE the helper threads expand the array: that stream waits for the device
 // result (an event behind everything on the bake's stream).  False: no second stream / no event -- the small arrays go in front of the wait, on the bake's stream.
-bool defer_small_arrays(BakeSession& ses, GpuEvents& resultEvent)
+bool defer_small_arrays(BakeSession& ses, EventList<1>& resultEvent)
 {
     if (!ses.open_comm() || !resultEvent.create(1)) return false;
     return HIP_OK(hipEventRecord(resultEvent.ev[0], ses.stream)) && HIP_OK(hipStreamWaitEvent(ses.commStream, resultEvent.ev[0], 0));
@@ -1760,7 +1772,7 @@ bool deliver_compressed(Baker& baker, BakeSession& ses, const CodecBlock& codec,
         memcpy(hStream, head.data(), head.size());
         const HostCodecLayout L = codec.L;
         const CodecSlicePlan plan = plan_codec_slices(L, (const uint32_t*)(hStream + L.offOfs), streamBytes);
-        GpuEvents evs;   // one per slice: on the host
+        EventList<kSlices> evs;   // one per slice: on the host
         ok = evs.create(kSlices) && plan.ok;
         for (uint32_t k = 0; ok && k < kSlices; ++k) {
             const CodecSlicePlan::Slice& s = plan.slice[k];
@@ -1919,7 +1931,7 @@ ommResult bake_impl(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult
     ok = ok && res->index != nullptr && res->triArea != nullptr;
     const size_t outIdx = index_bytes(R.indexFormat);
     // the small arrays: behind the expansion's back on the second stream with a compressed result (defer_small_arrays), otherwise here, in front of the wait
-    GpuEvents resultEvent;   // the device result is complete (everything in front of it on the bake's stream)
+    EventList<1> resultEvent;   // the device result is complete (everything in front of it on the bake's stream)
     const bool deferSmall = ok && codec.on && defer_small_arrays(ses, resultEvent);
     if (ok && !deferSmall) ok = copy_small_arrays(res, R.descs, R.index, R.triAreaScratch, E, T, outIdx, stream);
     const int d1 = et.mark();
@@ -2461,9 +2473,8 @@ OMM_MI355X_API ommResult ommxBakeDevice(ommBaker baker, const ommCpuBakeInputDes
     const DeviceScope onBakersDevice(b->bind_device());
     BakeSession ses(*b);
     if (!ses.open()) return b->log.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)");
-    DeviceBakeResult* res = b->mem.make<DeviceBakeResult>();
-    if (!res) return ommResult_FAILURE;
-    res->mem = b->mem; memset(&res->desc, 0, sizeof res->desc);
+    DeviceResultOwner res(b->mem, ses.stream);
+    if (!res.make()) return ommResult_FAILURE;
     EventTimer et(ses.stream);
     ommxBakeTimings tm; memset(&tm, 0, sizeof tm);
     DeviceInputs din; din.texCoords = desc->texCoords; din.indices = desc->indexBuffer; din.perTriLevels = desc->subdivisionLevels;
@@ -2473,21 +2484,21 @@ OMM_MI355X_API ommResult ommxBakeDevice(ommBaker baker, const ommCpuBakeInputDes
         ommResult hr = bake_core(*b, *desc, din, ses.arena, ses.states, ses.stream, et, scratchR, tm, nullptr, &ht);
         HostTailResult hres; ommIndexFormat ifmt = ommIndexFormat_UINT_32;
         if (hr == ommResult_SUCCESS) hr = run_host_tail_for(*desc, desc->indexCount / 3u, ht.items, hres, ifmt);
-        if (hr == ommResult_SUCCESS) hr = upload_host_tail(*b, hres, ifmt, desc->indexCount / 3u, (int)desc->format, ses.stream, res);
+        if (hr == ommResult_SUCCESS) hr = upload_host_tail(*b, hres, ifmt, desc->indexCount / 3u, (int)desc->format, ses.stream, res.p);
         if (hr == ommResult_SUCCESS && !keep_tri_areas(res->R, scratchR.triAreaScratch, desc->indexCount / 3u, ses.stream)) hr = b->log.failure("[Failure] - could not keep the triangle areas on the device");
-        if (hr != ommResult_SUCCESS) { (void)hipStreamSynchronize(ses.stream); b->mem.destroy(res); return hr; }
+        if (hr != ommResult_SUCCESS) return hr;
         tm.totalMs = (float)(now_ms() - t0);
         store_timings(*b, tm);
-        *outResult = (ommxDeviceBakeResult)res;
+        *outResult = (ommxDeviceBakeResult)res.release();
         return ommResult_SUCCESS;
     }
     r = bake_core(*b, *desc, din, ses.arena, ses.states, ses.stream, et, res->R, tm);
     if (r == ommResult_SUCCESS && !keep_tri_areas(res->R, res->R.triAreaScratch, desc->indexCount / 3u, ses.stream)) r = b->log.failure("[Failure] - could not keep the triangle areas on the device");
-    if (r != ommResult_SUCCESS) { (void)hipStreamSynchronize(ses.stream); b->mem.destroy(res); return r; } // (pooled blocks go back only when the stream is idle)
-    finish_device_result(res);
+    if (r != ommResult_SUCCESS) return r;
+    finish_device_result(res.p);
     tm.totalMs = (float)(now_ms() - t0);
     store_timings(*b, tm);
-    *outResult = (ommxDeviceBakeResult)res;
+    *outResult = (ommxDeviceBakeResult)res.release();
     return ommResult_SUCCESS;
     });
 }
@@ -2578,47 +2589,26 @@ void rccl_status_on_device(RcclComm* c, int device)
     rccl_prepare_status(c);   // (on the current device = `device`)
 }
 // A rank-local failure (out of memory, mostly) must not leave the other ranks waiting in the next collective: before every data collective each rank
-// contributes its status to a one-element MIN all-reduce and all of them go on, or none.  `stream`: the bake's stream (idle ranks: the communicator's own).
-bool rccl_agree(RcclComm* rc, hipStream_t stream, bool mineOk, const Logger& L, const char* stage)
+// contributes its status to a one-element all-reduce and all of them go on, or none.  The one routine behind both forms:
+//   plain (dWord null)   MIN over the ranks' status words; a rank that has no bake stream (null) uses the communicator's own
+//   carrying a number    MAX over the device words *dWord, 0xFFFFFFFF written there only if this rank failed; *outMax = the largest one
+// false = a rank failed (this one or another).
+bool rccl_agree(RcclComm* rc, hipStream_t stream, bool mineOk, const Logger& L, const char* stage, uint32_t* dWord = nullptr, uint32_t* outMax = nullptr)
 {
+    const bool carries = dWord != nullptr;
     bool ok = true;
     if (!rc->dStatus) ok = HIP_OK(hipMalloc((void**)&rc->dStatus, 2 * sizeof(uint32_t)));
-    if (ok && !stream) { if (!rc->statusStream) ok = HIP_OK(hipStreamCreateWithFlags(&rc->statusStream, hipStreamNonBlocking)); stream = rc->statusStream; }
+    if (ok && !carries && !stream) { if (!rc->statusStream) ok = HIP_OK(hipStreamCreateWithFlags(&rc->statusStream, hipStreamNonBlocking)); stream = rc->statusStream; }
     if (!ok) { (void)hipGetLastError(); L.failure("[Failure] - sharded bake: no device memory for the status word (the other ranks may be waiting in a collective)"); return false; }
-    const uint32_t mine = mineOk ? 1u : 0u; uint32_t all = 0;
-    ok = HIP_OK(hipMemcpyAsync(rc->dStatus, &mine, sizeof mine, hipMemcpyHostToDevice, stream)) && HIP_OK(hipStreamSynchronize(stream));
-    ok = ok && rc->all_reduce(rc->dStatus, rc->dStatus + 1, 1, kRcclMin, stream) == 0;
-    ok = ok && HIP_OK(hipMemcpyAsync(&all, rc->dStatus + 1, sizeof all, hipMemcpyDeviceToHost, stream)) && HIP_OK(hipStreamSynchronize(stream));
-    if (!ok) { L.failure("[Failure] - sharded bake: the status all-reduce failed"); return false; }
-    if (mineOk && all == 0u) { char buf[200]; snprintf(buf, sizeof buf, "[Failure] - sharded bake: another rank failed (%s); this rank stops with it", stage); L.failure(buf); }
-    return mineOk && all != 0u;
-}
-// The same agreement carrying a number: every rank contributes the device word *dWord (0xFFFFFFFF if it failed) to a MAX all-reduce; *outMax = the
-// largest one.  false = a rank failed (this one or another).
-bool rccl_agree_max(RcclComm* rc, hipStream_t stream, bool mineOk, uint32_t* dWord, uint32_t* outMax, const Logger& L, const char* stage)
-{
-    bool ok = true;
-    if (!rc->dStatus) ok = HIP_OK(hipMalloc((void**)&rc->dStatus, 2 * sizeof(uint32_t)));
-    if (!ok) { (void)hipGetLastError(); L.failure("[Failure] - sharded bake: no device memory for the status word (the other ranks may be waiting in a collective)"); return false; }
-    const uint32_t failed = 0xFFFFFFFFu; uint32_t all = failed;
-    if (!mineOk) ok = HIP_OK(hipMemcpyAsync(dWord, &failed, sizeof failed, hipMemcpyHostToDevice, stream)) && HIP_OK(hipStreamSynchronize(stream));
-    ok = ok && rc->all_reduce(dWord, rc->dStatus + 1, 1, kRcclMax, stream) == 0;
+    uint32_t* const dMine = carries ? dWord : rc->dStatus;
+    const uint32_t failed = carries ? 0xFFFFFFFFu : 0u, mine = mineOk ? 1u : failed; uint32_t all = failed;
+    if (!carries || !mineOk) ok = HIP_OK(hipMemcpyAsync(dMine, &mine, sizeof mine, hipMemcpyHostToDevice, stream)) && HIP_OK(hipStreamSynchronize(stream));
+    ok = ok && rc->all_reduce(dMine, rc->dStatus + 1, 1, carries ? kRcclMax : kRcclMin, stream) == 0;
     ok = ok && HIP_OK(hipMemcpyAsync(&all, rc->dStatus + 1, sizeof all, hipMemcpyDeviceToHost, stream)) && HIP_OK(hipStreamSynchronize(stream));
     if (!ok) { L.failure("[Failure] - sharded bake: the status all-reduce failed"); return false; }
     if (mineOk && all == failed) { char buf[200]; snprintf(buf, sizeof buf, "[Failure] - sharded bake: another rank failed (%s); this rank stops with it", stage); L.failure(buf); }
-    *outMax = all;
+    if (outMax) *outMax = all;
     return mineOk && all != failed;
-}
-
-// The all-gather of the block contributions moves in chunks of <= 64 MiB per rank (at most 8 chunks, multiples of 256 bytes), so that the
-// scatter of one chunk overlaps the transfer of the next.  ommxBakerKnob_ShardChunkBytes overrides the chunk size (tests use tiny chunks to
-// force blocks across chunk boundaries).
-uint64_t shard_chunk_bytes(const Baker& b, uint64_t strideBytes)
-{
-    uint64_t want = 64ull << 20;
-    if (const uint64_t v = b.knob(ommxBakerKnob_ShardChunkBytes)) want = v;
-    uint64_t chunks = (strideBytes + want - 1) / want; if (chunks > 8) chunks = 8; if (chunks < 1) chunks = 1;
-    return ((((strideBytes + chunks - 1) / chunks) + 255) & ~255ull);
 }
 
 ommResult sharded_checks(ommBaker baker, const ommCpuBakeInputDesc* desc, Baker** outB, bool hostTailOk)
@@ -2657,24 +2647,37 @@ ommResult sharded_tail(ShardedBake* sb)
     if (c.counts.arrayDataSize > 0xFFFFFFFFull) return ommResult_FAILURE; // bake_cpu_impl.cpp:1774-1775
     if (!HIP_OK(run_shard_layout(c.to.order, c.to.sizes, c.tab.active, c.tab.owner, c.counts.numOmms, c.world, c.tab.cofs, c.tab.totals, c.totals, c.tab.scratch, c.tab.scratchBytes, stream)))
         return L.failure("[Failure] - sharded layout failed");
-    uint64_t mx = 0; for (uint32_t r = 0; r < c.world; ++r) mx = c.totals[r] > mx ? c.totals[r] : mx;
-    c.strideBytes = (mx + 255) & ~255ull; if (c.strideBytes == 0) c.strideBytes = 256;
-    // contribution + (for the RCCL path) the gather staging of all ranks: one grow-only block of the session's working set
-    const size_t gatherBytes = c.asyncBegin ? (size_t)c.strideBytes * c.world + 4096 : 0;
-    // (RCCL path) the contributions cross the links as codec streams of at most half their size: this rank's and the gathered ones
-    c.compCap = c.asyncBegin ? pad256((size_t)(c.strideBytes / 2) + 4096) : 0;
-    // (the codec's count / scan scratch grows with the contribution -- one word per 4 KiB of it plus rocPRIM's -- while the bake's own scratch block is sized
-    //  from the triangle count: a few large blocks, level 10 and up, need more than that, so it comes from this arena)
-    c.codecScratchBytes = c.asyncBegin ? pad256(shard_codec_scratch_bytes(c.strideBytes)) : 0;
-    const size_t codecBytes = c.asyncBegin ? (size_t)c.compCap * (c.world + 1) + 1024 + c.codecScratchBytes : 0;
-    if (!sb->ses.set->xchg.reserve((size_t)c.strideBytes + 256 + gatherBytes + codecBytes, *sb->baker->devPool->poison)) return L.failure("[Failure] - out of device memory for the shard contribution");
-    c.dContrib = sb->ses.set->xchg.take<uint8_t>((size_t)c.strideBytes);
-    c.dGathered = gatherBytes ? sb->ses.set->xchg.take<uint8_t>(gatherBytes) : nullptr;
-    if (codecBytes) { c.dComp = sb->ses.set->xchg.take<uint8_t>((size_t)c.compCap); c.dGatherComp = sb->ses.set->xchg.take<uint8_t>((size_t)c.compCap * c.world); c.dCompSize = sb->ses.set->xchg.take<uint32_t>(1); c.dCodecScratch = sb->ses.set->xchg.take<uint8_t>(c.codecScratchBytes); }
+    c.strideBytes = contribution_stride(c.totals, c.world);
+    // the exchange buffers: one grow-only block of the session's working set, size and pointers from the same traversal (bake_host.h)
+    DeviceArena& xchg = sb->ses.set->xchg;
+    const size_t codecScratch = c.asyncBegin ? shard_codec_scratch_bytes(c.strideBytes) : 0;
+    if (!xchg.reserve(carve_exchange_arena(0, c.strideBytes, c.world, c.asyncBegin, codecScratch).bytes, *sb->baker->devPool->poison)) return L.failure("[Failure] - out of device memory for the shard contribution");
+    c.x = carve_exchange_arena((uintptr_t)xchg.base, c.strideBytes, c.world, c.asyncBegin, codecScratch);
     // (the padding behind this rank's blocks travels too: zeros, which the codec folds away)
-    if (c.strideBytes > c.totals[c.rank] && !HIP_OK(hipMemsetAsync(c.dContrib + c.totals[c.rank], 0, (size_t)(c.strideBytes - c.totals[c.rank]), stream))) return L.failure("[Failure] - device memset failed");
-    launch_shard_gather(c.dStates, c.tab.stateOfs, c.tab.active, c.tab.owner, c.rank, c.to.order, c.tab.cofs, c.to.sizes, c.counts.numOmms, c.dContrib, stream);
+    if (c.strideBytes > c.totals[c.rank] && !HIP_OK(hipMemsetAsync(c.x.contrib + c.totals[c.rank], 0, (size_t)(c.strideBytes - c.totals[c.rank]), stream))) return L.failure("[Failure] - device memset failed");
+    launch_shard_gather(c.dStates, c.tab.stateOfs, c.tab.active, c.tab.owner, c.rank, c.to.order, c.tab.cofs, c.to.sizes, c.counts.numOmms, c.x.contrib, stream);
     return HIP_OK(hipGetLastError()) ? ommResult_SUCCESS : L.failure("[Failure] - shard gather failed");
+}
+
+// The timings of a sharded bake once its stream has been synchronised (Begin may have returned without that): the event marks of the begin phase as
+// times -- the host-tail form has no digest pass of its own to time --, the total, and the whole to the baker.
+void store_begin_timings(ShardedBake* sb, bool withDigest)
+{
+    const int* e = sb->ctx.ev; const EventTimer& et = *sb->et; ommxBakeTimings& tm = sb->tm;
+    tm.setupMs = et.ms(e[0], e[1]); tm.triageMs = et.ms(e[1], e[2]); tm.classifyMs = et.ms(e[2], e[3]);
+    if (withDigest) tm.digestMs = et.ms(e[3], e[4]);
+    tm.totalMs = (float)(now_ms() - sb->t0);
+    store_timings(*sb->baker, tm);
+}
+// the gathered blocks to their final offsets in arrayData: bytes [lo, hi) of every rank's contribution, from `src` (byte lo of rank 0; rank r `pitch` bytes behind rank r - 1) ...
+void shard_scatter(const ShardCtx& c, const uint8_t* src, uint64_t pitch, uint64_t lo, uint64_t hi, uint8_t* arrayData, hipStream_t stream)
+{
+    launch_shard_scatter(src, pitch, lo, hi, c.tab.active, c.tab.owner, c.tab.mask, c.tab.level, c.bits, c.to.order, c.tab.cofs, c.to.dstOfs, c.to.sizes, c.counts.numOmms, arrayData, stream);
+}
+// ... or every block straight from its owner's codec stream of `sendBytes` among the gathered ones (no expanded copy of the contributions)
+void shard_scatter_streams(const ShardCtx& c, size_t sendBytes, uint8_t* arrayData, hipStream_t stream)
+{
+    launch_shard_scatter_streams(c.x.gatherComp, sendBytes, c.strideBytes, c.tab.active, c.tab.owner, c.tab.mask, c.tab.level, c.bits, c.to.order, c.tab.cofs, c.to.dstOfs, c.to.sizes, c.counts.numOmms, arrayData, stream);
 }
 
 // phase 3: result buffers, descriptors, index buffer; `scatter` places the gathered blocks (one call or one per chunk)
@@ -2683,9 +2686,8 @@ ommResult sharded_finish(ShardedBake* sb, ScatterFn&& scatter, ommxDeviceBakeRes
 {
     ShardCtx& c = sb->ctx; Baker* b = sb->baker; const Logger& L = b->log; hipStream_t stream = sb->ses.stream;
     const uint32_t E = c.counts.numOmms, T = c.T;
-    DeviceBakeResult* res = b->mem.make<DeviceBakeResult>();
-    if (!res) return ommResult_FAILURE;
-    res->mem = b->mem; memset(&res->desc, 0, sizeof res->desc);
+    DeviceResultOwner res(b->mem, stream);
+    if (!res.make()) return ommResult_FAILURE;
     DeviceResult& R = res->R;
     R.pool = b->devPool;
     R.bits = c.bits; R.numDescs = E; R.arrayDataSize = E ? c.counts.arrayDataSize : 0; R.numTris = T;
@@ -2703,14 +2705,10 @@ ommResult sharded_finish(ShardedBake* sb, ScatterFn&& scatter, ommxDeviceBakeRes
     ok = ok && HIP_OK(hipMemcpyAsync(R.hist, c.tab.arrayHist, sizeof(uint32_t) * kNumLevels, hipMemcpyDeviceToHost, stream));
     ok = ok && HIP_OK(hipMemcpyAsync(R.hist + kNumLevels, c.tab.indexHist, sizeof(uint32_t) * kNumLevels, hipMemcpyDeviceToHost, stream));
     ok = ok && HIP_OK(hipStreamSynchronize(stream));
-    if (!ok) { (void)hipStreamSynchronize(stream); b->mem.destroy(res); return L.failure("[Failure] - could not materialise the merged bake result on the device"); }
-    finish_device_result(res);
-    // the bake's HIP events are complete now (Begin may have returned without synchronising)
-    const int* e = c.ev;
-    sb->tm.setupMs = sb->et->ms(e[0], e[1]); sb->tm.triageMs = sb->et->ms(e[1], e[2]); sb->tm.classifyMs = sb->et->ms(e[2], e[3]); sb->tm.digestMs = sb->et->ms(e[3], e[4]);
-    sb->tm.totalMs = (float)(now_ms() - sb->t0);
-    store_timings(*b, sb->tm);
-    *outResult = (ommxDeviceBakeResult)res;
+    if (!ok) return L.failure("[Failure] - could not materialise the merged bake result on the device");
+    finish_device_result(res.p);
+    store_begin_timings(sb, true);
+    *outResult = (ommxDeviceBakeResult)res.release();
     return ommResult_SUCCESS;
 }
 
@@ -2780,155 +2778,207 @@ Baker* peer_baker(Baker& b, uint32_t rank, int dev)
     return p;
 }
 
-ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult* out, uint32_t N)
-{
-    const Logger& L = baker.log;
-    const double t0 = now_ms();
-    const uint32_t T = d.indexCount / 3u;
-    const int primary = baker.bind_device();
-    int deviceCount = 0;
-    if (primary < 0 || !HIP_OK(hipGetDeviceCount(&deviceCount)) || deviceCount < 1) return L.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)");
-    if (N > (uint32_t)kMaxRanks) N = kMaxRanks;
-    Texture* tex0 = untag<Texture>(d.texture);
-    // ---- per rank: device, baker, texture (made before the threads start: replicas and shadow bakers are created once and kept) ----
+// rank 0's layout tables on the host: what the host scatter reads
+struct HostLayout { std::vector<uint32_t> order, dstOfs, sizes, mask; std::vector<uint64_t> cofs; std::vector<uint8_t> active, owner, level; };
+// One such bake: what its stages hand on, and the stages themselves in the order they run (bake_impl_multi below calls them).
+struct MultiBake {
     struct Rank {
         int dev = 0; Baker* baker = nullptr; Texture* tex = nullptr; ShardedBake* sb = nullptr; PoolBlock dRaw; CodecBlock codec;
         std::vector<uint32_t> meta; const uint8_t* hStream = nullptr; bool raw = false; ommResult status = ommResult_SUCCESS;
         // on the rank's device: the sharded bake first (its session drains the rank's streams), then the pooled blocks those streams used
         ~Rank() { const DeviceScope onDev(dev); if (sb) baker->mem.destroy(sb); dRaw.release(); codec.block.release(); }
     };
-    std::vector<Rank> ranks(N);
-    for (uint32_t r = 0; r < N; ++r) {
-        ranks[r].dev = (primary + (int)r) % deviceCount;
-        ranks[r].baker = peer_baker(baker, r, ranks[r].dev);
-        ranks[r].tex = texture_on_device(tex0, ranks[r].dev);
-        if (!ranks[r].baker || !ranks[r].tex) return L.failure("[Failure] - multi-device bake: could not set up a device (texture copy / memory)");
-    }
-    const RawInputLayout raw = raw_input_layout(d, T, max_index(d.indexBuffer, d.indexFormat, 3ull * T));
+    // ---- the call ----
+    Baker& baker; const ommCpuBakeInputDesc& d; const Logger& L; const uint32_t N, T; const double t0 = now_ms();
+    // ---- what the stages hand on ----
+    int primary = -1; std::vector<Rank> ranks; RawInputLayout raw;
+    RankTeam team; std::vector<uint32_t> metaSum; size_t metaWords = 0;   // the metadata words of the active items, summed across the ranks in host memory
+    HostCodecLayout layout{}; uint64_t strideBytes = 0;                   // of every rank's codec stream (rank 0's say)
+    double tA = 0;                                                        // the ranks are done
+    MultiBake(Baker& baker_, const ommCpuBakeInputDesc& d_, uint32_t devices)
+        : baker(baker_), d(d_), L(baker_.log), N(devices > (uint32_t)kMaxRanks ? (uint32_t)kMaxRanks : devices), T(d_.indexCount / 3u), ranks(N) { team.n = N; }
 
-    RankTeam team; team.n = N;
-    std::vector<uint32_t> metaSum; size_t metaWords = 0;
-    HostCodecLayout layout{}; uint64_t strideBytes = 0;
-    // phase A (all ranks): upload, share of the classification, metadata through the host, tail, own contribution as a codec stream on the host
-    auto body = [&](uint32_t r) {
-        Rank& R = ranks[r];
-        const DeviceScope onDev(R.dev);
+    // reads the baker's device and the texture; leaves per rank its device, baker and texture (made before the threads start: replicas and shadow bakers are created once and kept), the upload's layout
+    ommResult setup_ranks()
+    {
+        primary = baker.bind_device();
+        int deviceCount = 0;
+        if (primary < 0 || !HIP_OK(hipGetDeviceCount(&deviceCount)) || deviceCount < 1) return L.failure("[Failure] - no usable HIP device (the MI355X baker has no CPU fallback)");
+        Texture* tex0 = untag<Texture>(d.texture);
+        for (uint32_t r = 0; r < N; ++r) {
+            ranks[r].dev = (primary + (int)r) % deviceCount;
+            ranks[r].baker = peer_baker(baker, r, ranks[r].dev);
+            ranks[r].tex = texture_on_device(tex0, ranks[r].dev);
+            if (!ranks[r].baker || !ranks[r].tex) return L.failure("[Failure] - multi-device bake: could not set up a device (texture copy / memory)");
+        }
+        raw = raw_input_layout(d, T, max_index(d.indexBuffer, d.indexFormat, 3ull * T));
+        return ommResult_SUCCESS;
+    }
+    // reads the caller's triangle data; leaves it on the rank's device over the rank's own link, and R.sb with the rank's share classified (R.status)
+    bool upload_and_begin(Rank& R, uint32_t r)
+    {
         Baker& sub = *R.baker;
         (void)R.dRaw.acquire(sub.devPool.get(), raw.total);
         const DeviceInputs din = upload_raw_inputs(raw, d, R.dRaw.bytes(), nullptr);
-        bool ok = din.texCoords != nullptr;
+        if (din.texCoords == nullptr) { R.status = ommResult_FAILURE; return false; }
         ommCpuBakeInputDesc dd = d;
         dd.texture = (ommCpuTexture)((uintptr_t)R.tex | kTexture);
         dd.texCoords = din.texCoords; dd.indexBuffer = din.indices; dd.subdivisionLevels = din.perTriLevels;
-        if (ok) { R.status = sharded_begin(&sub, &dd, r, N, false, &R.sb); ok = R.status == ommResult_SUCCESS; if (!ok) R.sb = nullptr; }
-        else R.status = ommResult_FAILURE;
-        if (!team.barrier(ok)) return;
-        // ---- metadata of the active items (mask, known count, digest: 4 words each; zero outside a rank's share): summed across the ranks in host memory ----
-        ShardCtx& c = R.sb->ctx; hipStream_t stream = R.sb->ses.stream;
+        R.status = sharded_begin(&sub, &dd, r, N, false, &R.sb);
+        if (R.status != ommResult_SUCCESS) R.sb = nullptr;
+        return R.status == ommResult_SUCCESS;
+    }
+    // reads the rank's metadata words (mask, known count, digest: 4 words per active item; zero outside its share); leaves them in R.meta, rank 0 also the sum's size
+    bool meta_to_host(Rank& R, uint32_t r)
+    {
+        const ShardCtx& c = R.sb->ctx;
         const size_t words = 4ull * c.hc.activeStart[kNumLevels];
         R.meta.resize(words ? words : 1);
-        if (words) ok = HIP_OK(hipMemcpy(R.meta.data(), c.tab.meta, words * 4, hipMemcpyDeviceToHost));
         if (r == 0) { metaWords = words; metaSum.assign(words ? words : 1, 0u); }
-        if (!team.barrier(ok)) return;
-        if (!team.barrier(words == metaWords)) return;   // (every rank ran the same set-up: anything else is an internal error -- and nobody may read a shorter copy)
-        for (size_t k = metaWords * r / N; k < metaWords * (r + 1) / N; ++k) { uint32_t a = 0; for (uint32_t q = 0; q < N; ++q) a += ranks[q].meta[k]; metaSum[k] = a; }
-        if (!team.barrier(true)) return;
-        if (words) ok = HIP_OK(hipMemcpy(c.tab.meta, metaSum.data(), words * 4, hipMemcpyHostToDevice));
-        // ---- replicated tail, layout, this rank's blocks packed into its contribution ----
-        if (ok) { R.status = sharded_tail(R.sb); ok = R.status == ommResult_SUCCESS; }
-        // ---- the contribution as a codec stream, over this device's own link ----
-        const CodecBlock& cb = R.codec;
-        if (ok) ok = R.codec.reserve(sub.devPool.get(), c.strideBytes, false);   // (a multiple of 256 already: cb.padded is the stride)
-        uint64_t streamBytes = 0;
-        if (ok) {
-            uint8_t* dComp = cb.at.stream;
-            ok = cb.compress(c.dContrib, stream)
-              && HIP_OK(hipMemcpyAsync(&streamBytes, dComp, 8, hipMemcpyDeviceToHost, stream)) && HIP_OK(hipStreamSynchronize(stream));
-            R.raw = ok && (streamBytes > cb.cap || streamBytes < cb.L.offRaw);
-            const uint64_t take = R.raw ? c.totals[r] : streamBytes;
-            ok = ok && R.sb->ses.set->pinned.reserve((size_t)take + 4096);
-            if (ok && take) ok = HIP_OK(hipMemcpyAsync(R.sb->ses.set->pinned.base, R.raw ? c.dContrib : dComp, (size_t)take, hipMemcpyDeviceToHost, stream)) && HIP_OK(hipStreamSynchronize(stream));
-            R.hStream = R.sb->ses.set->pinned.base;
-        }
-        if (r == 0) { layout = cb.L; strideBytes = cb.padded; }
-        (void)team.barrier(ok);
-    };
-    // rank 0 is the calling thread; a rank whose thread cannot be started is run by the caller AFTER the others would deadlock the barriers: refuse instead
-    std::vector<std::thread> threads;
-    bool spawned = true;
-    // (nothing may leave a rank's thread: an exception -- std::bad_alloc of a host vector -- fails the rank and releases the others from their barriers)
-    auto guardedBody = [&](uint32_t r) { try { body(r); } catch (...) { ranks[r].status = ommResult_FAILURE; team.abort(); } };
-    try { threads.reserve(N); for (uint32_t r = 1; r < N; ++r) threads.emplace_back(guardedBody, r); } catch (...) { spawned = false; }
-    if (!spawned) {
-        team.abort();   // (threads that did start wait in the first barrier for ranks that never come)
-        for (auto& t : threads) t.join();
-        return L.failure("[Failure] - multi-device bake: could not start a thread per device");
+        return !words || HIP_OK(hipMemcpy(R.meta.data(), c.tab.meta, words * 4, hipMemcpyDeviceToHost));
     }
-    guardedBody(0);
-    for (auto& t : threads) t.join();
-    for (const Rank& R : ranks) if (R.status != ommResult_SUCCESS) return R.status;
-    for (const Rank& R : ranks) if (!R.sb || !R.hStream) return L.failure("[Failure] - multi-device bake: a device failed");
-    const double tA = now_ms();
-
-    // ---- rank 0: layout tables to the host, descriptors / index buffer / histograms, then the blocks from their owners' streams ----
-    const DeviceScope onPrimary(primary);
-    ShardedBake* sb0 = ranks[0].sb; ShardCtx& c0 = sb0->ctx; hipStream_t stream0 = sb0->ses.stream;
-    const uint32_t E = c0.counts.numOmms, U = c0.ti.numItems;
-    std::vector<uint32_t> hOrder(E ? E : 1), hDstOfs(E ? E : 1), hSizes(E ? E : 1), hMask(U ? U : 1); std::vector<uint64_t> hCofs(E ? E : 1);
-    std::vector<uint8_t> hActive(U ? U : 1), hOwner(U ? U : 1), hLevel(U ? U : 1);
-    // Asynchronous copies into the vectors above (and, further down, into the result's arrays) are queued on stream0: whatever way this function is left --
-    // a failed copy half way down a chain, an exception of a host container or of the thread pool -- the stream is drained BEFORE their memory is released
-    // (destructors run in reverse order of declaration: each guard is declared right behind the memory it protects).
-    const StreamDrain drainBeforeVectors{ stream0 };
-    bool ok = true;
-    if (E) ok = HIP_OK(hipMemcpyAsync(hOrder.data(), c0.to.order, (size_t)E * 4, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(hDstOfs.data(), c0.to.dstOfs, (size_t)E * 4, hipMemcpyDeviceToHost, stream0))
-              && HIP_OK(hipMemcpyAsync(hSizes.data(), c0.to.sizes, (size_t)E * 4, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(hCofs.data(), c0.tab.cofs, (size_t)E * 8, hipMemcpyDeviceToHost, stream0));
-    if (ok && U) ok = HIP_OK(hipMemcpyAsync(hActive.data(), c0.tab.active, U, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(hOwner.data(), c0.tab.owner, U, hipMemcpyDeviceToHost, stream0))
-                   && HIP_OK(hipMemcpyAsync(hLevel.data(), c0.tab.level, U, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(hMask.data(), c0.tab.mask, (size_t)U * 4, hipMemcpyDeviceToHost, stream0));
-    ommxDeviceBakeResult dres = nullptr;
-    if (ok) { const ommResult fr = sharded_finish(sb0, [](uint8_t*) { return true; }, &dres, false); if (fr != ommResult_SUCCESS) return fr; }   // (synchronises the stream: the copies above are complete)
-    if (!ok) return L.failure("[Failure] - device to host transfer of the bake result failed");
-    DeviceBakeResult* dr = (DeviceBakeResult*)dres;
-    struct DresGuard { Baker& b; DeviceBakeResult* p; ~DresGuard() { b.mem.destroy(p); } } dresGuard{ baker, dr };
-    DeviceResult& DR = dr->R;
-
-    HostResultGuard resGuard{ baker, baker.mem.make<BakeResult>(), nullptr };
-    BakeResult* const res = resGuard.r;
-    if (!res) return ommResult_FAILURE;
-    res->mem = baker.mem;
-    const StreamDrain drainBeforeResult{ stream0 };
-    if (E && baker.mem.alloc == default_alloc && baker.hostPool->wants((size_t)DR.arrayDataSize)) { res->arrayData = baker.hostPool->acquire((size_t)DR.arrayDataSize); if (res->arrayData) res->pool = baker.hostPool; }
-    if (alloc_host_result(baker, res, E, (size_t)DR.arrayDataSize, T) != ommResult_SUCCESS) return ommResult_FAILURE;
-    ok = copy_small_arrays(res, DR.descs, DR.index, c0.tab.triArea, E, T, index_bytes(DR.indexFormat), stream0);
-    // the blocks: OMM ranges of ~2 MiB each to the helper threads, while the small arrays above are on their way
-    uint32_t threadsUsed = 1;
-    if (ok && E) {
+    // reads every rank's R.meta; leaves this rank's share of metaSum
+    void sum_meta_share(uint32_t r)
+    {
+        size_t lo, hi; meta_sum_share(metaWords, r, N, &lo, &hi);
+        for (size_t k = lo; k < hi; ++k) { uint32_t a = 0; for (uint32_t q = 0; q < N; ++q) a += ranks[q].meta[k]; metaSum[k] = a; }
+    }
+    // reads metaSum; leaves it on the rank's device, the replicated tail and layout run, the rank's blocks packed into its contribution (R.status)
+    bool meta_to_device_and_tail(Rank& R)
+    {
+        if (metaWords && !HIP_OK(hipMemcpy(R.sb->ctx.tab.meta, metaSum.data(), metaWords * 4, hipMemcpyHostToDevice))) return false;
+        R.status = sharded_tail(R.sb);
+        return R.status == ommResult_SUCCESS;
+    }
+    // reads the rank's contribution; leaves it in the session's pinned memory (R.hStream), as a codec stream or raw (R.raw), sent over this device's own link
+    bool contribution_to_host(Rank& R, uint32_t r)
+    {
+        const ShardCtx& c = R.sb->ctx; hipStream_t stream = R.sb->ses.stream; CodecBlock& cb = R.codec; HostArena& pinned = R.sb->ses.set->pinned;
+        if (!cb.reserve(R.baker->devPool.get(), c.strideBytes, false)) return false;   // (a multiple of 256 already: cb.padded is the stride)
+        uint64_t streamBytes = 0;
+        bool ok = cb.compress(c.x.contrib, stream) && HIP_OK(hipMemcpyAsync(&streamBytes, cb.at.stream, 8, hipMemcpyDeviceToHost, stream)) && HIP_OK(hipStreamSynchronize(stream));
+        const RankSend send = ok ? rank_send(streamBytes, cb.cap, cb.L.offRaw, c.totals[r]) : RankSend{ false, 0 };
+        R.raw = send.raw;
+        ok = ok && pinned.reserve((size_t)send.bytes + 4096);
+        if (ok && send.bytes) ok = HIP_OK(hipMemcpyAsync(pinned.base, R.raw ? c.x.contrib : cb.at.stream, (size_t)send.bytes, hipMemcpyDeviceToHost, stream)) && HIP_OK(hipStreamSynchronize(stream));
+        R.hStream = pinned.base;
+        return ok;
+    }
+    // One rank, on its device; every barrier of the team is here.  Reads the set-up of the ranks; leaves R.sb, R.hStream, R.raw, R.status, rank 0 also `layout` and `strideBytes`.
+    void rank_phase(uint32_t r)
+    {
+        Rank& R = ranks[r];
+        const DeviceScope onDev(R.dev);
+        if (!team.barrier(upload_and_begin(R, r))) return;
+        if (!team.barrier(meta_to_host(R, r))) return;
+        if (!team.barrier(4ull * R.sb->ctx.hc.activeStart[kNumLevels] == metaWords)) return;   // (every rank ran the same set-up: anything else is an internal error -- and nobody may read a shorter copy)
+        sum_meta_share(r);
+        if (!team.barrier(true)) return;
+        const bool ok = meta_to_device_and_tail(R) && contribution_to_host(R, r);
+        if (r == 0) { layout = R.codec.L; strideBytes = R.codec.padded; }
+        (void)team.barrier(ok);
+    }
+    // reads the ranks' set-up; leaves every rank's phase run -- rank 0 on the calling thread, the others on a thread each -- and `tA`
+    ommResult run_team()
+    {
+        // (nothing may leave a rank's thread: an exception -- std::bad_alloc of a host vector -- fails the rank and releases the others from their barriers)
+        auto guardedPhase = [this](uint32_t r) { try { rank_phase(r); } catch (...) { ranks[r].status = ommResult_FAILURE; team.abort(); } };
+        // a rank whose thread cannot be started is run by the caller AFTER the others would deadlock the barriers: refuse instead
+        std::vector<std::thread> threads;
+        bool spawned = true;
+        try { threads.reserve(N); for (uint32_t r = 1; r < N; ++r) threads.emplace_back(guardedPhase, r); } catch (...) { spawned = false; }
+        if (!spawned) {
+            team.abort();   // (threads that did start wait in the first barrier for ranks that never come)
+            for (auto& t : threads) t.join();
+            return L.failure("[Failure] - multi-device bake: could not start a thread per device");
+        }
+        guardedPhase(0);
+        for (auto& t : threads) t.join();
+        for (const Rank& R : ranks) if (R.status != ommResult_SUCCESS) return R.status;
+        for (const Rank& R : ranks) if (!R.sb || !R.hStream) return L.failure("[Failure] - multi-device bake: a device failed");
+        tA = now_ms();
+        return ommResult_SUCCESS;
+    }
+    // reads rank 0's tail outputs; leaves its layout tables in `lay` and descriptors, index buffer and histograms in `dres` (sharded_finish synchronises the stream: the copies into `lay` are complete)
+    ommResult read_layout(HostLayout& lay, DeviceResultOwner& dres)
+    {
+        ShardedBake* sb0 = ranks[0].sb; const ShardCtx& c0 = sb0->ctx; hipStream_t stream0 = sb0->ses.stream;
+        const uint32_t E = c0.counts.numOmms, U = c0.ti.numItems;
+        lay.order.resize(E ? E : 1); lay.dstOfs.resize(E ? E : 1); lay.sizes.resize(E ? E : 1); lay.cofs.resize(E ? E : 1);
+        lay.mask.resize(U ? U : 1); lay.active.resize(U ? U : 1); lay.owner.resize(U ? U : 1); lay.level.resize(U ? U : 1);
+        bool ok = true;
+        if (E) ok = HIP_OK(hipMemcpyAsync(lay.order.data(), c0.to.order, (size_t)E * 4, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(lay.dstOfs.data(), c0.to.dstOfs, (size_t)E * 4, hipMemcpyDeviceToHost, stream0))
+                  && HIP_OK(hipMemcpyAsync(lay.sizes.data(), c0.to.sizes, (size_t)E * 4, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(lay.cofs.data(), c0.tab.cofs, (size_t)E * 8, hipMemcpyDeviceToHost, stream0));
+        if (ok && U) ok = HIP_OK(hipMemcpyAsync(lay.active.data(), c0.tab.active, U, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(lay.owner.data(), c0.tab.owner, U, hipMemcpyDeviceToHost, stream0))
+                       && HIP_OK(hipMemcpyAsync(lay.level.data(), c0.tab.level, U, hipMemcpyDeviceToHost, stream0)) && HIP_OK(hipMemcpyAsync(lay.mask.data(), c0.tab.mask, (size_t)U * 4, hipMemcpyDeviceToHost, stream0));
+        if (!ok) return L.failure("[Failure] - device to host transfer of the bake result failed");
+        ommxDeviceBakeResult made = nullptr;
+        const ommResult fr = sharded_finish(sb0, [](uint8_t*) { return true; }, &made, false);
+        dres.p = (DeviceBakeResult*)made;
+        return fr;
+    }
+    // reads `lay` and every rank's stream; leaves every block of res->arrayData written from its owner's stream: OMM ranges of ~2 MiB each to the helper threads.  Returns the threads used.
+    uint32_t scatter_on_host(const HostLayout& lay, BakeResult* res)
+    {
         HostScatter S; memset(&S, 0, sizeof S);
-        S.world = N; S.L = layout; S.bits = c0.bits;
+        S.world = N; S.L = layout; S.bits = ranks[0].sb->ctx.bits;
         for (uint32_t r = 0; r < N; ++r) { S.stream[r] = ranks[r].hStream; S.raw[r] = ranks[r].raw; }
-        S.active = hActive.data(); S.owner = hOwner.data(); S.level = hLevel.data(); S.stateMask = hMask.data(); S.order = hOrder.data(); S.dstOfs = hDstOfs.data();
-        S.sizes = hSizes.data(); S.cofs = hCofs.data(); S.arrayData = (uint8_t*)res->arrayData;
-        std::vector<uint32_t> cut; cut.push_back(0);
-        uint64_t acc = 0; for (uint32_t j = 0; j < E; ++j) { acc += hSizes[j]; if (acc >= ((uint64_t)2 << 20)) { cut.push_back(j + 1); acc = 0; } }
-        if (cut.back() != E) cut.push_back(E);
+        S.active = lay.active.data(); S.owner = lay.owner.data(); S.level = lay.level.data(); S.stateMask = lay.mask.data(); S.order = lay.order.data(); S.dstOfs = lay.dstOfs.data();
+        S.sizes = lay.sizes.data(); S.cofs = lay.cofs.data(); S.arrayData = (uint8_t*)res->arrayData;
+        const std::vector<uint32_t> cut = scatter_cuts(lay.sizes.data(), ranks[0].sb->ctx.counts.numOmms);
         const std::shared_ptr<WorkerPool> pool = baker.worker_pool(expand_thread_count(baker));
         if (baker.knob(ommxBakerKnob_HelperAffinity) == 0) (void)pool->bind_near(res->arrayData);
         pool->run((uint32_t)cut.size() - 1u, [&](uint32_t t) { codec_scatter_omms(S, cut[t], cut[t + 1]); });
-        threadsUsed = pool->workers() + 1u;
+        return pool->workers() + 1u;
     }
-    ok = ok && HIP_OK(hipStreamSynchronize(stream0));
-    if (!ok) return L.failure("[Failure] - device to host transfer of the bake result failed");
-    memcpy(res->arrayHist, dr->arrayHist, sizeof(ommCpuOpacityMicromapUsageCount) * 2 * kNumLevels);
-    memcpy(res->indexHist, dr->indexHist, sizeof(ommCpuOpacityMicromapUsageCount) * 2 * kNumLevels);
-    fill_result_desc(&res->desc, res->arrayData, DR.arrayDataSize, res->descs, E, res->index, T, DR.indexFormat, res->arrayHist, dr->desc.descArrayHistogramCount, res->indexHist, dr->desc.indexHistogramCount);
+    // reads `lay`, `dr` and the ranks' streams; leaves the caller's result -- arrays, blocks, histograms -- and the baker's timings
+    ommResult deliver(const HostLayout& lay, DeviceBakeResult* dr, ommCpuBakeResult* out)
     {
-        std::lock_guard<std::mutex> g(baker.timingsMu);   // (sharded_finish stored rank 0's phase clocks)
-        uint64_t wire = 0; for (uint32_t r = 0; r < N; ++r) wire += ranks[r].raw ? c0.totals[r] : (ranks[r].hStream ? *(const uint64_t*)ranks[r].hStream : 0);
-        baker.timings.devices = N; baker.timings.resultTransfer = ommxResultTransfer_Compressed; baker.timings.compressedBytes = wire; baker.timings.expandThreads = threadsUsed;
-        baker.timings.expandMs = (float)(now_ms() - tA); baker.timings.totalMs = (float)(now_ms() - t0); baker.timings.contributionBytes = strideBytes;
+        const ShardCtx& c0 = ranks[0].sb->ctx; hipStream_t stream0 = ranks[0].sb->ses.stream;
+        DeviceResult& DR = dr->R; const uint32_t E = c0.counts.numOmms;
+        HostResultGuard resGuard{ baker, baker.mem.make<BakeResult>(), nullptr };
+        BakeResult* const res = resGuard.r;
+        if (!res) return ommResult_FAILURE;
+        res->mem = baker.mem;
+        const StreamDrain drainBeforeResult{ stream0 };   // (right behind the memory it protects, like the one in front of `lay`)
+        if (E && baker.mem.alloc == default_alloc && baker.hostPool->wants((size_t)DR.arrayDataSize)) { res->arrayData = baker.hostPool->acquire((size_t)DR.arrayDataSize); if (res->arrayData) res->pool = baker.hostPool; }
+        if (alloc_host_result(baker, res, E, (size_t)DR.arrayDataSize, T) != ommResult_SUCCESS) return ommResult_FAILURE;
+        bool ok = copy_small_arrays(res, DR.descs, DR.index, c0.tab.triArea, E, T, index_bytes(DR.indexFormat), stream0);
+        // the blocks, while the small arrays above are on their way
+        const uint32_t threadsUsed = ok && E ? scatter_on_host(lay, res) : 1u;
+        ok = ok && HIP_OK(hipStreamSynchronize(stream0));
+        if (!ok) return L.failure("[Failure] - device to host transfer of the bake result failed");
+        memcpy(res->arrayHist, dr->arrayHist, sizeof(ommCpuOpacityMicromapUsageCount) * 2 * kNumLevels);
+        memcpy(res->indexHist, dr->indexHist, sizeof(ommCpuOpacityMicromapUsageCount) * 2 * kNumLevels);
+        fill_result_desc(&res->desc, res->arrayData, DR.arrayDataSize, res->descs, E, res->index, T, DR.indexFormat, res->arrayHist, dr->desc.descArrayHistogramCount, res->indexHist, dr->desc.indexHistogramCount);
+        {
+            std::lock_guard<std::mutex> g(baker.timingsMu);   // (sharded_finish stored rank 0's phase clocks)
+            uint64_t wire = 0; for (uint32_t r = 0; r < N; ++r) wire += ranks[r].raw ? c0.totals[r] : (ranks[r].hStream ? *(const uint64_t*)ranks[r].hStream : 0);
+            baker.timings.devices = N; baker.timings.resultTransfer = ommxResultTransfer_Compressed; baker.timings.compressedBytes = wire; baker.timings.expandThreads = threadsUsed;
+            baker.timings.expandMs = (float)(now_ms() - tA); baker.timings.totalMs = (float)(now_ms() - t0); baker.timings.contributionBytes = strideBytes;
+        }
+        *out = (ommCpuBakeResult)resGuard.release();
+        return ommResult_SUCCESS;
     }
-    *out = (ommCpuBakeResult)resGuard.release();
-    return ommResult_SUCCESS;
+};
+
+ommResult bake_impl_multi(Baker& baker, const ommCpuBakeInputDesc& d, ommCpuBakeResult* out, uint32_t N)
+{
+    MultiBake m(baker, d, N);
+    // phase A (all ranks): upload, share of the classification, metadata through the host, tail, own contribution as a codec stream on the host
+    ommResult r = m.setup_ranks();
+    if (r == ommResult_SUCCESS) r = m.run_team();
+    if (r != ommResult_SUCCESS) return r;
+    // rank 0: layout tables to the host, descriptors / index buffer / histograms, then the blocks from their owners' streams.
+    // Asynchronous copies into `lay` (and, in deliver, into the result's arrays) are queued on rank 0's stream: whatever way this function is left -- a failed
+    // copy half way down a chain, an exception of a host container or of the thread pool -- the stream is drained BEFORE their memory is released
+    // (destructors run in reverse order of declaration: each guard is declared right behind the memory it protects).
+    const DeviceScope onPrimary(m.primary);
+    HostLayout lay;
+    const StreamDrain drainBeforeVectors{ m.ranks[0].sb->ses.stream };
+    DeviceResultOwner dres(baker.mem, nullptr);   // (no drain of its own: deliver's guard has drained the stream when this one goes)
+    r = m.read_layout(lay, dres);
+    return r != ommResult_SUCCESS ? r : m.deliver(lay, dres.p, out);
 }
 } // namespace
 
@@ -2938,7 +2988,7 @@ OMM_MI355X_API ommResult ommxShardedBegin(ommBaker baker, const ommCpuBakeInputD
     if (out == 0) return ommResult_INVALID_ARGUMENT;
     const ommResult r = sharded_checks(baker, desc, &b, false);
     if (r != ommResult_SUCCESS) return r;
-    if (worldSize == 0 || worldSize > (uint32_t)kMaxRanks || rank >= worldSize) return b->log.invalid("[Invalid Argument] - rank / worldSize out of range (at most 16 ranks)");
+    if (!rank_in_world(rank, worldSize)) return b->log.invalid("[Invalid Argument] - rank / worldSize out of range (at most 16 ranks)");
     return guarded(&b->log, [&]() -> ommResult {
         const DeviceScope onBakersDevice(b->bind_device());
         ShardedBake* sb = nullptr;
@@ -2966,7 +3016,7 @@ OMM_MI355X_API ommResult ommxShardedTail(ommxShardedBake h, void** contribution,
         const ommResult r = sharded_tail(sb);   // (a second call re-uses the same exchange block: nothing leaks)
         if (r != ommResult_SUCCESS) return r;
         if (!HIP_OK(hipStreamSynchronize(sb->ses.stream))) return sb->baker->log.failure("[Failure] - shard gather failed");
-        *contribution = c.dContrib; *contributionBytes = c.totals[c.rank]; *strideBytes = c.strideBytes;
+        *contribution = c.x.contrib; *contributionBytes = c.totals[c.rank]; *strideBytes = c.strideBytes;
         sb->tm.tailMs = (float)(now_ms() - t1);
         return ommResult_SUCCESS;
     });
@@ -2982,13 +3032,9 @@ OMM_MI355X_API ommResult ommxShardedFinish(ommxShardedBake h, const void* gather
         const double t1 = now_ms();
         const ommResult r = sharded_finish(sb, [&](uint8_t* arrayData) {
             if (!arrayData) return false;   // (the result could not be allocated)
-            // same chunk walk as the RCCL path (there each chunk arrives separately): a block that straddles a chunk boundary is placed in pieces
-            const uint64_t chunkBytes = shard_chunk_bytes(*sb->baker, c.strideBytes);
-            for (uint64_t lo = 0; lo < c.strideBytes; lo += chunkBytes) {
-                const uint64_t hi = lo + chunkBytes < c.strideBytes ? lo + chunkBytes : c.strideBytes;
-                launch_shard_scatter((const uint8_t*)gathered + lo, c.strideBytes, lo, hi, c.tab.active, c.tab.owner, c.tab.mask, c.tab.level, c.bits, c.to.order, c.tab.cofs, c.to.dstOfs, c.to.sizes,
-                                     c.counts.numOmms, arrayData, sb->ses.stream);
-            }
+            // the chunk walk of the RCCL path (there each chunk arrives separately)
+            for (ShardChunks w(c.strideBytes, sb->baker->knob(ommxBakerKnob_ShardChunkBytes)); w.next();)
+                shard_scatter(c, (const uint8_t*)gathered + w.lo, c.strideBytes, w.lo, w.hi, arrayData, sb->ses.stream);
             return true;
         }, outResult);
         sb->tm.gatherMs = (float)(now_ms() - t1);
@@ -3013,43 +3059,48 @@ OMM_MI355X_API ommResult ommxRcclGetUniqueId(void* outId, size_t idBytes)
     return rccl().getUniqueId((RcclUniqueId*)outId) == 0 ? ommResult_SUCCESS : ommResult_FAILURE;
 }
 
-OMM_MI355X_API ommResult ommxRcclCommInitRank(const void* id, size_t idBytes, uint32_t rank, uint32_t worldSize, ommxRcclComm* outComm)
+// The one way a communicator handle is made: `fill` sets what the entry knows (a failure of it is the entry's answer), the status words follow.
+template <class Fill> static ommResult make_comm(ommxRcclComm* outComm, Fill&& fill)
 {
-    if (id == nullptr || idBytes < sizeof(RcclUniqueId) || outComm == nullptr || worldSize == 0 || worldSize > (uint32_t)kMaxRanks || rank >= worldSize) return ommResult_INVALID_ARGUMENT;
-    if (!rccl().ok()) return ommResult_FAILURE;
-    RcclUniqueId uid; memcpy(&uid, id, sizeof uid);
     RcclComm* c = new (std::nothrow) RcclComm();
     if (!c) return ommResult_FAILURE;
-    if (rccl().commInitRank(&c->comm, (int)worldSize, uid, (int)rank) != 0) { delete c; return ommResult_FAILURE; }
-    c->owned = true; c->rank = (int)rank; c->world = (int)worldSize;
+    const ommResult r = fill(*c);
+    if (r != ommResult_SUCCESS) { delete c; return r; }
     rccl_prepare_status(c);
     *outComm = (ommxRcclComm)c;
     return ommResult_SUCCESS;
+}
+
+OMM_MI355X_API ommResult ommxRcclCommInitRank(const void* id, size_t idBytes, uint32_t rank, uint32_t worldSize, ommxRcclComm* outComm)
+{
+    if (id == nullptr || idBytes < sizeof(RcclUniqueId) || outComm == nullptr || !rank_in_world(rank, worldSize)) return ommResult_INVALID_ARGUMENT;
+    if (!rccl().ok()) return ommResult_FAILURE;
+    RcclUniqueId uid; memcpy(&uid, id, sizeof uid);
+    return make_comm(outComm, [&](RcclComm& c) {
+        if (rccl().commInitRank(&c.comm, (int)worldSize, uid, (int)rank) != 0) return ommResult_FAILURE;
+        c.owned = true; c.rank = (int)rank; c.world = (int)worldSize;
+        return ommResult_SUCCESS;
+    });
 }
 
 OMM_MI355X_API ommResult ommxRcclCommWrap(void* ncclComm, ommxRcclComm* outComm)
 {
     if (ncclComm == nullptr || outComm == nullptr) return ommResult_INVALID_ARGUMENT;
     if (!rccl().ok()) return ommResult_FAILURE;
-    RcclComm* c = new (std::nothrow) RcclComm();
-    if (!c) return ommResult_FAILURE;
-    c->comm = ncclComm; c->owned = false;
-    if (rccl().commCount(c->comm, &c->world) != 0 || rccl().commUserRank(c->comm, &c->rank) != 0 || c->world < 1 || c->world > kMaxRanks) { delete c; return ommResult_INVALID_ARGUMENT; }
-    rccl_prepare_status(c);
-    *outComm = (ommxRcclComm)c;
-    return ommResult_SUCCESS;
+    return make_comm(outComm, [&](RcclComm& c) {
+        c.comm = ncclComm; c.owned = false;
+        const bool known = rccl().commCount(c.comm, &c.world) == 0 && rccl().commUserRank(c.comm, &c.rank) == 0 && c.world >= 1 && c.world <= kMaxRanks;
+        return known ? ommResult_SUCCESS : ommResult_INVALID_ARGUMENT;
+    });
 }
 
 OMM_MI355X_API ommResult ommxCommFromCollectives(const ommxCollectives* collectives, uint32_t rank, uint32_t worldSize, ommxRcclComm* outComm)
 {
-    if (collectives == nullptr || collectives->allReduceU32 == nullptr || collectives->allGatherBytes == nullptr || outComm == nullptr ||
-        worldSize == 0 || worldSize > (uint32_t)kMaxRanks || rank >= worldSize) return ommResult_INVALID_ARGUMENT;
-    RcclComm* c = new (std::nothrow) RcclComm();
-    if (!c) return ommResult_FAILURE;
-    c->custom = true; c->user = *collectives; c->rank = (int)rank; c->world = (int)worldSize;
-    rccl_prepare_status(c);
-    *outComm = (ommxRcclComm)c;
-    return ommResult_SUCCESS;
+    if (collectives == nullptr || collectives->allReduceU32 == nullptr || collectives->allGatherBytes == nullptr || outComm == nullptr || !rank_in_world(rank, worldSize)) return ommResult_INVALID_ARGUMENT;
+    return make_comm(outComm, [&](RcclComm& c) {
+        c.custom = true; c.user = *collectives; c.rank = (int)rank; c.world = (int)worldSize;
+        return ommResult_SUCCESS;
+    });
 }
 
 OMM_MI355X_API ommResult ommxRcclCommInfo(ommxRcclComm comm, uint32_t* outRank, uint32_t* outWorldSize)
@@ -3073,6 +3124,128 @@ OMM_MI355X_API ommResult ommxRcclCommDestroy(ommxRcclComm comm)
     return ommResult_SUCCESS;
 }
 
+namespace {
+// One ommxShardedBakeRccl: what its stages hand on, and the stages themselves in the order they run.  Collectives that every rank must enter are
+// preceded by an agreement (rccl_agree): a rank that failed answers with its own code, one that stops for another's sake with FAILURE (stopped).
+struct RcclBake {
+    // ---- the call ----
+    Baker* const b; const ommCpuBakeInputDesc& desc; RcclComm* const rc; const Logger& L; const bool hostTail;
+    // ---- what the stages hand on ----
+    ShardedBake* sb = nullptr; hipStream_t stream = nullptr;   // the bake, this object's to destroy, and its stream
+    double t1 = 0;                                             // the ranks' shares are classified
+    RcclBake(Baker* b_, const ommCpuBakeInputDesc& desc_, RcclComm* rc_) : b(b_), desc(desc_), rc(rc_), L(b_->log), hostTail(wants_host_tail(desc_)) {}
+    RcclBake(const RcclBake&) = delete; RcclBake& operator=(const RcclBake&) = delete;
+    ~RcclBake() { if (sb) b->mem.destroy(sb); }
+    ommResult nccl_fail(int code, const char* what) const { char buf[256]; snprintf(buf, sizeof buf, "[Failure] - %s: %s", what, rc->error_string(code)); return L.failure(buf); }
+    static ommResult stopped(ommResult mine) { return mine != ommResult_SUCCESS ? mine : ommResult_FAILURE; }
+
+    // reads the call; leaves `sb` with this rank's share classified and its metadata packed (nothing synchronised), and every rank's word that it got that far
+    ommResult begin()
+    {
+        const ommResult r = sharded_begin(b, &desc, (uint32_t)rc->rank, (uint32_t)rc->world, true, &sb, hostTail);
+        if (r != ommResult_SUCCESS) sb = nullptr;
+        if (!rccl_agree(rc, sb ? sb->ses.stream : nullptr, r == ommResult_SUCCESS, L, "classification of its share")) return stopped(r);
+        stream = sb->ses.stream; t1 = now_ms();
+        return ommResult_SUCCESS;
+    }
+    // The opt-in lossy reducers (near-duplicate merge, maxArrayDataSize): the serial reference algorithms need the states of ALL work items.  Every rank
+    // classified its share into a zeroed buffer, so SUM all-reduces of the metadata words and of the packed states merge them; each rank then runs the
+    // identical serial tail on the host and uploads the (identical) result.  Reads the ranks' shares; leaves the result and the baker's timings.
+    ommResult host_tail(ommxDeviceBakeResult* outResult)
+    {
+        ShardCtx& c = sb->ctx;
+        const size_t words = 4ull * c.hc.activeStart[kNumLevels], stateWords = (size_t)(c.hc.stateBytes / 4);
+        int e = words ? rc->all_reduce(c.tab.meta, c.tab.meta, words, kRcclSum, stream) : 0;
+        if (e == 0 && stateWords) e = rc->all_reduce(c.dStates, c.dStates, stateWords, kRcclSum, stream);
+        if (e != 0) return nccl_fail(e, "ncclAllReduce of the micro-triangle states");
+        launch_shard_unpack_meta(c.bounds, c.tab.activeIds, c.hc.activeStart[kNumLevels], c.tab.meta, c.tab.mask, (uint32_t*)c.ti.knownCount, c.ti.digests, c.tab.owner, stream);
+        std::vector<HostItem> items;
+        ommResult r = gather_host_items(L, stream, c.ti.numItems, c.T, c.hc, c.ti.uv, c.tab.level, c.tab.active, c.tab.mask, c.tab.stateOfs, c.dStates, c.ti.triToItem, c.bits, items);
+        HostTailResult hres; ommIndexFormat ifmt = ommIndexFormat_UINT_32;
+        if (r == ommResult_SUCCESS) r = run_host_tail_for(desc, c.T, items, hres, ifmt);
+        if (r != ommResult_SUCCESS) return r;
+        DeviceResultOwner res(b->mem, stream);
+        if (!res.make()) return ommResult_FAILURE;
+        r = upload_host_tail(*b, hres, ifmt, c.T, c.bits, stream, res.p);
+        if (r != ommResult_SUCCESS) return r;
+        sb->tm.tailMs = (float)(now_ms() - t1);
+        store_begin_timings(sb, false);
+        *outResult = (ommxDeviceBakeResult)res.release();
+        return ommResult_SUCCESS;
+    }
+    // exchange 1.  Reads the metadata words of this rank's share; leaves every rank's, by a SUM all-reduce in place on the bake's own stream right behind the digests
+    ommResult exchange_meta()
+    {
+        ShardCtx& c = sb->ctx;
+        const size_t words = 4ull * c.hc.activeStart[kNumLevels];
+        const int e = words ? rc->all_reduce(c.tab.meta, c.tab.meta, words, kRcclSum, stream) : 0;
+        return e != 0 ? nccl_fail(e, "ncclAllReduce of the work-item metadata") : ommResult_SUCCESS;
+    }
+    // reads the summed metadata; leaves the replicated tail run, this rank's contribution packed, and every rank's word that it got that far
+    ommResult tail()
+    {
+        const ommResult r = sharded_tail(sb);
+        if (!rccl_agree(rc, stream, r == ommResult_SUCCESS, L, "tail of the bake")) return stopped(r);
+        sb->tm.tailMs = (float)(now_ms() - t1);
+        return ommResult_SUCCESS;
+    }
+    // exchange 2.  Reads the ranks' contributions; leaves the result (sharded_finish, with scatter_blocks for the array) and the exchange's fields of the baker's timings
+    ommResult exchange_blocks(ommxDeviceBakeResult* outResult)
+    {
+        const double t2 = now_ms();
+        const ommResult r = sharded_finish(sb, [this](uint8_t* arrayData) { return scatter_blocks(arrayData); }, outResult);
+        sb->tm.gatherMs = (float)(now_ms() - t2);
+        if (r == ommResult_SUCCESS) { std::lock_guard<std::mutex> g(b->timingsMu); b->timings.tailMs = sb->tm.tailMs; b->timings.gatherMs = sb->tm.gatherMs; b->timings.exchangeBytes = sb->tm.exchangeBytes; b->timings.contributionBytes = sb->tm.contributionBytes; }
+        return r;
+    }
+    // Reads this rank's contribution; leaves every rank's blocks at their final offsets in arrayData -- null when this rank could not allocate the result: it
+    // still takes part in the agreement, so that nobody waits for it.  (A one-rank communicator takes the same route: the collectives degenerate to copies.)
+    // The contribution becomes a codec stream (tail_kernels.hip "block exchange codec"), and the agreement on the ranks' status carries the stream sizes:
+    // MAX over the ranks = what every rank sends (the all-gather needs equal counts), or "one of them does not shrink" = everybody sends raw.
+    bool scatter_blocks(uint8_t* arrayData)
+    {
+        ShardCtx& c = sb->ctx;
+        EventList<1 + kShardMaxChunks> evs;   // contribution ready | chunk k gathered: they go with this scope, behind the last wait on either stream
+        bool ok = arrayData != nullptr && sb->ses.open_comm() && evs.create(1);
+        ok = ok && HIP_OK(run_shard_compress(c.x.contrib, c.strideBytes, c.x.comp, c.x.compCap, c.x.compSize, c.x.codecScratch, c.x.codecScratchBytes, stream));
+        uint32_t maxUnits = 0;
+        ok = rccl_agree(rc, stream, ok, L, "allocation of the result", c.x.compSize, &maxUnits) && ok;
+        if (!ok) return false;
+        sb->tm.contributionBytes = c.strideBytes;
+        return maxUnits != kCodecIncompressible ? blocks_as_streams((size_t)maxUnits * 16u, arrayData) : blocks_raw_in_chunks(evs, arrayData);
+    }
+    // reads this rank's codec stream, `sendBytes` of it (<= compCap by construction); leaves the blocks placed, the stream synchronised
+    bool blocks_as_streams(size_t sendBytes, uint8_t* arrayData)
+    {
+        ShardCtx& c = sb->ctx;
+        sb->tm.exchangeBytes = sendBytes;
+        const int e = rc->all_gather(c.x.comp, c.x.gatherComp, sendBytes, stream);
+        if (e != 0) { (void)nccl_fail(e, "ncclAllGather of the OMM blocks"); return false; }
+        shard_scatter_streams(c, sendBytes, arrayData, stream);
+        return HIP_OK(hipGetLastError()) && HIP_OK(hipStreamSynchronize(stream));
+    }
+    // Reads the padded contributions, all-gathered in chunks on the communication stream: every chunk is scattered to its final arrayData offsets on the bake's
+    // stream while the next one is on the wire.  Leaves the blocks placed and BOTH streams synchronised, also when a step failed.
+    bool blocks_raw_in_chunks(EventList<1 + kShardMaxChunks>& evs, uint8_t* arrayData)
+    {
+        ShardCtx& c = sb->ctx; hipStream_t cs = sb->ses.commStream;
+        sb->tm.exchangeBytes = c.strideBytes;
+        bool ok = HIP_OK(hipEventRecord(evs.ev[0], stream)) && HIP_OK(hipStreamWaitEvent(cs, evs.ev[0], 0));
+        int ncclErr = 0; uint32_t k = 0;
+        for (ShardChunks w(c.strideBytes, b->knob(ommxBakerKnob_ShardChunkBytes)); ok && w.next(); ++k) {
+            uint8_t* stage = c.x.gathered + w.lo * (uint64_t)rc->world;               // chunk k of all ranks: world x (hi - lo) bytes
+            ncclErr = rc->all_gather(c.x.contrib + w.lo, stage, (size_t)(w.hi - w.lo), cs);
+            ok = ncclErr == 0 && evs.create(k + 2u) && HIP_OK(hipEventRecord(evs.ev[k + 1u], cs)) && HIP_OK(hipStreamWaitEvent(stream, evs.ev[k + 1u], 0));
+            if (ok) shard_scatter(c, stage, w.hi - w.lo, w.lo, w.hi, arrayData, stream);
+        }
+        ok = ok && HIP_OK(hipStreamSynchronize(stream));
+        (void)hipStreamSynchronize(cs);
+        if (ncclErr != 0) (void)nccl_fail(ncclErr, "ncclAllGather of the OMM blocks");
+        return ok;
+    }
+};
+} // namespace
+
 OMM_MI355X_API ommResult ommxShardedBakeRccl(ommBaker baker, const ommCpuBakeInputDesc* desc, ommxRcclComm comm, ommxDeviceBakeResult* outResult)
 {
     Baker* b = nullptr;
@@ -3085,101 +3258,13 @@ OMM_MI355X_API ommResult ommxShardedBakeRccl(ommBaker baker, const ommCpuBakeInp
     return guarded(&L, [&]() -> ommResult {
         const DeviceScope onBakersDevice(b->bind_device());
         rccl_status_on_device(rc, b->bind_device());          // (status words / idle-rank stream on the bake's device, whatever was current when the communicator was made)
-        auto nccl_fail = [&](int code, const char* what) {
-            char buf[256]; snprintf(buf, sizeof buf, "[Failure] - %s: %s", what, rc->error_string(code));
-            return L.failure(buf);
-        };
-        const bool hostTail = wants_host_tail(*desc);
-        ShardedBake* sb = nullptr;
-        ommResult r = sharded_begin(b, desc, (uint32_t)rc->rank, (uint32_t)rc->world, true, &sb, hostTail);
-        if (r != ommResult_SUCCESS) sb = nullptr;
-        struct Owner { Baker* b; ShardedBake* sb; ~Owner() { if (sb) b->mem.destroy(sb); } } owner{ b, sb };
-        if (!rccl_agree(rc, sb ? sb->ses.stream : nullptr, r == ommResult_SUCCESS, L, "classification of its share")) return r != ommResult_SUCCESS ? r : ommResult_FAILURE;
-        ShardCtx& c = sb->ctx; hipStream_t stream = sb->ses.stream;
-        const double t1 = now_ms();
-        if (hostTail) {
-            // opt-in lossy reducers (near-duplicate merge, maxArrayDataSize): the serial reference algorithms need the states of ALL work items.
-            // Every rank classified its share into a zeroed buffer, so SUM all-reduces of the metadata words and of the packed states merge
-            // them; each rank then runs the identical serial tail on the host and uploads the (identical) result.
-            const size_t words = 4ull * c.hc.activeStart[kNumLevels], stateWords = (size_t)(c.hc.stateBytes / 4);
-            int e = words ? rc->all_reduce(c.tab.meta, c.tab.meta, words, kRcclSum, stream) : 0;
-            if (e == 0 && stateWords) e = rc->all_reduce(c.dStates, c.dStates, stateWords, kRcclSum, stream);
-            if (e != 0) return nccl_fail(e, "ncclAllReduce of the micro-triangle states");
-            launch_shard_unpack_meta(c.bounds, c.tab.activeIds, c.hc.activeStart[kNumLevels], c.tab.meta, c.tab.mask, (uint32_t*)c.ti.knownCount, c.ti.digests, c.tab.owner, stream);
-            std::vector<HostItem> items;
-            r = gather_host_items(L, stream, c.ti.numItems, c.T, c.hc, c.ti.uv, c.tab.level, c.tab.active, c.tab.mask, c.tab.stateOfs, c.dStates, c.ti.triToItem, c.bits, items);
-            HostTailResult hres; ommIndexFormat ifmt = ommIndexFormat_UINT_32;
-            if (r == ommResult_SUCCESS) r = run_host_tail_for(*desc, c.T, items, hres, ifmt);
-            if (r != ommResult_SUCCESS) return r;
-            DeviceBakeResult* res = b->mem.make<DeviceBakeResult>();
-            if (!res) return ommResult_FAILURE;
-            res->mem = b->mem; memset(&res->desc, 0, sizeof res->desc);
-            r = upload_host_tail(*b, hres, ifmt, c.T, c.bits, stream, res);
-            if (r != ommResult_SUCCESS) { b->mem.destroy(res); return r; }
-            const int* ev = c.ev;
-            sb->tm.setupMs = sb->et->ms(ev[0], ev[1]); sb->tm.triageMs = sb->et->ms(ev[1], ev[2]); sb->tm.classifyMs = sb->et->ms(ev[2], ev[3]);
-            sb->tm.tailMs = (float)(now_ms() - t1); sb->tm.totalMs = (float)(now_ms() - sb->t0);
-            store_timings(*b, sb->tm);
-            *outResult = (ommxDeviceBakeResult)res;
-            return ommResult_SUCCESS;
-        }
-        // exchange 1: per-item metadata, SUM all-reduce in place, on the bake's own stream right behind the digests
-        const size_t words = 4ull * c.hc.activeStart[kNumLevels];
-        if (words) { const int e = rc->all_reduce(c.tab.meta, c.tab.meta, words, kRcclSum, stream); if (e != 0) return nccl_fail(e, "ncclAllReduce of the work-item metadata"); }
-        r = sharded_tail(sb);
-        if (!rccl_agree(rc, stream, r == ommResult_SUCCESS, L, "tail of the bake")) return r != ommResult_SUCCESS ? r : ommResult_FAILURE;
-        sb->tm.tailMs = (float)(now_ms() - t1);
-        const double t2 = now_ms();
-        // exchange 2: the padded contributions, all-gathered in chunks on a second stream; every chunk is scattered to its final arrayData
-        // offsets on the bake's stream while the next one is on the wire
-        const uint32_t E = c.counts.numOmms;
-        r = sharded_finish(sb, [&](uint8_t* arrayData) -> bool {
-            // (a one-rank communicator takes the same route: the collectives degenerate to copies, the plumbing is the same)
-            // (arrayData is null when this rank could not allocate the result: it still takes part in the agreement, so that nobody waits for it)
-            hipEvent_t ready = nullptr, done[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-            bool ok = arrayData != nullptr && sb->ses.open_comm() && HIP_OK(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-            // the contribution as a codec stream (tail_kernels.hip "block exchange codec"); the agreement on the ranks' status carries the stream sizes:
-            // MAX over the ranks = what every rank sends (the all-gather needs equal counts), or "one of them does not shrink" = everybody sends raw
-            ok = ok && HIP_OK(run_shard_compress(c.dContrib, c.strideBytes, c.dComp, c.compCap, c.dCompSize, c.dCodecScratch, c.codecScratchBytes, stream));
-            uint32_t maxUnits = 0;
-            ok = rccl_agree_max(rc, stream, ok, c.dCompSize, &maxUnits, L, "allocation of the result") && ok;
-            if (!ok) { if (ready) (void)hipEventDestroy(ready); return false; }
-            sb->tm.contributionBytes = c.strideBytes;
-            if (maxUnits != kCodecIncompressible) {
-                const size_t sendBytes = (size_t)maxUnits * 16u;   // (<= compCap by construction)
-                sb->tm.exchangeBytes = sendBytes;
-                const int e = rc->all_gather(c.dComp, c.dGatherComp, sendBytes, stream);
-                if (e != 0) { (void)nccl_fail(e, "ncclAllGather of the OMM blocks"); (void)hipEventDestroy(ready); return false; }
-                // every block straight from its owner's stream to its final offset (no expanded copy of the contributions)
-                launch_shard_scatter_streams(c.dGatherComp, sendBytes, c.strideBytes, c.tab.active, c.tab.owner, c.tab.mask, c.tab.level, c.bits, c.to.order, c.tab.cofs, c.to.dstOfs, c.to.sizes, E, arrayData, stream);
-                ok = HIP_OK(hipGetLastError()) && HIP_OK(hipStreamSynchronize(stream));
-                (void)hipEventDestroy(ready);
-                return ok;
-            }
-            sb->tm.exchangeBytes = c.strideBytes;
-            hipStream_t cs = sb->ses.commStream;
-            const uint64_t chunkBytes = shard_chunk_bytes(*sb->baker, c.strideBytes);              // per rank and chunk; at most 8 chunks
-            uint64_t chunks = (c.strideBytes + chunkBytes - 1) / chunkBytes;
-            ok = HIP_OK(hipEventRecord(ready, stream)) && HIP_OK(hipStreamWaitEvent(cs, ready, 0));
-            int ncclErr = 0;
-            for (uint64_t k = 0; ok && k < chunks; ++k) {
-                const uint64_t lo = k * chunkBytes, hi = lo + chunkBytes < c.strideBytes ? lo + chunkBytes : c.strideBytes;
-                if (lo >= hi) { chunks = k; break; }
-                uint8_t* stage = c.dGathered + lo * (uint64_t)rc->world;               // chunk k of all ranks: world x (hi - lo) bytes
-                ncclErr = rc->all_gather(c.dContrib + lo, stage, (size_t)(hi - lo), cs);
-                ok = ncclErr == 0 && HIP_OK(hipEventCreateWithFlags(&done[k], hipEventDisableTiming)) && HIP_OK(hipEventRecord(done[k], cs)) && HIP_OK(hipStreamWaitEvent(stream, done[k], 0));
-                if (ok) launch_shard_scatter(stage, hi - lo, lo, hi, c.tab.active, c.tab.owner, c.tab.mask, c.tab.level, c.bits, c.to.order, c.tab.cofs, c.to.dstOfs, c.to.sizes, E, arrayData, stream);
-            }
-            ok = ok && HIP_OK(hipStreamSynchronize(stream));
-            (void)hipStreamSynchronize(cs);
-            if (ready) (void)hipEventDestroy(ready);
-            for (hipEvent_t e : done) if (e) (void)hipEventDestroy(e);
-            if (ncclErr != 0) (void)nccl_fail(ncclErr, "ncclAllGather of the OMM blocks");
-            return ok;
-        }, outResult);
-        sb->tm.gatherMs = (float)(now_ms() - t2);
-        if (r == ommResult_SUCCESS) { std::lock_guard<std::mutex> g(b->timingsMu); b->timings.tailMs = sb->tm.tailMs; b->timings.gatherMs = sb->tm.gatherMs; b->timings.exchangeBytes = sb->tm.exchangeBytes; b->timings.contributionBytes = sb->tm.contributionBytes; }
-        return r;
+        RcclBake run(b, *desc, rc);
+        ommResult r = run.begin();
+        if (r != ommResult_SUCCESS) return r;
+        if (run.hostTail) return run.host_tail(outResult);
+        r = run.exchange_meta();
+        if (r == ommResult_SUCCESS) r = run.tail();
+        return r != ommResult_SUCCESS ? r : run.exchange_blocks(outResult);
     });
 }
 

@@ -376,6 +376,159 @@ static void readback_and_small_rules()
     for (uint32_t active : actives) CHECK(max_distinct_digests(active) == active + 64u, "%u active items", active);
 }
 
+// ---- the sharded bake's rules: each held to the expression it had inline in the sharded section of omm_host.cpp (at 01c096a), restated ----
+static void shard_rank_and_stride_rules()
+{
+    for (uint32_t worldSize = 0; worldSize < 18; ++worldSize) for (uint32_t rank = 0; rank < 18; ++rank)
+        CHECK(rank_in_world(rank, worldSize) == !(worldSize == 0 || worldSize > 16u || rank >= worldSize), "rank %u of %u", rank, worldSize);
+    CHECK(rank_in_world(15, 16) && !rank_in_world(16, 16) && !rank_in_world(0, 17), "at most 16 ranks");
+    CHECK(!rank_in_world(0xFFFFFFFFu, 16) && !rank_in_world(0, 0xFFFFFFFFu) && !rank_in_world(0, 0), "far out of range");
+    const uint64_t maxima[6] = { 0, 1, 255, 256, 257, (1ull << 32) + 1 }, strides[6] = { 256, 256, 256, 256, 512, (1ull << 32) + 256 };
+    const uint32_t worlds[5] = { 1, 2, 3, 8, 16 };
+    for (int m = 0; m < 6; ++m) {
+        for (uint32_t world : worlds) {
+            uint64_t totals[kBakeMaxRanks];
+            for (uint32_t r = 0; r < kBakeMaxRanks; ++r) totals[r] = r < world ? maxima[m] / 2 : ~0ull;   // (ranks outside the world must not count)
+            totals[(m + world / 2) % world] = maxima[m];
+            uint64_t mx = 0; for (uint32_t r = 0; r < world; ++r) mx = totals[r] > mx ? totals[r] : mx;
+            uint64_t strideBytes = (mx + 255) & ~255ull; if (strideBytes == 0) strideBytes = 256;
+            CHECK(contribution_stride(totals, world) == strideBytes, "largest total %llu of %u ranks", (unsigned long long)maxima[m], world);
+        }
+        CHECK(contribution_stride(&maxima[m], 1) == strides[m], "a total of %llu bytes", (unsigned long long)maxima[m]);
+    }
+}
+
+static uint64_t parent_chunk_bytes(uint64_t knob, uint64_t strideBytes)
+{
+    uint64_t want = 64ull << 20;
+    if (const uint64_t v = knob) want = v;
+    uint64_t chunks = (strideBytes + want - 1) / want; if (chunks > 8) chunks = 8; if (chunks < 1) chunks = 1;
+    return ((((strideBytes + chunks - 1) / chunks) + 255) & ~255ull);
+}
+struct Chunk { uint64_t lo, hi; };
+static void shard_chunk_rules()
+{
+    const uint64_t M = 64ull << 20;
+    const uint64_t strides[7] = { 256, 512, M - 256, M, M + 256, 8 * M, 8 * M + 256 }, knobs[3] = { 0, 256, 4352 };
+    for (uint64_t strideBytes : strides) for (uint64_t knob : knobs) {
+        const uint64_t chunkBytes = parent_chunk_bytes(knob, strideBytes);
+        CHECK(shard_chunk_bytes(strideBytes, knob) == chunkBytes, "chunk size of a stride of %llu, knob %llu", (unsigned long long)strideBytes, (unsigned long long)knob);
+        std::vector<Chunk> got;
+        for (ShardChunks w(strideBytes, knob); w.next();) got.push_back(Chunk{ w.lo, w.hi });
+        // the two loops the walk replaced: the four-phase finish ...
+        std::vector<Chunk> finish, rccl;
+        for (uint64_t lo = 0; lo < strideBytes; lo += chunkBytes) finish.push_back(Chunk{ lo, lo + chunkBytes < strideBytes ? lo + chunkBytes : strideBytes });
+        // ... and the raw exchange of the one-call form
+        uint64_t chunks = (strideBytes + chunkBytes - 1) / chunkBytes;
+        for (uint64_t k = 0; k < chunks; ++k) {
+            const uint64_t lo = k * chunkBytes, hi = lo + chunkBytes < strideBytes ? lo + chunkBytes : strideBytes;
+            if (lo >= hi) { chunks = k; break; }
+            rccl.push_back(Chunk{ lo, hi });
+        }
+        bool same = got.size() == finish.size() && got.size() == rccl.size();
+        for (size_t k = 0; same && k < got.size(); ++k) same = got[k].lo == finish[k].lo && got[k].hi == finish[k].hi && got[k].lo == rccl[k].lo && got[k].hi == rccl[k].hi;
+        CHECK(same, "%zu chunks, %zu and %zu before", got.size(), finish.size(), rccl.size());
+        bool tiles = !got.empty() && got.front().lo == 0 && got.back().hi == strideBytes, whole = true;
+        for (size_t k = 0; k < got.size(); ++k) {
+            tiles = tiles && got[k].lo < got[k].hi && (k == 0 || got[k].lo == got[k - 1].hi);
+            whole = whole && (k + 1 == got.size() || (got[k].hi - got[k].lo) % 256 == 0);
+        }
+        CHECK(tiles, "the chunks tile [0, %llu) without gap or overlap", (unsigned long long)strideBytes);
+        CHECK(whole, "every chunk but the last is a multiple of 256 bytes");
+        CHECK(got.size() <= kShardMaxChunks, "%zu chunks (one event each)", got.size());
+    }
+    CHECK(shard_chunk_bytes(M, 0) == M && shard_chunk_bytes(M + 256, 0) == M / 2 + 256, "one chunk up to 64 MiB, two from there");
+    CHECK(shard_chunk_bytes(8 * M, 0) == M && shard_chunk_bytes(8 * M + 256, 0) == M + 256, "eight chunks of 64 MiB, then eight larger ones");
+    CHECK(shard_chunk_bytes(4352 * 3, 4352) == 4352 && shard_chunk_bytes(4352 * 3, 256) == 1792, "the knob sets the size, the eight chunks bound it");
+}
+
+static void exchange_arena()
+{
+    const uint32_t worlds[3] = { 1, 2, 16 };
+    const uint64_t strides[2] = { 256, 1ull << 20 };
+    for (int asyncBegin = 0; asyncBegin < 2; ++asyncBegin) for (uint32_t world : worlds) for (uint64_t strideBytes : strides) {
+        const size_t scratchWanted = 4 * (size_t)(strideBytes / 4096) + 1234;   // (stands for shard_codec_scratch_bytes: no multiple of 256)
+        const ExchangeArena sized = carve_exchange_arena(0, strideBytes, world, asyncBegin != 0, scratchWanted);
+        // what sharded_tail summed by hand, and where its six takes landed
+        const size_t gatherBytes = asyncBegin ? (size_t)strideBytes * world + 4096 : 0;
+        const size_t compCap = asyncBegin ? p256((size_t)(strideBytes / 2) + 4096) : 0;
+        const size_t codecScratchBytes = asyncBegin ? p256(scratchWanted) : 0;
+        const size_t codecBytes = asyncBegin ? compCap * (world + 1) + 1024 + codecScratchBytes : 0;
+        CHECK(sized.bytes == (size_t)strideBytes + 256 + gatherBytes + codecBytes, "%zu bytes reserved, %zu before", sized.bytes, (size_t)strideBytes + 256 + gatherBytes + codecBytes);
+        const size_t dGathered = p256((size_t)strideBytes), dComp = dGathered + p256(gatherBytes), dGatherComp = dComp + p256(compCap), dCompSize = dGatherComp + p256(compCap * world), dCodecScratch = dCompSize + 256;
+        if (asyncBegin) CHECK(sized.contrib == nullptr && (size_t)sized.gathered == dGathered && (size_t)sized.comp == dComp && (size_t)sized.gatherComp == dGatherComp && (size_t)sized.compSize == dCompSize &&
+                              (size_t)sized.codecScratch == dCodecScratch && sized.compCap == compCap && sized.codecScratchBytes == codecScratchBytes, "the offsets of the six takes");
+        else CHECK(!sized.contrib && !sized.gathered && !sized.comp && !sized.gatherComp && !sized.compSize && !sized.codecScratch && !sized.compCap && !sized.codecScratchBytes, "the synchronous form has the contribution only");
+        uint8_t* block = (uint8_t*)aligned_alloc(256, sized.bytes);   // (exact size: a slot that runs over is the sanitizer's to report)
+        const ExchangeArena x = carve_exchange_arena((uintptr_t)block, strideBytes, world, asyncBegin != 0, scratchWanted);
+        CHECK(block != nullptr && x.contrib == block && x.bytes == sized.bytes && x.compCap == sized.compCap && x.codecScratchBytes == sized.codecScratchBytes &&
+              (!asyncBegin || (x.gathered == block + dGathered && x.comp == block + dComp && x.gatherComp == block + dGatherComp && (uint8_t*)x.compSize == block + dCompSize && x.codecScratch == block + dCodecScratch)),
+              "both passes agree");
+        std::vector<Region> r = { { "contrib", (uintptr_t)x.contrib, (size_t)strideBytes } };
+        if (asyncBegin) {
+            r.push_back(Region{ "gathered", (uintptr_t)x.gathered, gatherBytes }); r.push_back(Region{ "comp", (uintptr_t)x.comp, compCap }); r.push_back(Region{ "gatherComp", (uintptr_t)x.gatherComp, compCap * world });
+            r.push_back(Region{ "compSize", (uintptr_t)x.compSize, 4 }); r.push_back(Region{ "codecScratch", (uintptr_t)x.codecScratch, codecScratchBytes });
+        }
+        bool apart = r.back().at + p256(r.back().bytes) + (asyncBegin ? 1024 : 256) == (uintptr_t)block + x.bytes;   // (the slots are in carve order; the arena's slack lies behind the last)
+        for (size_t k = 0; k < r.size(); ++k) { apart = apart && r[k].at % 256 == 0 && (k + 1 == r.size() || r[k].at + r[k].bytes <= r[k + 1].at); memset((void*)r[k].at, (int)k + 1, r[k].bytes); }
+        CHECK(apart, "slots are aligned, disjoint and end the reservation's slack before its end");
+        CHECK(x.contrib[strideBytes - 1] == 1 && (!asyncBegin || (x.gathered[gatherBytes - 1] == 2 && x.codecScratch[codecScratchBytes - 1] == 6)), "every slot was written end to end");
+        free(block);
+    }
+}
+
+static void meta_share_and_send_rules()
+{
+    const size_t wordCounts[5] = { 0, 1, 4, 7, 4 * (size_t)1000003 };
+    const uint32_t worlds[5] = { 1, 2, 3, 8, 16 };
+    for (size_t metaWords : wordCounts) for (uint32_t N : worlds) {
+        size_t end = 0;
+        for (uint32_t r = 0; r < N; ++r) {
+            size_t lo = 99, hi = 99; meta_sum_share(metaWords, r, N, &lo, &hi);
+            CHECK(lo == metaWords * r / N && hi == metaWords * (r + 1) / N && lo == end && hi >= lo, "share of rank %u of %u in %zu words", r, N, metaWords);
+            end = hi;
+        }
+        CHECK(end == metaWords, "the shares of %u ranks tile [0, %zu)", N, metaWords);
+    }
+    // a rank's stream of cap 1000 whose tables end at byte 100, next to a contribution of 777 bytes
+    const uint64_t sizes[6] = { 0, 99, 100, 101, 1000, 1001 };
+    for (uint64_t streamBytes : sizes) {
+        const uint64_t cap = 1000, offRaw = 100, total = 777;
+        const bool raw = streamBytes > cap || streamBytes < offRaw;
+        const uint64_t take = raw ? total : streamBytes;
+        const RankSend s = rank_send(streamBytes, cap, offRaw, total);
+        CHECK(s.raw == raw && s.bytes == take && s.raw == (streamBytes < 100 || streamBytes > 1000), "a stream of %llu bytes", (unsigned long long)streamBytes);
+    }
+}
+
+static void scatter_cut_case(const std::vector<uint32_t>& hSizes, const std::vector<uint32_t>& want)
+{
+    const uint32_t E = (uint32_t)hSizes.size();
+    std::vector<uint32_t> cut; cut.push_back(0);
+    uint64_t acc = 0; for (uint32_t j = 0; j < E; ++j) { acc += hSizes[j]; if (acc >= ((uint64_t)2 << 20)) { cut.push_back(j + 1); acc = 0; } }
+    if (cut.back() != E) cut.push_back(E);
+    const std::vector<uint32_t> got = scatter_cuts(hSizes.data(), E);
+    CHECK(got == cut, "%u blocks: %zu cuts, %zu before", E, got.size(), cut.size());
+    CHECK(got == want, "%u blocks: %zu cuts, %zu expected", E, got.size(), want.size());
+    bool sound = got.front() == 0 && got.back() == E && (E ? got.size() >= 2 : got.size() == 1);
+    for (size_t t = 0; t + 1 < got.size(); ++t) {
+        uint64_t bytes = 0; for (uint32_t j = got[t]; j < got[t + 1]; ++j) bytes += hSizes[j];
+        sound = sound && got[t] < got[t + 1] && (t + 2 == got.size() || bytes >= (2u << 20));
+    }
+    CHECK(sound, "%u blocks: first cut 0, last cut E, no empty range, at least 2 MiB in every range but the last", E);
+}
+static void scatter_cut_rules()
+{
+    const uint32_t K = 512u << 10;
+    scatter_cut_case({}, { 0 });
+    scatter_cut_case({ 16 }, { 0, 1 });
+    scatter_cut_case({ 4u << 20 }, { 0, 1 });
+    scatter_cut_case(std::vector<uint32_t>(1000, 16u), { 0, 1000 });
+    scatter_cut_case({ K, K, K, K }, { 0, 4 });                   // 2 MiB exactly on the last block: no empty range behind it
+    scatter_cut_case({ K, K, K, K, K, K, K, K }, { 0, 4, 8 });
+    scatter_cut_case({ K, K, K, K - 16, 16, K }, { 0, 5, 6 });
+}
+
 int main()
 {
     index_formats();
@@ -389,6 +542,11 @@ int main()
     interleave_rules();
     states_carve();
     readback_and_small_rules();
+    shard_rank_and_stride_rules();
+    shard_chunk_rules();
+    exchange_arena();
+    meta_share_and_send_rules();
+    scatter_cut_rules();
     printf("ok %ld\n", g_checks);
     return 0;
 }

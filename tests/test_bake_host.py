@@ -3,7 +3,9 @@ triangle upload and the carve of the working set -- a stand-alone program, tests
 is run twice per shape, from a null base (the size to reserve) and over an exact-size heap block that every slot is then filled in: a slot that is not
 aligned, overlaps another, runs over the reservation, or breaks one of the two adjacency contracts (counters + digest table, the read-back span) stops it.
 The decisions and layouts that bake_core's stages take from that header -- rank ranges, the ranges of a streamed result, the deferred generic pass, the
-interleave stride, the carve of the states arena, the read-back slots -- are each held to the expression they replaced, restated in the program."""
+interleave stride, the carve of the states arena, the read-back slots -- are each held to the expression they replaced, restated in the program; so are
+the rules of the sharded bake: rank validity, contribution stride, the chunk walk of the exchange, the exchange arena (carved and written like the
+working set), each rank's share of the metadata sum, raw or stream, the cuts of the host scatter."""
 import os
 import subprocess
 
@@ -39,4 +41,16 @@ def test_bake_host_rules_and_working_set_carve(tmp_path):
     # read-back slots: 6 spans, 2 + 2 at the block size; launches: no / each / every level (15) + 3 values; 6 + 1 waits; 3 digest bounds
     readback_and_small = 6 + 2 + 2 + 15 + 3 + 6 + 1 + 3
     stages = rank_ranges + stream_ranges + generic_pass + interleave + states_carve + readback_and_small
-    assert int(r.stdout.split()[1]) == index_formats + histograms + result_descs + raw_inputs + carve + stages
+    # the sharded bake's rules, each against the expression it had inline:
+    # rank validity over worlds and ranks 0..17, 2 limits; the stride at 6 largest totals x 5 worlds, and the 6 strides themselves
+    rank_and_stride = 18 * 18 + 2 + 6 * 5 + 6
+    # 7 strides x 3 knob values: the chunk size, the walk against both loops it replaced, it tiles the stride, multiples of 256, at most 8 chunks; 3 of the sizes' meaning
+    chunks = 7 * 3 * 5 + 3
+    # exchange arena, async on / off x 3 worlds x 2 strides: the reservation, the offsets, both passes, the slots apart, each written end to end
+    exchange_arena = 2 * 3 * 2 * 5
+    # meta-sum share: 5 word counts x (30 ranks of 5 worlds + the 5 tilings); raw or stream at 6 stream sizes
+    meta_share_and_send = 5 * (30 + 5) + 6
+    # 7 lists of block sizes: the cuts against the loop they replaced, against the expected ones, and their properties
+    scatter_cuts = 7 * 3
+    sharded = rank_and_stride + chunks + exchange_arena + meta_share_and_send + scatter_cuts
+    assert int(r.stdout.split()[1]) == index_formats + histograms + result_descs + raw_inputs + carve + stages + sharded
